@@ -22,9 +22,16 @@ per-sample-latency mode (one sample over 2 CFG halves x up to 4 frame groups, RC
 in the same run: RCCL rank count, exchanges and bytes sent per rank and step.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the whole step against the dense fp16 MFMA peak using the
-ALGORITHMIC 96.59 TFLOP/step of SURVEY.md §8(d); `roofline.kernels` is a per-kernel-family breakdown from a
-HIP-event-instrumented extra step (same process, not part of the timed region); `cpu_baseline` is the CPU
-oracle (a port of the reference's op graph, faithful mode) on a bounded sample on this host's cores.
+ALGORITHMIC 96.59 TFLOP/step of SURVEY.md §8(d).
+
+A plain run only sets up, warms up, times `--steps` steps and prints the line.  `--full` adds everything else the benchmark
+measures or checks: the parity guard against the golden pins, `roofline.clocks` (sampled shader clock), `roofline.kernels` (a
+per-kernel-family breakdown from a HIP-event-instrumented extra step, not part of the timed region), `modes` (the other operand
+policy timed too), `cpu_baseline` (the CPU oracle, a port of the reference's op graph in faithful mode, on this host's cores) and,
+for N > 1 with `--parallelism auto`, the strong-scaling records.
+
+`--dump-outputs DIR` writes what the timed path computed in its last timed step (the sampler's latent: DIR/x.npy, float32;
+DIR/x_rank<r>.npy per rank for N > 1) so that two builds can be compared output for output; the inputs are seeded.
 """
 from __future__ import annotations
 
@@ -57,6 +64,25 @@ GOLDEN_PIN_CFG5 = ("full_cfg5_step0.npz", 999, 0)
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_ELEMENTS = 4 << 20           # per array: 16 MB of float32; a larger output is written as a fixed, seeded sample
+
+
+def dump_output(dirpath, name, t):
+    """`--dump-outputs`: one output of the timed path as DIR/<name>.npy in float32.  An output above DUMP_MAX_ELEMENTS is written
+    as the elements at a fixed, seeded set of flat indices (sorted; the same for every build and run of one shape)."""
+    import numpy as np
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    a = t.detach().float().cpu().reshape(-1)
+    if a.numel() > DUMP_MAX_ELEMENTS:
+        idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMENTS].sort().values
+        a = a[idx]
+    else:
+        a = a.reshape(t.shape)
+    np.save(d / f"{name}.npy", a.numpy())
+    log(f"dump: {d / name}.npy {tuple(a.shape)} float32")
 
 
 def E_precision_name(p):
@@ -168,22 +194,13 @@ def run_vae_decode(args, dev):
         sync()
         dt = (time.perf_counter() - t0) / args.steps
         assert img.shape == oshape and torch.isfinite(img).all()
-        prof = hip.Profiler()
-        hip.set_profiler(prof)
-        run(z)
-        hip.set_profiler(None)
-    summ = prof.summary()
-    flops = sum(v["flops"] for v in summ.values())
-    tot = sum(v["ms"] for v in summ.values())
-    kern = {}
-    for fam, v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"]):
-        e = {"launches": v["launches"], "ms": round(v["ms"], 3), "share": round(v["ms"] / tot, 4)}
-        if v["flops"]:
-            e["TFLOP/s"] = round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)
-        elif v["bytes"]:
-            e["GB/s"] = round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 0)
-        kern[fam] = e
-    ach = flops / dt / 1e12
+        if args.dump_outputs:
+            dump_output(args.dump_outputs, "moments" if enc else "image", img)
+        if args.full:
+            prof = hip.Profiler()
+            hip.set_profiler(prof)
+            run(z)
+            hip.set_profiler(None)
     what = "encodes" if enc else "decodes"
     out = {"metric": f"first-stage {what}/s (8 frames x 6 views x 256x512)", "value": 1.0 / dt, "unit": f"{what}/s",
            "n_gpus": 1, "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": dt * 1e3,
@@ -191,12 +208,25 @@ def run_vae_decode(args, dev):
            "config": {"workload": ("AutoencoderKL.encode moments" if enc else "AutoencoderKL.decode") +
                       " (ch 128, mult 1-2-4-4, 2 res blocks, mid attention over 12288 tokens): " +
                       ("(8, 3, 256, 3072) -> (8, 8, 32, 384)" if enc else "(8, 4, 32, 384) -> (8, 3, 256, 3072)"),
-                      "stage": args.stage},
-           "roofline": {"bound": "mfma", "achieved": ach, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": ach / MFMA_PEAK_TFLOPS, "traffic": None,
-                        "basis": f"{flops / 1e12:.2f} TFLOP per {what[:-1]} (2MNK of every contraction launched) / measured time",
-                        "kernels": kern, "kernel_ms_sum": round(tot, 2)}}
-    if not args.no_cpu_baseline:
+                      "stage": args.stage}}
+    if args.full:
+        summ = prof.summary()
+        flops = sum(v["flops"] for v in summ.values())
+        tot = sum(v["ms"] for v in summ.values())
+        kern = {}
+        for fam, v in sorted(summ.items(), key=lambda kv: -kv[1]["ms"]):
+            e = {"launches": v["launches"], "ms": round(v["ms"], 3), "share": round(v["ms"] / tot, 4)}
+            if v["flops"]:
+                e["TFLOP/s"] = round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)
+            elif v["bytes"]:
+                e["GB/s"] = round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 0)
+            kern[fam] = e
+        ach = flops / dt / 1e12
+        out["roofline"] = {"bound": "mfma", "achieved": ach, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                           "frac": ach / MFMA_PEAK_TFLOPS, "traffic": None,
+                           "basis": f"{flops / 1e12:.2f} TFLOP per {what[:-1]} (2MNK of every contraction launched) / measured time",
+                           "kernels": kern, "kernel_ms_sum": round(tot, 2)}
+    if args.cpu_baseline != "none":
         from oracle import vae_oracle as vo
         g5 = torch.Generator().manual_seed(5)
         zs = torch.tanh(torch.randn(1, 3, 128, 768, generator=g5)) if enc else torch.randn(1, 4, 16, 96, generator=g5) * 2.0
@@ -387,6 +417,8 @@ def run_text_tower(args, dev):
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
     assert out.shape == (2, 77, 1024) and torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "text_embedding", out)
     flops = 23 * (2.0 * 154 * 1024 * (3 * 1024 + 1024 + 8 * 1024) + 2 * 16 * 4.0 * 77 * 77 * 64)
     print(json.dumps({"metric": "text-tower encodes/s (OpenCLIP ViT-H/14 text side, 2 prompts x 77 tokens)", "value": 1.0 / dt,
                       "unit": "encodes/s", "n_gpus": 1, "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": dt * 1e3,
@@ -432,7 +464,7 @@ def main():
     ap.add_argument("--num-sampling-steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "step", "sample", "none"],
-                    help="CPU oracle leg (N = 1 only): auto = bounded sample, then ONE whole step when it fits ~8 min")
+                    help="CPU oracle leg (N = 1, --full only): auto = bounded sample, then ONE whole step when it fits ~8 min")
     ap.add_argument("--precision", default="precise", choices=["fast", "precise", "precise-all", "precise-lite", "precise-f16lo"],
                     help="operand policy of the timed region (DESIGN §6).  precise (default) meets eps max-abs < 1e-3; the "
                          "other of fast / precise is timed too and reported under `modes`")
@@ -489,8 +521,13 @@ def main():
     ap.add_argument("--hoist", action="store_true",
                     help="sampler mode (SURVEY §8 f1): text K/V + ControlNet hint stem computed once per schedule, outside "
                          "the timed steps.  NOT the headline: the default re-evaluates the whole path every step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: parity guard, clock sampling, kernel breakdown, the other operand "
+                         "policy, the CPU baseline and (N > 1, --parallelism auto) the strong-scaling records")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
-    if args.no_cpu_baseline:
+    if args.no_cpu_baseline or not args.full:
         args.cpu_baseline = "none"
     if args.yaml_exact:
         args.num_sampling_steps = 25
@@ -634,7 +671,7 @@ def main():
         """eps of one network call at BASELINE config 3 vs the REFERENCE's own fp32 forward, at every committed pin (three noise
         levels, two input seeds); the headline numbers are the WORST over the pins"""
         if not (args.config == "full" and T in (1, 8) and rank == 0 and GOLDEN_FULL.exists()) or shard is not None or vshard is not None \
-                or args.no_parity:
+                or args.no_parity or not args.full:
             return None          # (a frame-sharded network runs collectives: no single-rank evaluation)
         import numpy as np
         net.diffusion_model.precision = prec
@@ -689,7 +726,7 @@ def main():
             sync()
         barrier()
         sync()
-        clocks = ClockSampler(dev.index or 0) if dev.type == "cuda" and rank == 0 else None
+        clocks = ClockSampler(dev.index or 0) if dev.type == "cuda" and rank == 0 and args.full else None
         if clocks is not None:
             clocks.__enter__()
         t_start = time.perf_counter()
@@ -706,6 +743,8 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = tt.item()
     assert torch.isfinite(xx).all()
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "x" if world == 1 else f"x_rank{rank}", xx)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = layout.samples * args.steps / elapsed    # every rank (group) advances its own sample by `steps`
@@ -775,7 +814,7 @@ def main():
     if args.emulate_kernels:
         out["emulated_kernels"] = True
         out["metric"] += " [HARNESS SELF-TEST on the CPU emulation of the C-ABI: not a measurement]"
-    if args.parallelism == "auto" and world > 1 and world % 2 == 0:
+    if args.full and args.parallelism == "auto" and world > 1 and world % 2 == 0:
         # The secondary modes must never cost the headline: they run collectives that no multi-GPU node has exercised for the
         # builder.  An exception is recorded in the line; a HANG (a rank lost inside a collective) is cut by a watchdog that
         # prints the headline line with the failure noted and ends the process.
@@ -825,7 +864,7 @@ def main():
                                      "MB_sent_per_rank_and_step": round(nb / max(1, nsteps) / 1e6, 1),
                                      "note": "engine.ViewShard: conv halos, panorama GroupNorm statistics, neighbour views (DESIGN.md §9)"}
 
-    if rank == 0 and not args.no_kernel_breakdown and layout.per_sample == 1 and not args.emulate_kernels:
+    if args.full and rank == 0 and not args.no_kernel_breakdown and layout.per_sample == 1 and not args.emulate_kernels:
         prof = hip.Profiler()
         hip.set_profiler(prof)
         two = net.diffusion_model.two_stream
@@ -864,7 +903,8 @@ def main():
                 "note": "one-stream instrumented step (HIP events on the launch stream); rocprofv3 --kernel-trace --stats of "
                         "`bench.py --one-stream` is committed under profiles/ for the same build"}
     # the other operand policy, same steps: the judge and the reader see what the tolerance costs
-    if rank == 0 and world == 1 and args.config == "full" and args.precision in ("fast", "precise") and not args.no_modes and T == 8:
+    if args.full and rank == 0 and world == 1 and args.config == "full" and args.precision in ("fast", "precise") and not args.no_modes \
+            and T == 8:
         other = "fast" if args.precision == "precise" else "precise"
         net.diffusion_model.precision = other
         with torch.no_grad():

@@ -19,7 +19,10 @@ REF = Path("/root/reference")
 
 
 def available() -> bool:
-    return (REF / "sgm" / "modules" / "attention.py").exists()
+    try:
+        return (REF / "sgm" / "modules" / "attention.py").exists()
+    except OSError:              # a tree this user may not enter counts as absent
+        return False
 
 
 def import_reference():
