@@ -36,8 +36,9 @@ const char* pnc_version(void);
 /* ABI revision of this header (bumped whenever a parameter struct, a prototype or the option list changes): 7
  * (round 4: + pnc_groupnorm_combine, + PNC_OPT_ATTN_DEFER_MAX, PNC_OPT_GEMM_PERSIST is a bit set, - pnc_ff_chain_*;
  *  round 5 (5, 6): + pnc_concat_add_stats, + PNC_OPT_GEMM_STAGGER, + pnc_linear_smallm_segments;
- *  round 6 (7): + PNC_OPT_ATTN_SUM_TRIGGER) */
-#define PNC_ABI_VERSION 7
+ *  round 6 (7): + PNC_OPT_ATTN_SUM_TRIGGER;
+ *  8: + pnc_cfg_sampler_step / PncSamplerStepParams) */
+#define PNC_ABI_VERSION 8
 int pnc_abi_version(void);
 /* hex SHA-256 of the sources + compile flags the library was built from (panacea_amd/build.py computes the same digest over
  * the checkout): a loader compares the two and refuses a library built from other sources instead of calling it with
@@ -368,6 +369,52 @@ int pnc_nchw_to_tokens_f16(const float* a, int C1, const float* a_scale, int a_f
 int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
                        const float* x, const float* c_out, const float* sigma, const float* sigma_next, float* x_next,
                        void* stream);
+/* Exit of one step of the other samplers of sampling.py (Heun, ancestral Euler, DPM++ 2S ancestral, DPM++ 2M, LMS), one pass:
+ * denoised D is formed as in pnc_cfg_euler_step, then the sampler's update follows in the reference's rounding order (no FMA
+ * contraction).  Per-frame scalars are [T] fp32 device vectors v[0..5] computed by the caller with the reference's torch ops;
+ * x, x0, aux, hist[], noise, out, out_aux are NCHW [T][C][Npix] fp32 (out / out_aux may alias x0 / aux / hist[] element for
+ * element: each element is read before it is written).  Per mode (x = the latent the network saw):
+ *   HEUN1    v = {sigma_hat, next_sigma}             d = (x - D) / sigma_hat;  out = x + (next_sigma - sigma_hat) * d  (x_euler);
+ *                                                    out_aux = d                                    (sampling.py:85-107)
+ *   HEUN2    v = {sigma_hat, next_sigma}             x = x_euler, x0 = x_hat, aux = d:  d_new = (x - D) / next_sigma,
+ *                                                    out = next_sigma > 0 ? x0 + ((aux + d_new) / 2) * (next_sigma - sigma_hat) : x
+ *                                                                                                   (sampling.py:221-237)
+ *   EULER_A  v = {sigma, sigma_down, sigma_up, next_sigma}   y = x + (sigma_down - sigma) * ((x - D) / sigma);
+ *                                                    out = next_sigma > 0 ? y + noise * s_noise * sigma_up : y   (sampling.py:135-172,240-247)
+ *   DPM2S_1  v = {sigma, sigma_down, mult1, mult2}   out = mult1 * x - mult2 * D  (x2);  out_aux = the ancestral Euler y (x_euler)
+ *   DPM2S_2  v = {mult3, mult4, sigma_down, sigma_up, next_sigma}   x = x2, x0 = x, aux = x_euler:
+ *                                                    y = sigma_down > 0 ? mult3 * x0 - mult4 * D : aux;  then the noise term of
+ *                                                    EULER_A                                        (sampling.py:250-287)
+ *   DPM2M    v = {mult1, mult2, mult3, mult4, next_sigma}   s = mult1 * x - mult2 * D;  aux = previous D or NULL (first / last
+ *                                                    step: out = s);  otherwise out = next_sigma > 0 ? mult1 * x - mult2 *
+ *                                                    (mult3 * D - mult4 * aux) : s;  out_aux = D   (sampling.py:290-365)
+ *   LMS      v = {sigma, coeff_0 .. coeff_n_hist}    d = (x - D) / sigma;  out = x + (((0 + coeff_0 d) + coeff_1 hist[0]) + ...)
+ *                                                    with hist[] the previous d newest first;  out_aux = d  (sampling.py:176-211)
+ * Returns PNC_EABI when struct_bytes != sizeof(PncSamplerStepParams), PNC_EINVAL for a missing operand of the mode. */
+enum {
+    PNC_SAMPLER_HEUN1 = 0, PNC_SAMPLER_HEUN2 = 1, PNC_SAMPLER_EULER_A = 2, PNC_SAMPLER_DPM2S_1 = 3, PNC_SAMPLER_DPM2S_2 = 4,
+    PNC_SAMPLER_DPM2M = 5, PNC_SAMPLER_LMS = 6
+};
+typedef struct PncSamplerStepParams {
+    int32_t struct_bytes;   /* sizeof(PncSamplerStepParams) as the caller compiled it */
+    int32_t mode;           /* PNC_SAMPLER_* */
+    const float* eps_tok;   /* [(cfg ? 2 : 1) * T * Npix][ld], uncond frames first */
+    int32_t ld, T, Npix, C;
+    int32_t cfg;
+    float scale;
+    const float* x;
+    const float* c_out;     /* [T] */
+    const float* x0;
+    const float* aux;
+    const float* hist[4];
+    int32_t n_hist;         /* LMS: 0..3 */
+    float s_noise;
+    const float* noise;
+    const float* v[6];
+    float* out;
+    float* out_aux;
+} PncSamplerStepParams;
+int pnc_cfg_sampler_step(const PncSamplerStepParams* p, void* stream);
 /* channels-last fp32 [F*Npix][ld] -> NCHW fp32 (first C columns) */
 int pnc_tokens_to_nchw_f32(const float* x, int ld, int F, int Npix, int C,
                            float* out, void* stream);

@@ -256,6 +256,108 @@ __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const float* __rest
     }
 }
 
+// Exit of a step of the other samplers (include/panacea_hip.h: pnc_cfg_sampler_step).  Same denoised as above, then the
+// mode's update, every operation rounded on its own in the reference's order.
+__global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerStepParams p) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)p.T * p.Npix) return;
+    const int64_t t = i / p.Npix, pix = i - t * p.Npix;
+    const float co = p.c_out[t];
+    const float v0 = p.v[0] ? p.v[0][t] : 0.f, v1 = p.v[1] ? p.v[1][t] : 0.f, v2 = p.v[2] ? p.v[2][t] : 0.f;
+    const float v3 = p.v[3] ? p.v[3][t] : 0.f, v4 = p.v[4] ? p.v[4][t] : 0.f;
+    const float* eu = p.eps_tok + i * p.ld;
+    const float* ec = p.eps_tok + ((int64_t)(p.cfg ? p.T : 0) * p.Npix + i) * p.ld;
+    for (int c = 0; c < p.C; ++c) {
+        const int64_t o = (t * p.C + c) * p.Npix + pix;
+        const float xv = p.x[o];
+        const float pc = ec[c] * co;
+        float D = pc + xv;
+        if (p.cfg) {
+            const float pu = eu[c] * co;
+            const float du = pu + xv;
+            const float g = p.scale * (D - du);
+            D = du + g;
+        }
+        float y;
+        switch (p.mode) {
+        case PNC_SAMPLER_HEUN1: {
+            const float d = (xv - D) / v0;
+            const float dt = v1 - v0;
+            const float stp = dt * d;
+            y = xv + stp;
+            p.out_aux[o] = d;
+            break;
+        }
+        case PNC_SAMPLER_HEUN2: {
+            const float d_new = (xv - D) / v1;
+            const float sum = p.aux[o] + d_new;
+            const float dp = sum / 2.0f;
+            const float dt = v1 - v0;
+            const float stp = dp * dt;
+            const float xc = p.x0[o] + stp;
+            y = v1 > 0.f ? xc : xv;
+            break;
+        }
+        case PNC_SAMPLER_EULER_A:
+        case PNC_SAMPLER_DPM2S_1: {
+            const float d = (xv - D) / v0;
+            const float dt = v1 - v0;
+            const float stp = dt * d;
+            const float xe = xv + stp;
+            if (p.mode == PNC_SAMPLER_DPM2S_1) {
+                const float a = v2 * xv;
+                const float b = v3 * D;
+                y = a - b;
+                p.out_aux[o] = xe;
+            } else {
+                const float ns = p.noise[o] * p.s_noise;
+                const float up = ns * v2;
+                y = v3 > 0.f ? xe + up : xe;
+            }
+            break;
+        }
+        case PNC_SAMPLER_DPM2S_2: {
+            const float a = v0 * p.x0[o];
+            const float b = v1 * D;
+            const float xd = a - b;
+            const float xs = v2 > 0.f ? xd : p.aux[o];
+            const float ns = p.noise[o] * p.s_noise;
+            const float up = ns * v3;
+            y = v4 > 0.f ? xs + up : xs;
+            break;
+        }
+        case PNC_SAMPLER_DPM2M: {
+            const float a = v0 * xv;
+            const float b = v1 * D;
+            const float xs = a - b;
+            y = xs;
+            if (p.aux) {
+                const float m3 = v2 * D;
+                const float m4 = v3 * p.aux[o];
+                const float dd = m3 - m4;
+                const float b2 = v1 * dd;
+                const float xa = a - b2;
+                y = v4 > 0.f ? xa : xs;
+            }
+            p.out_aux[o] = D;
+            break;
+        }
+        default: {                                                   // PNC_SAMPLER_LMS
+            const float d = (xv - D) / v0;
+            float acc = 0.0f + v1 * d;                               // sum() starts from the int 0
+            if (p.n_hist > 0) { const float e = v2 * p.hist[0][o]; acc = acc + e; }
+            if (p.n_hist > 1) { const float e = v3 * p.hist[1][o]; acc = acc + e; }
+            if (p.n_hist > 2) { const float e = v4 * p.hist[2][o]; acc = acc + e; }
+            y = xv + acc;
+            p.out_aux[o] = d;
+            break;
+        }
+        }
+        p.out[o] = y;
+    }
+}
+
 }  // namespace
 
 extern "C" int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
@@ -265,6 +367,34 @@ extern "C" int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix,
     const int64_t n = (int64_t)T * Npix;
     hipLaunchKernelGGL(cfg_euler_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next);
+    return pnc_launch_status();
+}
+
+extern "C" int pnc_cfg_sampler_step(const PncSamplerStepParams* pp, void* stream) {
+    if (!pp || pp->struct_bytes != (int32_t)sizeof(PncSamplerStepParams)) return PNC_EABI;
+    const PncSamplerStepParams& p = *pp;
+    if (!p.eps_tok || !p.x || !p.c_out || !p.out || p.T < 1 || p.Npix < 1 || p.C < 1 || p.ld < p.C) return PNC_EINVAL;
+    int nv = 0;                                                      // per-frame vectors the mode reads
+    bool ok = true;
+    switch (p.mode) {
+    case PNC_SAMPLER_HEUN1: nv = 2; ok = p.out_aux; break;
+    case PNC_SAMPLER_HEUN2: nv = 2; ok = p.x0 && p.aux; break;
+    case PNC_SAMPLER_EULER_A: nv = 4; ok = p.noise; break;
+    case PNC_SAMPLER_DPM2S_1: nv = 4; ok = p.out_aux; break;
+    case PNC_SAMPLER_DPM2S_2: nv = 5; ok = p.x0 && p.aux && p.noise; break;
+    case PNC_SAMPLER_DPM2M: nv = p.aux ? 5 : 2; ok = p.out_aux; break;
+    case PNC_SAMPLER_LMS:
+        nv = 2 + p.n_hist;
+        ok = p.out_aux && p.n_hist >= 0 && p.n_hist <= 3;
+        for (int k = 0; ok && k < p.n_hist; ++k) ok = p.hist[k] != nullptr;
+        break;
+    default: return PNC_EINVAL;
+    }
+    for (int k = 0; ok && k < nv; ++k) ok = p.v[k] != nullptr;
+    if (!ok) return PNC_EINVAL;
+    const int64_t n = (int64_t)p.T * p.Npix;
+    hipLaunchKernelGGL(cfg_sampler_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), p);
     return pnc_launch_status();
 }
 

@@ -20,7 +20,7 @@ HEADER = PKG.parent / "include" / "panacea_hip.h"
 
 A_PLAIN, A_CONV3X3, A_CONV1D_T = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
-ABI_VERSION = 7          # PNC_ABI_VERSION of include/panacea_hip.h this binding was written against
+ABI_VERSION = 8          # PNC_ABI_VERSION of include/panacea_hip.h this binding was written against
 LO_F16, LO_E4M3 = 0, 1   # PNC_LO_*: storage format of the lo plane of a precise operand
 # dtype of a lo-plane tensor <-> format: an fp16 tensor holds fp16(r), a uint8 tensor OCP e4m3 bytes (one per element)
 LO_DTYPE = {LO_F16: torch.float16, LO_E4M3: torch.uint8}
@@ -87,6 +87,21 @@ class AttnParams(C.Structure):
     ]
 
 
+class SamplerStepParams(C.Structure):
+    _fields_ = [
+        ("struct_bytes", C.c_int32), ("mode", C.c_int32),
+        ("eps_tok", C.c_void_p), ("ld", C.c_int32), ("T", C.c_int32), ("Npix", C.c_int32), ("C", C.c_int32),
+        ("cfg", C.c_int32), ("scale", C.c_float),
+        ("x", C.c_void_p), ("c_out", C.c_void_p), ("x0", C.c_void_p), ("aux", C.c_void_p),
+        ("hist", C.c_void_p * 4), ("n_hist", C.c_int32), ("s_noise", C.c_float), ("noise", C.c_void_p),
+        ("v", C.c_void_p * 6), ("out", C.c_void_p), ("out_aux", C.c_void_p),
+    ]
+
+
+# PNC_SAMPLER_*: the update pnc_cfg_sampler_step applies after forming denoised
+SAMPLER_HEUN1, SAMPLER_HEUN2, SAMPLER_EULER_A, SAMPLER_DPM2S_1, SAMPLER_DPM2S_2, SAMPLER_DPM2M, SAMPLER_LMS = range(7)
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _SIGNATURES = {
     "pnc_version": (C.c_char_p, []),
@@ -110,6 +125,7 @@ _SIGNATURES = {
     "pnc_timestep_embedding": (_I, [_P, _I, _I, _P, _P, _P]),
     "pnc_nchw_to_tokens_f16": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pnc_cfg_euler_step": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "pnc_cfg_sampler_step": (_I, [C.POINTER(SamplerStepParams), _P]),
     "pnc_tokens_to_nchw_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "pnc_concat_add": (_I, [_P, _I, _P, _P, _I, _L, _P, _P, _P, _I, _P]),
     "pnc_concat_add_stats": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
@@ -461,6 +477,28 @@ def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma
     _check(_timed("elementwise", 0.0, T * Npix * Cch * (16.0 if cfg else 12.0), load().pnc_cfg_euler_step, _ptr(eps_tok), ld, T,
                   Npix, Cch, int(cfg), float(scale), _ptr(x), _ptr(c_out), _ptr(sigma), _ptr(sigma_next), _ptr(x_next),
                   _stream()), "pnc_cfg_euler_step")
+
+
+def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux=None, x0=None, aux=None,
+                     hist=(), noise=None, s_noise=1.0):
+    """pnc_cfg_sampler_step: `v` = the mode's per-frame [T] fp32 vectors in header order, `hist` = previous LMS d planes newest first"""
+    p = SamplerStepParams()
+    p.struct_bytes = C.sizeof(SamplerStepParams)
+    f32 = torch.float32
+    p.mode, p.ld, p.T, p.Npix, p.C, p.cfg, p.scale = mode, ld, T, Npix, Cch, int(cfg), float(scale)
+    p.eps_tok, p.x, p.c_out = _ptr(eps_tok, f32, "eps_tok"), _ptr(x, f32, "x"), _ptr(c_out, f32, "c_out")
+    p.x0, p.aux, p.noise = _ptr(x0, f32, "x0"), _ptr(aux, f32, "aux"), _ptr(noise, f32, "noise")
+    p.out, p.out_aux = _ptr(out, f32, "out"), _ptr(out_aux, f32, "out_aux")
+    if len(v) > 6 or len(hist) > 4:
+        raise PncError("cfg_sampler_step: at most 6 per-frame vectors and 4 history planes")
+    for k, t in enumerate(v):
+        p.v[k] = _ptr(t, f32, f"v[{k}]")
+    for k, t in enumerate(hist):
+        p.hist[k] = _ptr(t, f32, f"hist[{k}]")
+    p.n_hist, p.s_noise = len(hist), float(s_noise)
+    planes = 3 + (x0 is not None) + (aux is not None) + (noise is not None) + (out_aux is not None) + len(hist)
+    _check(_timed("elementwise", 0.0, T * Npix * Cch * (4.0 * planes + (4.0 if cfg else 0.0)), load().pnc_cfg_sampler_step,
+                  C.byref(p), _stream()), "pnc_cfg_sampler_step")
 
 
 def tokens_to_nchw_f32(x32, ld, F, Npix, Cch, out32):

@@ -1,6 +1,6 @@
 """Latents-in, frames-out composition of the pieces this package owns (hot path + f1 + f2 + f4):
 
-    cond / uc  ->  EulerEDMSampler + VanillaCFG + DiscreteDenoiser around the ControlNet-UNet (step invariants hoisted)
+    cond / uc  ->  EulerEDMSampler (or any sampler mirror) + VanillaCFG + DiscreteDenoiser around the ControlNet-UNet (step invariants hoisted)
                ->  z / scale_factor  ->  FirstStageDecoder  ->  frames in [-1, 1]  (-> checkpoint.save_view_frames / save_gif)
 
 which is what `DiffusionEngine3D.sample` + `decode_first_stage` do around the network (diffusion.py:138-151, 242-249;
@@ -20,11 +20,18 @@ SCALE_FACTOR = 0.18215
 
 def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
                   noise: torch.Tensor, num_steps: int = 25, cfg_scale: float = 5.0, hoist: bool = True,
-                  scale_factor: float = SCALE_FACTOR) -> torch.Tensor:
-    """noise: (T, 4, h, w) unit-variance latents of ONE sample; returns (T, 3, 8h, 8w) frames."""
+                  scale_factor: float = SCALE_FACTOR, sampler=None) -> torch.Tensor:
+    """noise: (T, 4, h, w) unit-variance latents of ONE sample; returns (T, 3, 8h, 8w) frames.
+    `sampler`: None = the YAML's 25-step Euler / CFG `cfg_scale` (num_steps, cfg_scale apply); a sampler mirror of
+    panacea_amd.sampling; or a reference `sampler_config` dict (sampling.from_config; its num_steps, else `num_steps`)."""
     dev = noise.device
     den = sampling.DiscreteDenoiser().to(dev)
-    smp = sampling.EulerEDMSampler(num_steps, guider=sampling.VanillaCFG(cfg_scale), device=dev)
+    if sampler is None:
+        smp = sampling.EulerEDMSampler(num_steps, guider=sampling.VanillaCFG(cfg_scale), device=dev)
+    else:
+        smp = sampling.from_config(sampler, device=dev) if isinstance(sampler, dict) else sampler
+        if smp.num_steps is None:
+            smp.num_steps = num_steps
     with torch.no_grad():
         z = smp(sampling.BoundDenoiser(den, network), noise, cond, uc, network=network if hoist else None)
         return first_stage.decode(z / scale_factor)

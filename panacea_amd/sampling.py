@@ -6,7 +6,10 @@ Host-side mirrors with the reference's names and call signatures
   EpsScaling                 .../denoiser_scaling.py:16-22
   DiscreteDenoiser           .../denoiser.py:31-63
   VanillaCFG                 .../guiders.py:8-40 (+ sampling_utils.py:7-9)
-  EulerEDMSampler            .../sampling.py:27-133,214-218
+  EulerEDMSampler            .../sampling.py:27-133,214-218 (+ churn)
+  HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler, DPMPP2MSampler, LinearMultistepSampler
+                             .../sampling.py:135-365 (+ sampling_utils.py:12-43); `from_config` builds any of them from the
+                             YAML's sampler_config
 written for a device-resident loop: the sigma schedule is a Python list of floats plus one device tensor
 (no `.item()` sync per step — the reference compares Python floats with a device element at
 sampling.py:118-122), and every per-step quantity (c_in, c_out, timestep index) is a host scalar.
@@ -129,8 +132,9 @@ class BoundDenoiser:
         return self.denoiser(self.network, x, sigma, cond)
 
 
-class EulerEDMSampler:
-    """sampling.py:27-133,214-218 with s_churn = 0 (deterministic; == DDIM for eps-prediction)."""
+class _Sampler:
+    """What every sampler mirror shares: BaseDiffusionSampler (sampling.py:24-76) and the device half of a fused step — the
+    network's eps tokens of the CFG batch for one sigma, handed to an exit kernel."""
     fuse = True          # use the fused device step when the denoiser is a BoundDenoiser around the HIP network
 
     def __init__(self, num_steps: int, guider: Optional[VanillaCFG] = None, discretization=None, device="cuda"):
@@ -142,6 +146,11 @@ class EulerEDMSampler:
     def sigmas(self, num_steps=None) -> torch.Tensor:
         return self.discretization(self.num_steps if num_steps is None else num_steps, device=self.device)
 
+    def host_sigmas(self, num_steps=None) -> List[float]:
+        """the same fp32 schedule as Python floats (computed on the host: the branches the reference takes on device values are
+        decided from these, without a sync)"""
+        return self.discretization(self.num_steps if num_steps is None else num_steps, device="cpu").tolist()
+
     def denoise(self, x, denoiser, sigma, cond, uc):
         if self.guider is None:
             return denoiser(x, sigma, cond)
@@ -150,6 +159,9 @@ class EulerEDMSampler:
     def _fusable(self, denoiser, x, cond) -> bool:
         if not (self.fuse and isinstance(denoiser, BoundDenoiser) and x.is_cuda):
             return False
+        return self._fusable_network(denoiser, cond)
+
+    def _fusable_network(self, denoiser, cond) -> bool:
         model = getattr(denoiser.network, "diffusion_model", None)
         den = denoiser.denoiser
         # frame- / view-sharded networks fuse as well (round 4): the entry and exit kernels are elementwise over whatever frames /
@@ -160,10 +172,9 @@ class EulerEDMSampler:
                 and isinstance(den.scaling, EpsScaling) and den.quantize_c_noise
                 and "concat" in cond and cond.get("vector") is None)
 
-    def _fused_step(self, sigma, next_sigma, denoiser, x, cond, uc):
-        """One step with three tiny torch ops (table snap of T sigmas) + the network + one exit kernel; same arithmetic, in
-        the reference's rounding order, as denoise() + the Euler update below."""
-        from . import engine as E
+    def _fused_eps(self, sigma, denoiser, x, cond, uc) -> "_Eps":
+        """The network half of a fused step: three tiny torch ops (table snap of T sigmas) + the network with c_in and the CFG
+        batch doubling in its entry kernel.  Returns the channels-last fp32 eps tokens with what an exit kernel needs."""
         den, model = denoiser.denoiser, denoiser.network.diffusion_model
         T = x.shape[0]
         idx = den.sigma_to_idx(sigma)
@@ -192,7 +203,6 @@ class EulerEDMSampler:
         eps = model.denoise_tokens(x, c_in.repeat(nh).contiguous(), c_noise.repeat(nh).contiguous(), ctx, cat["concat"],
                                    cat["cond_feat"], invariants=inv)
         x32 = x.detach().to(torch.float32).contiguous()
-        out = torch.empty_like(x32)
         eps32, cfg = eps.f32, nh == 2
         if half is not None:
             import torch.distributed as dist
@@ -202,30 +212,517 @@ class EulerEDMSampler:
             both = torch.empty((2 * send.shape[0], send.shape[1]), dtype=send.dtype, device=send.device)   # [uncond half; cond half]
             dist.all_gather_into_tensor(both, send, group=self.guider.group)
             eps32, cfg = both.to(mine.device), True
-        E.backend().cfg_euler_step(eps32, eps.C, T, eps.N, x.shape[1], cfg, float(self.guider.scale) if cfg else 0.0,
-                                   x32, (-sig_q).contiguous(), sigma.contiguous(), next_sigma.contiguous(), out)
+        return _Eps(eps32, eps.C, T, eps.N, x.shape[1], cfg, float(self.guider.scale) if cfg else 0.0, x32, (-sig_q).contiguous())
+
+
+class _Eps:
+    """eps tokens of one network evaluation: tok [(cfg ? 2 : 1) * T * Npix][ld] fp32, x = the fp32 NCHW latent the network saw,
+    c_out = -sigma snapped to the table"""
+    __slots__ = ("tok", "ld", "T", "Npix", "C", "cfg", "scale", "x", "c_out")
+
+    def __init__(self, tok, ld, T, Npix, C, cfg, scale, x, c_out):
+        self.tok, self.ld, self.T, self.Npix, self.C, self.cfg, self.scale, self.x, self.c_out = tok, ld, T, Npix, C, cfg, scale, x, c_out
+
+    def step(self, mode, v, out_aux=None, **kw) -> torch.Tensor:
+        """pnc_cfg_sampler_step on these tokens; returns `out` (a new fp32 latent)"""
+        from . import engine as E
+        out = torch.empty_like(self.x)
+        E.backend().cfg_sampler_step(mode, self.tok, self.ld, self.T, self.Npix, self.C, self.cfg, self.scale, self.x, self.c_out,
+                                     [t.contiguous() for t in v], out, out_aux=out_aux, **kw)
+        return out
+
+
+def _churn_gamma(s_churn, s_tmin, s_tmax, sigma_i: float, num_sigmas: int) -> float:
+    """EDMSampler.__call__ (sampling.py:118-122) on the host: the device comparison is fp32 against the fp32-rounded bounds"""
+    lo, hi = float(np.float32(s_tmin)), float(np.float32(s_tmax))
+    return min(s_churn / (num_sigmas - 1), 2 ** 0.5 - 1) if lo <= sigma_i <= hi else 0.0
+
+
+class _EDM(_Sampler):
+    """EDMSampler (sampling.py:85-133): optional churn noise before the network.  The churn stays three torch ops in the
+    reference's order (x + eps * sqrt(sigma_hat^2 - sigma^2)) in front of the fused step; its noise comes from `noise_sampler`."""
+
+    def __init__(self, num_steps: int, guider: Optional[VanillaCFG] = None, discretization=None, device="cuda",
+                 s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0):
+        super().__init__(num_steps, guider, discretization, device)
+        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
+        self.noise_sampler = lambda x: torch.randn_like(x)
+
+    def _churn(self, sigma, x, gamma, noise=None):
+        sigma_hat = sigma * (gamma + 1.0)
+        if gamma > 0:
+            eps = (self.noise_sampler(x) if noise is None else noise) * self.s_noise
+            x = x + eps * append_dims(sigma_hat ** 2 - sigma ** 2, x.ndim) ** 0.5
+        return sigma_hat, x
+
+
+class EulerEDMSampler(_EDM):
+    """sampling.py:27-133,214-218.  s_churn = 0 (default) is deterministic (== DDIM for eps-prediction)."""
+
+    def _fused_step(self, sigma, next_sigma, denoiser, x, cond, uc):
+        """One step with three tiny torch ops (table snap of T sigmas) + the network + one exit kernel; same arithmetic, in
+        the reference's rounding order, as denoise() + the Euler update below."""
+        from . import engine as E
+        e = self._fused_eps(sigma, denoiser, x, cond, uc)
+        out = torch.empty_like(e.x)
+        E.backend().cfg_euler_step(e.tok, e.ld, e.T, e.Npix, e.C, e.cfg, e.scale, e.x, e.c_out, sigma.contiguous(),
+                                   next_sigma.contiguous(), out)
         return out.to(x.dtype)
 
-    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None):
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0):
+        if gamma > 0:
+            sigma, x = self._churn(sigma, x, gamma)                   # sigma_hat from here on
         if self._fusable(denoiser, x, cond):
             return self._fused_step(sigma, next_sigma, denoiser, x, cond, uc)
         denoised = self.denoise(x, denoiser, sigma, cond, uc)
         d = (x - denoised) / append_dims(sigma, x.ndim)
         return x + append_dims(next_sigma - sigma, x.ndim) * d
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None):
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None, callback=None):
         """`network`: optional OpenAIWrapperControlLDM3D.  When given, the step invariants of the conditioning (text
         K/V of every cross-attention site, ControlNet hint stem) are computed once for the whole schedule instead of
-        once per step; the trajectory is bit-identical to the plain loop."""
+        once per step; the trajectory is bit-identical to the plain loop.  `callback(i, x)` sees the
+        latent after every step."""
         sig = self.sigmas(num_steps)
         uc = cond if uc is None else uc
         if network is not None:
             cond, uc = hoist_invariants(network, self.guider, cond, uc)
         x = x * torch.sqrt(1.0 + sig[0] ** 2.0)
         s_in = x.new_ones([x.shape[0]])
+        sig_f = self.host_sigmas(num_steps) if self.s_churn > 0 else None
         for i in range(len(sig) - 1):
-            x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc)
+            gamma = _churn_gamma(self.s_churn, self.s_tmin, self.s_tmax, sig_f[i], len(sig)) if sig_f else 0.0
+            if gamma > 0:
+                x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc, gamma)
+            else:
+                x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc)
+            if callback is not None:
+                callback(i, x)
         return x
+
+    # the step forms of a schedule (graph.GraphedSchedule): one per churn gamma
+    def _steps(self, sig, sig_f, s_in):
+        for i in range(len(sig_f) - 1):
+            gamma = _churn_gamma(self.s_churn, self.s_tmin, self.s_tmax, sig_f[i], len(sig_f))
+            yield gamma, {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, gamma > 0
+
+    def _state(self, x):
+        return {}
+
+    def _device_step(self, form, sv, x, denoiser, cond, uc, state):
+        sigma, x = self._churn(sv["sigma"], x, form, sv.get("noise"))
+        return self._fused_step(sigma, sv["next_sigma"], denoiser, x, cond, uc)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the other samplers of sampling.py.  Each has the reference's `sampler_step` (torch ops in the reference's order, used whenever the
+# step does not fuse) and a device step: the network's eps tokens + ONE pnc_cfg_sampler_step per network evaluation, with every
+# per-frame scalar (sigma_hat, sigma_down / sigma_up, the exp / expm1 multipliers, the LMS coefficients) a [T] device vector made by
+# the same torch ops as the plain step, so a fused step gives the plain step's bits.  Branches the reference takes on device sums
+# (`torch.sum(next_sigma) < 1e-14`, the first step) are decided from the host copy of the schedule.
+# ------------------------------------------------------------------------------------------------------------------------------
+def to_d(x, sigma, denoised):
+    return (x - denoised) / append_dims(sigma, x.ndim)
+
+
+def to_neg_log_sigma(sigma):
+    return sigma.log().neg()
+
+
+def to_sigma(neg_log_sigma):
+    return neg_log_sigma.neg().exp()
+
+
+def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
+    """sampling_utils.py: (sigma_down, sigma_up); sigma_up is the float 0.0 when eta is 0"""
+    if not eta:
+        return sigma_to, 0.0
+    sigma_up = torch.minimum(sigma_to, eta * (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5)
+    sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+    return sigma_down, sigma_up
+
+
+def _vec(v, like):
+    """a per-frame scalar as a [T] fp32 vector (sigma_up is a Python 0.0 when eta = 0)"""
+    return v if torch.is_tensor(v) else torch.full_like(like, float(v))
+
+
+def _all_zero(v: List[float]) -> bool:
+    """`torch.sum(v) < 1e-14` of a [T] vector whose frames hold the same value"""
+    return len(v) * v[0] < 1e-14 if v else True
+
+
+class _Scheduled(_Sampler):
+    """The schedule loop of the samplers below: the reference's own loop on plain steps, or the device loop over
+    `_steps()` / `_device_step()` (the forms graph.GraphedSchedule captures)."""
+
+    def _check_guider(self):
+        if hasattr(self.guider, "half"):
+            raise NotImplementedError(f"{type(self).__name__} does not run under parallel.ShardedCFG (one CFG half per rank); "
+                                      "use VanillaCFG, or EulerEDMSampler for CFG-half sharding")
+
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None, callback=None):
+        """`network`: hoist the step invariants once per schedule (they serve every evaluation of a step); `callback(i, x)`
+        sees the latent after every step."""
+        self._check_guider()
+        sig, sig_f = self.sigmas(num_steps), self.host_sigmas(num_steps)
+        uc = cond if uc is None else uc
+        if network is not None:
+            cond, uc = hoist_invariants(network, self.guider, cond, uc)
+        x = x * torch.sqrt(1.0 + sig[0] ** 2.0)
+        s_in = x.new_ones([x.shape[0]])
+        loop = self._fused_loop if self._fusable(denoiser, x, cond) else self._plain_loop
+        return loop(sig, sig_f, s_in, denoiser, x, cond, uc, callback)
+
+    def _fused_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+        state = self._state(x)
+        for i, (form, sv, draw) in enumerate(self._steps(sig, sig_f, s_in)):
+            if draw:
+                sv["noise"] = self.noise_sampler(x).to(torch.float32).contiguous()
+            x = self._device_step(form, sv, x, denoiser, cond, uc, state).to(x.dtype)
+            if callback is not None:
+                callback(i, x)
+        return x
+
+    def _state(self, x):
+        return {}
+
+
+class HeunEDMSampler(_EDM, _Scheduled):
+    """sampling.py:85-133,221-237: Euler to next_sigma, then (unless every next_sigma is 0) a second evaluation there and the
+    trapezoidal correction."""
+
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0, last=None):
+        sigma_hat, x = self._churn(sigma, x, gamma)
+        denoised = self.denoise(x, denoiser, sigma_hat, cond, uc)
+        d = to_d(x, sigma_hat, denoised)
+        dt = append_dims(next_sigma - sigma_hat, x.ndim)
+        euler_step = x + dt * d
+        if last is None:
+            last = bool(torch.sum(next_sigma) < 1e-14)
+        if last:
+            return euler_step
+        denoised = self.denoise(euler_step, denoiser, next_sigma, cond, uc)
+        d_new = to_d(euler_step, next_sigma, denoised)
+        d_prime = (d + d_new) / 2.0
+        return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x + d_prime * dt, euler_step)
+
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+        for i, ((gamma, last), _, _) in enumerate(self._steps(sig, sig_f, s_in)):
+            x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc, gamma, last=last)
+            if callback is not None:
+                callback(i, x)
+        return x
+
+    def _steps(self, sig, sig_f, s_in):
+        T = s_in.shape[0]
+        for i in range(len(sig_f) - 1):
+            gamma = _churn_gamma(self.s_churn, self.s_tmin, self.s_tmax, sig_f[i], len(sig_f))
+            yield (gamma, _all_zero([sig_f[i + 1]] * T)), {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, gamma > 0
+
+    def _device_step(self, form, sv, x, denoiser, cond, uc, state):
+        from . import hip
+        gamma, last = form
+        nxt = sv["next_sigma"]
+        sigma_hat, x = self._churn(sv["sigma"], x, gamma, sv.get("noise"))
+        e = self._fused_eps(sigma_hat, denoiser, x, cond, uc)
+        d = torch.empty_like(e.x)
+        x_euler = e.step(hip.SAMPLER_HEUN1, [sigma_hat, nxt], out_aux=d)
+        if last:
+            return x_euler
+        e2 = self._fused_eps(nxt, denoiser, x_euler, cond, uc)
+        return e2.step(hip.SAMPLER_HEUN2, [sigma_hat, nxt], x0=e.x, aux=d)
+
+
+class _Ancestral(_Scheduled):
+    """AncestralSampler (sampling.py:135-172)"""
+
+    def __init__(self, num_steps: int, guider: Optional[VanillaCFG] = None, discretization=None, device="cuda",
+                 eta=1.0, s_noise=1.0):
+        super().__init__(num_steps, guider, discretization, device)
+        self.eta, self.s_noise = eta, s_noise
+        self.noise_sampler = lambda x: torch.randn_like(x)
+
+    def ancestral_euler_step(self, x, denoised, sigma, sigma_down):
+        d = to_d(x, sigma, denoised)
+        dt = append_dims(sigma_down - sigma, x.ndim)
+        return x + dt * d
+
+    def ancestral_step(self, x, sigma, next_sigma, sigma_up):
+        return torch.where(append_dims(next_sigma, x.ndim) > 0.0,
+                           x + self.noise_sampler(x) * self.s_noise * append_dims(sigma_up, x.ndim), x)
+
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+        for i in range(len(sig_f) - 1):
+            x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc)
+            if callback is not None:
+                callback(i, x)
+        return x
+
+    def _noise_v(self, sigma, nxt):
+        sd, su = get_ancestral_step(sigma, nxt, eta=self.eta)
+        return sd, _vec(su, sigma)
+
+
+class EulerAncestralSampler(_Ancestral):
+    """sampling.py:240-247"""
+
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None):
+        sigma_down, sigma_up = get_ancestral_step(sigma, next_sigma, eta=self.eta)
+        denoised = self.denoise(x, denoiser, sigma, cond, uc)
+        x = self.ancestral_euler_step(x, denoised, sigma, sigma_down)
+        return self.ancestral_step(x, sigma, next_sigma, sigma_up)
+
+    def _steps(self, sig, sig_f, s_in):
+        for i in range(len(sig_f) - 1):
+            yield None, {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, True
+
+    def _device_step(self, form, sv, x, denoiser, cond, uc, state):
+        from . import hip
+        sigma, nxt = sv["sigma"], sv["next_sigma"]
+        sd, su = self._noise_v(sigma, nxt)
+        e = self._fused_eps(sigma, denoiser, x, cond, uc)
+        return e.step(hip.SAMPLER_EULER_A, [sigma, sd, su, nxt], noise=sv["noise"], s_noise=self.s_noise)
+
+
+class DPMPP2SAncestralSampler(_Ancestral):
+    """sampling.py:250-287: DPM-Solver++(2S) with ancestral noise; the midpoint evaluation is skipped where sigma_down is 0."""
+
+    def get_variables(self, sigma, sigma_down):
+        t, t_next = [to_neg_log_sigma(s) for s in (sigma, sigma_down)]
+        h = t_next - t
+        s = t + 0.5 * h
+        return h, s, t, t_next
+
+    def get_mult(self, h, s, t, t_next):
+        return to_sigma(s) / to_sigma(t), (-0.5 * h).expm1(), to_sigma(t_next) / to_sigma(t), (-h).expm1()
+
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, last=None):
+        sigma_down, sigma_up = get_ancestral_step(sigma, next_sigma, eta=self.eta)
+        denoised = self.denoise(x, denoiser, sigma, cond, uc)
+        x_euler = self.ancestral_euler_step(x, denoised, sigma, sigma_down)
+        if last is None:
+            last = bool(torch.sum(sigma_down) < 1e-14)
+        if last:
+            x = x_euler
+        else:
+            h, s, t, t_next = self.get_variables(sigma, sigma_down)
+            mult = [append_dims(m, x.ndim) for m in self.get_mult(h, s, t, t_next)]
+            x2 = mult[0] * x - mult[1] * denoised
+            denoised2 = self.denoise(x2, denoiser, to_sigma(s), cond, uc)
+            x_dpmpp2s = mult[2] * x - mult[3] * denoised2
+            x = torch.where(append_dims(sigma_down, x.ndim) > 0.0, x_dpmpp2s, x_euler)
+        return self.ancestral_step(x, sigma, next_sigma, sigma_up)
+
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+        for i, (last, _, _) in enumerate(self._steps(sig, sig_f, s_in)):
+            x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc, last=last)
+            if callback is not None:
+                callback(i, x)
+        return x
+
+    def _steps(self, sig, sig_f, s_in):
+        T = s_in.shape[0]
+        for i in range(len(sig_f) - 1):
+            # sigma_down of the fp32 schedule, on the host (the reference sums it on the device)
+            sd, _ = get_ancestral_step(torch.tensor([sig_f[i]]), torch.tensor([sig_f[i + 1]]), eta=self.eta)
+            yield _all_zero([float(sd[0])] * T), {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, True
+
+    def _device_step(self, form, sv, x, denoiser, cond, uc, state):
+        from . import hip
+        sigma, nxt = sv["sigma"], sv["next_sigma"]
+        sd, su = self._noise_v(sigma, nxt)
+        e = self._fused_eps(sigma, denoiser, x, cond, uc)
+        if form:                                                      # every sigma_down is 0: the ancestral Euler step
+            return e.step(hip.SAMPLER_EULER_A, [sigma, sd, su, nxt], noise=sv["noise"], s_noise=self.s_noise)
+        h, s, t, t_next = self.get_variables(sigma, sd)
+        m1, m2, m3, m4 = self.get_mult(h, s, t, t_next)
+        x_euler = torch.empty_like(e.x)
+        x2 = e.step(hip.SAMPLER_DPM2S_1, [sigma, sd, m1, m2], out_aux=x_euler)
+        e2 = self._fused_eps(to_sigma(s), denoiser, x2, cond, uc)
+        return e2.step(hip.SAMPLER_DPM2S_2, [m3, m4, sd, su, nxt], x0=e.x, aux=x_euler, noise=sv["noise"], s_noise=self.s_noise)
+
+
+class DPMPP2MSampler(_Scheduled):
+    """sampling.py:290-365: DPM-Solver++(2M); carries the previous step's denoised (a device plane)."""
+
+    def get_variables(self, sigma, next_sigma, previous_sigma=None):
+        t, t_next = [to_neg_log_sigma(s) for s in (sigma, next_sigma)]
+        h = t_next - t
+        if previous_sigma is not None:
+            h_last = t - to_neg_log_sigma(previous_sigma)
+            return h, h_last / h, t, t_next
+        return h, None, t, t_next
+
+    def get_mult(self, h, r, t, t_next, previous_sigma):
+        mult1 = to_sigma(t_next) / to_sigma(t)
+        mult2 = (-h).expm1()
+        if previous_sigma is not None:
+            return mult1, mult2, 1 + 1 / (2 * r), 1 / (2 * r)
+        return mult1, mult2
+
+    def sampler_step(self, old_denoised, previous_sigma, sigma, next_sigma, denoiser, x, cond, uc=None, last=None):
+        denoised = self.denoise(x, denoiser, sigma, cond, uc)
+        h, r, t, t_next = self.get_variables(sigma, next_sigma, previous_sigma)
+        mult = [append_dims(m, x.ndim) for m in self.get_mult(h, r, t, t_next, previous_sigma)]
+        x_standard = mult[0] * x - mult[1] * denoised
+        if last is None:
+            last = bool(torch.sum(next_sigma) < 1e-14)
+        if old_denoised is None or last:
+            return x_standard, denoised
+        denoised_d = mult[2] * denoised - mult[3] * old_denoised
+        x_advanced = mult[0] * x - mult[1] * denoised_d
+        return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x_advanced, x_standard), denoised
+
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+        old = None
+        T = s_in.shape[0]
+        for i in range(len(sig_f) - 1):
+            x, old = self.sampler_step(old, None if i == 0 else s_in * sig[i - 1], s_in * sig[i], s_in * sig[i + 1], denoiser, x,
+                                       cond, uc, last=_all_zero([sig_f[i + 1]] * T))
+            if callback is not None:
+                callback(i, x)
+        return x
+
+    def _steps(self, sig, sig_f, s_in):
+        T = s_in.shape[0]
+        for i in range(len(sig_f) - 1):
+            sv = {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}
+            if i > 0:
+                sv["previous_sigma"] = s_in * sig[i - 1]
+            # forms: "first" (no previous denoised), "last" (every next_sigma 0), "middle"
+            yield ("first" if i == 0 else "last" if _all_zero([sig_f[i + 1]] * T) else "middle"), sv, False
+
+    def _state(self, x):
+        return {"old": torch.empty(x.shape, dtype=torch.float32, device=x.device)}
+
+    def _device_step(self, form, sv, x, denoiser, cond, uc, state):
+        from . import hip
+        sigma, nxt, prev = sv["sigma"], sv["next_sigma"], sv.get("previous_sigma")
+        e = self._fused_eps(sigma, denoiser, x, cond, uc)
+        h, r, t, t_next = self.get_variables(sigma, nxt, prev)
+        mult = self.get_mult(h, r, t, t_next, prev)
+        old = state["old"]
+        if form == "middle":
+            # the kernel reads the previous denoised of an element before it writes this step's there
+            return e.step(hip.SAMPLER_DPM2M, [*mult, nxt], out_aux=old, aux=old)
+        return e.step(hip.SAMPLER_DPM2M, list(mult[:2]), out_aux=old)
+
+
+def linear_multistep_coeff(order: int, t, i: int, j: int, epsrel=1e-4) -> float:
+    """sampling_utils.py:12-24 in float64: the integral over [t_i, t_(i+1)] of the j-th Lagrange basis polynomial through
+    t_i, t_(i-1), ...  scipy's `quad` when scipy is present, else Gauss-Legendre with 4 nodes (exact: degree <= 3)."""
+    if order - 1 > i:
+        raise ValueError(f"Order {order} too high for step {i}")
+    t = [float(v) for v in t]
+
+    def fn(tau):
+        prod = 1.0
+        for k in range(order):
+            if j != k:
+                prod *= (tau - t[i - k]) / (t[i - j] - t[i - k])
+        return prod
+    try:
+        from scipy import integrate
+    except ImportError:
+        a, b = t[i], t[i + 1]
+        nodes, weights = np.polynomial.legendre.leggauss(4)
+        return float(sum(w * fn(0.5 * (b - a) * u + 0.5 * (a + b)) for u, w in zip(nodes, weights)) * 0.5 * (b - a))
+    return integrate.quad(fn, t[i], t[i + 1], epsrel=epsrel)[0]
+
+
+class LinearMultistepSampler(_Scheduled):
+    """sampling.py:176-211: linear multistep of `order` on the last `order` d = (x - denoised) / sigma.  The coefficients are
+    computed once per schedule (float64) and enter the update as fp32 scalars, the way torch rounds a Python float."""
+    MAX_FUSED_ORDER = 4          # pnc_cfg_sampler_step keeps up to 3 previous d
+
+    def __init__(self, num_steps: int, guider: Optional[VanillaCFG] = None, discretization=None, device="cuda", order=4):
+        super().__init__(num_steps, guider, discretization, device)
+        self.order = order
+
+    def coefficients(self, sig_f: List[float]) -> List[List[float]]:
+        out = []
+        for i in range(len(sig_f) - 1):
+            cur = min(i + 1, self.order)
+            out.append([linear_multistep_coeff(cur, sig_f, i, j) for j in range(cur)])
+        return out
+
+    def sampler_step(self, sigma, denoiser, x, cond, uc, ds: list, coeffs: List[float]):
+        """one step of the reference's loop: appends this step's d to `ds` (kept at `order` entries)"""
+        denoised = self.denoise(x, denoiser, sigma, cond, uc)
+        d = to_d(x, sigma, denoised)
+        ds.append(d)
+        if len(ds) > self.order:
+            ds.pop(0)
+        return x + sum(coeff * d for coeff, d in zip(coeffs, reversed(ds)))
+
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+        ds = []
+        for i, cs in enumerate(self.coefficients(sig_f)):
+            x = self.sampler_step(s_in * sig[i], denoiser, x, cond, uc, ds, cs)
+            if callback is not None:
+                callback(i, x)
+        return x
+
+    def _steps(self, sig, sig_f, s_in):
+        if self.order > self.MAX_FUSED_ORDER:
+            raise NotImplementedError(f"the fused LMS step keeps at most {self.MAX_FUSED_ORDER - 1} previous d (order {self.order})")
+        co = self.coefficients(sig_f)
+        table = torch.tensor([c + [0.0] * (self.order - len(c)) for c in co], dtype=torch.float32)      # fp32 rounding of each
+        table = table[:, :, None].expand(-1, -1, s_in.shape[0]).contiguous().to(s_in.device)
+        for i, cs in enumerate(co):
+            yield len(cs) - 1, {"sigma": s_in * sig[i], "coeffs": table[i, :len(cs)]}, False
+
+    def _state(self, x):
+        return {"hist": [torch.empty(x.shape, dtype=torch.float32, device=x.device) for _ in range(self.order - 1)]}
+
+    def _device_step(self, form, sv, x, denoiser, cond, uc, state):
+        from . import hip
+        e = self._fused_eps(sv["sigma"], denoiser, x, cond, uc)
+        hist = state["hist"]
+        d = torch.empty_like(e.x)
+        out = e.step(hip.SAMPLER_LMS, [sv["sigma"], *sv["coeffs"].unbind(0)], out_aux=d, hist=hist[:form])
+        for k in range(len(hist) - 1, 0, -1):                         # newest first: shift the history, d enters in front
+            hist[k].copy_(hist[k - 1])
+        if hist:
+            hist[0].copy_(d)
+        return out
+
+
+SAMPLERS = {"EulerEDMSampler": EulerEDMSampler, "HeunEDMSampler": HeunEDMSampler, "EulerAncestralSampler": EulerAncestralSampler,
+            "DPMPP2SAncestralSampler": DPMPP2SAncestralSampler, "DPMPP2MSampler": DPMPP2MSampler,
+            "LinearMultistepSampler": LinearMultistepSampler}
+_REF_SAMPLING = "sgm.modules.diffusionmodules.sampling."
+
+
+def from_config(sampler_config: Dict, device="cuda") -> _Sampler:
+    """The mirror of the reference's YAML `sampler_config` (configs/inference_nuscenes.yaml:115-126): `target` one of the six
+    samplers of sgm.modules.diffusionmodules.sampling, `params` with num_steps, discretization_config (LegacyDDPMDiscretization),
+    guider_config (VanillaCFG or IdentityGuider) and the sampler's own kwargs (s_churn, eta, s_noise, order, ...)."""
+    target = sampler_config.get("target", "")
+    name = target[len(_REF_SAMPLING):] if target.startswith(_REF_SAMPLING) else None
+    if name not in SAMPLERS:
+        raise NotImplementedError(f"sampler target {target!r} has no mirror in panacea_amd.sampling "
+                                  f"(supported: {', '.join(_REF_SAMPLING + n for n in SAMPLERS)})")
+    params = dict(sampler_config.get("params") or {})
+    params.pop("verbose", None)
+    disc_cfg = params.pop("discretization_config", None) or {"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"}
+    if not str(disc_cfg.get("target", "")).endswith("LegacyDDPMDiscretization"):
+        raise NotImplementedError(f"discretization {disc_cfg.get('target')!r} has no mirror (LegacyDDPMDiscretization only)")
+    disc = LegacyDDPMDiscretization(**dict(disc_cfg.get("params") or {}))
+    g_cfg = params.pop("guider_config", None)
+    g_target = str((g_cfg or {}).get("target", "IdentityGuider"))
+    if g_target.endswith("VanillaCFG"):
+        g_params = dict(g_cfg.get("params") or {})
+        if g_params.get("dyn_thresh_config") is not None:
+            raise NotImplementedError("dynamic thresholding is not mirrored")
+        guider = VanillaCFG(g_params["scale"])
+    elif g_target.endswith("IdentityGuider"):
+        guider = None
+    else:
+        raise NotImplementedError(f"guider {g_target!r} has no mirror (VanillaCFG / IdentityGuider)")
+    num_steps = params.pop("num_steps", None)
+    return SAMPLERS[name](num_steps, guider=guider, discretization=disc, device=device, **params)
 
 
 def share_noise_init(randn: torch.Tensor, concat: torch.Tensor, share_noise_level: float) -> torch.Tensor:

@@ -1,21 +1,24 @@
 #!/usr/bin/env python
 """End-to-end demo of everything this package owns, with SYNTHETIC weights (no checkpoint, no dataset offline):
-conditioning tensors -> N Euler/CFG steps of the ControlNet-UNet (step invariants hoisted) -> first-stage decode ->
+conditioning tensors -> N sampler/CFG steps (Euler by default, `--sampler` picks another) of the ControlNet-UNet (step invariants hoisted) -> first-stage decode ->
 per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference's weights are loaded instead
 (`model.diffusion_model.*` into the denoiser, `first_stage_model.*` into the decoder).
 
     python tools/sample.py --steps 5 --out gpurun_out/sample
+    python tools/sample.py --sampler dpmpp2m --steps 15
 """
 import argparse, json, sys, time
 from pathlib import Path
 import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from panacea_amd import build_network, checkpoint, configs, pipeline, synth   # noqa: E402
+from panacea_amd import build_network, checkpoint, configs, pipeline, sampling, synth   # noqa: E402
 from panacea_amd.nn import model                                               # noqa: E402
 
 VAE = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4, 4],
            num_res_blocks=2, attn_resolutions=[], dropout=0.0)
+SAMPLERS = {"euler": "EulerEDMSampler", "heun": "HeunEDMSampler", "euler_a": "EulerAncestralSampler",
+            "dpmpp2s_a": "DPMPP2SAncestralSampler", "dpmpp2m": "DPMPP2MSampler", "lms": "LinearMultistepSampler"}
 
 
 def main():
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--out", default="gpurun_out/sample")
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--seed", type=int, default=3407)
+    ap.add_argument("--sampler", choices=sorted(SAMPLERS), default="euler")
+    ap.add_argument("--cfg-scale", type=float, default=5.0)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     kw = configs.get("full")
@@ -44,9 +49,13 @@ def main():
     uc = {"crossattn": g["crossattn"][0:1], "concat": g["concat"][:T], "cond_feat": g["cond_feat"][:T]}
     noise = torch.randn(T, 4, h, w, generator=torch.Generator().manual_seed(a.seed)).to(dev)
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps)
+    smp = sampling.from_config({"target": "sgm.modules.diffusionmodules.sampling." + SAMPLERS[a.sampler],
+                                "params": {"num_steps": a.steps, "guider_config": {
+                                    "target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": a.cfg_scale}}}},
+                               device=dev)
+    frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print(f"{a.steps} steps + decode of {T} frames {tuple(frames.shape)}: {dt:.2f} s "
+    print(f"{a.sampler}: {a.steps} steps + decode of {T} frames {tuple(frames.shape)}: {dt:.2f} s "
           f"(range {frames.min().item():.2f} .. {frames.max().item():.2f}, finite={bool(torch.isfinite(frames).all())})")
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
     checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=frames.shape[-1] // 6)
