@@ -290,6 +290,32 @@ int pnc_attn_temporal_f16(const void* q, int ldq, const void* k, int ldk,
                           const void* v, int ldv, void* o, int ldo,
                           int B, int T, int Npix, int heads, float scale, void* stream);
 
+/* Attention on SPLIT operands (the `precise-wide` operand policy: every operand carried as v ~ hi + lo * 2^-11, both planes fp16,
+ * valid up to |v| < 65504).  Products on the MFMA, fp32 accumulation and softmax:
+ *   S = Qh.Kh + 2^-11 (Qh.Kl + Ql.Kh)          (lo.lo dropped)
+ *   P = softmax(scale * S),  P = Ph + 2^-11 Pl  (fp16 pair)
+ *   O = Ph.Vh + 2^-11 (Ph.Vl + Pl.Vh),  written as hi + fp16 lo planes.
+ * Every lo plane has the leading dimension of its hi plane; pointers 8-byte aligned, leading dimensions % 4 == 0.
+ *
+ * pnc_attn_views_split_f16: the geometries of pnc_attn_views_f16 (intra-view, cross-view with one or two kv segments, text keys
+ * masked per key with kv_valid) EXCEPT that V is read ROW-major, laid out like K: `a.vt` points at V[key row][channel] with
+ * leading dimension `a.ldvt` (the QKV GEMM's out16 + out16_lo form; no lo plane exists for the transposed out16t store) and
+ * `a.vt_gstride` is ignored.  causal = 1 and the halo views (k_halo / vt_halo) are not supported (PNC_EINVAL).
+ * Returns PNC_EABI when struct_bytes != sizeof(PncAttnSplitParams). */
+typedef struct PncAttnSplitParams {
+    int32_t struct_bytes;   /* sizeof(PncAttnSplitParams) as the caller compiled it */
+    PncAttnParams a;
+    const void* q_lo;
+    const void* k_lo;
+    const void* v_lo;
+    void* o_lo;
+} PncAttnSplitParams;
+int pnc_attn_views_split_f16(const PncAttnSplitParams* p, void* stream);
+/* temporal self-attention of pnc_attn_temporal_f16 on split operands (T <= 16) */
+int pnc_attn_temporal_split_f16(const void* q, const void* q_lo, int ldq, const void* k, const void* k_lo, int ldk,
+                                const void* v, const void* v_lo, int ldv, void* o, void* o_lo, int ldo,
+                                int B, int T, int Npix, int heads, float scale, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * 3. Normalisations (fp32 stream in, fp16 operand out).  y16_lo (may be NULL) receives the lo plane of a precise
  *    operand, same layout as y16 (see PncGemmParams.A_lo), in the format lo_fmt (PNC_LO_*; pnc_layernorm: fp16 only).

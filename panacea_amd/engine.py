@@ -75,6 +75,24 @@ class Precision:
     gnt: bool = False
     conv_mid: bool = False
     lo8: bool = False
+    # the classes below are split by `precise-wide` only (every operand of the path, fp16 lo planes): the LayerNorm outputs, the
+    # q / k / v of the intra-view, cross-view and temporal attention, the text queries and keys / values, the fp16 context, the
+    # GEGLU hidden state and the attention output.  The five attention classes (qkv, q_text, kv_text, ctx, attn_o) go together: the
+    # split attention kernels (pnc_attn_views_split_f16 / pnc_attn_temporal_split_f16) read and write all of them.
+    ln: bool = False
+    qkv: bool = False
+    q_text: bool = False
+    kv_text: bool = False
+    ctx: bool = False
+    ff_hidden: bool = False
+    attn_o: bool = False
+
+    def __post_init__(self):
+        att = (self.qkv, self.q_text, self.kv_text, self.attn_o, self.ctx)
+        if any(att) and not all(att):
+            raise ValueError("the attention operand classes qkv, q_text, kv_text, ctx and attn_o are split together or not at all")
+        if any(att) and self.lo8:
+            raise ValueError("the split attention kernels read fp16 lo planes: a policy that splits q / k / v cannot set lo8")
 
     @property
     def name(self) -> str:
@@ -101,8 +119,13 @@ PRECISE_ALL = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_hea
 PRECISE_LITE = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_head=True, lo8=True)
 # round 2's form of `precise`: every lo plane fp16, lo pass on the fp16 MFMA (A/B of the e4m3 lo pass)
 PRECISE_F16LO = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_head=True, gnt=True)
+# every operand class split, every lo plane fp16: an fp16 lo plane (v - fp16(v)) * 2^11 has the hi plane's range, so the policy holds
+# up to |operand| < 65504 (the e4m3 lo planes of `precise` saturate from |v| = 512 on).  Eps 8.5e-6 in the CPU error budget of the
+# heavy-tail weight set, where `precise` leaves 2.0e-3.  The target of on_range_exceeded = "escalate".
+PRECISE_WIDE = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_head=True, gn_res=True, gnt=True, conv_mid=True,
+                         ln=True, qkv=True, q_text=True, kv_text=True, ctx=True, ff_hidden=True, attn_o=True)
 PRECISIONS = {"fast": FAST, "precise": PRECISE, "precise-all": PRECISE_ALL, "precise-lite": PRECISE_LITE,
-              "precise-f16lo": PRECISE_F16LO}
+              "precise-f16lo": PRECISE_F16LO, "precise-wide": PRECISE_WIDE}
 
 
 def precision(p) -> Precision:
@@ -644,6 +667,7 @@ class Runtime:
         self.emb_all: Optional[torch.Tensor] = None    # frame-sharded runs: SiLU(emb) rows of ALL B*T frames
         self.prec: Precision = FAST                    # operand precision policy of this evaluation
         self.ctx16: Optional[torch.Tensor] = None      # [B*TEXT_PAD, context_dim] fp16, zero padded
+        self.ctx16_lo: Optional[torch.Tensor] = None   # its lo plane when the policy splits `ctx`
         self.n_text = 77
         self.trace: Optional[Dict[str, torch.Tensor]] = None
         self.text_kv: Dict[int, tuple] = {}            # per cross-attention site: (k, ldk, vt, ldvt, vt_gstride)
@@ -682,6 +706,13 @@ class Runtime:
         if D % 8:
             raise ValueError("context_dim must be a multiple of 8")
         self.n_text = n
+        if self.prec.ctx:
+            c32 = torch.zeros((B, TEXT_PAD, D), device=self.device, dtype=torch.float32)
+            c32[:, :n] = context.to(device=self.device, dtype=torch.float32)
+            self.ctx16 = self.empty((B * TEXT_PAD, D), torch.float16)
+            self.ctx16_lo = self.lo_plane((B * TEXT_PAD, D), "ctx")
+            self.be.cast_f16(c32, c32.numel(), self.ctx16, self.ctx16_lo)
+            return
         c = torch.zeros((B, TEXT_PAD, D), device=self.device, dtype=torch.float16)
         c[:, :n] = context.to(device=self.device, dtype=torch.float16)
         self.ctx16 = c.view(B * TEXT_PAD, D)
@@ -905,6 +936,14 @@ def layer_norm(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta) -> t
     y = rt.empty((M, C), torch.float16)
     rt.be.layernorm(x32, C, M, C, gamma, beta, 1e-5, y, C)
     return y
+
+
+def layer_norm_split(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta):
+    """-> (y16, y16_lo): LayerNorm with the lo plane of operand class `ln` (None unless the policy splits it)"""
+    y = rt.empty((M, C), torch.float16)
+    ylo = rt.lo_plane((M, C), "ln")
+    rt.be.layernorm(x32, C, M, C, gamma, beta, 1e-5, y, C, ylo)
+    return y, ylo
 
 
 def small_linear(rt: Runtime, a32: torch.Tensor, w16: torch.Tensor, bias, M: int, N: int, K: int,

@@ -16,9 +16,22 @@ from typing import Callable
 import torch
 
 
+def refuse_unescalated(network):
+    """A captured step replays kernels only: the range monitor of on_range_exceeded = "escalate" never runs inside it.  A network
+    in that mode may be captured once it has escalated (its policy no longer changes), not before."""
+    if network is None:
+        return
+    model = getattr(network, "diffusion_model", network)
+    if getattr(model, "on_range_exceeded", None) == "escalate" and not model.escalated:
+        raise ValueError("on_range_exceeded='escalate' is not monitored during graph replay: capture the network after it has "
+                         "escalated, or use 'warn' / 'raise'")
+
+
 class GraphedStep:
     def __init__(self, step_fn: Callable[[torch.Tensor, torch.Tensor, torch.Tensor], torch.Tensor],
-                 x: torch.Tensor, sigma: torch.Tensor, next_sigma: torch.Tensor, warmup: int = 2):
+                 x: torch.Tensor, sigma: torch.Tensor, next_sigma: torch.Tensor, warmup: int = 2, network=None):
+        """`network`: the network `step_fn` evaluates (refused while in an un-escalated "escalate" mode)"""
+        refuse_unescalated(network)
         self.x, self.sigma, self.next_sigma = x.clone(), sigma.clone(), next_sigma.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -56,6 +69,7 @@ class GraphedSchedule:
 
     def __init__(self, sampler, denoiser, x_like: torch.Tensor, cond, uc=None, num_steps=None, network=None, warmup: int = 1):
         from . import sampling
+        refuse_unescalated(network if network is not None else getattr(denoiser, "network", None))
         if hasattr(sampler, "_check_guider"):
             sampler._check_guider()
         if not sampler._fusable(denoiser, x_like, cond):

@@ -87,6 +87,13 @@ class AttnParams(C.Structure):
     ]
 
 
+class AttnSplitParams(C.Structure):
+    _fields_ = [
+        ("struct_bytes", C.c_int32), ("a", AttnParams),
+        ("q_lo", C.c_void_p), ("k_lo", C.c_void_p), ("v_lo", C.c_void_p), ("o_lo", C.c_void_p),
+    ]
+
+
 class SamplerStepParams(C.Structure):
     _fields_ = [
         ("struct_bytes", C.c_int32), ("mode", C.c_int32),
@@ -112,6 +119,8 @@ _SIGNATURES = {
     "pnc_gemm_workspace_floats": (_L, [C.POINTER(GemmParams)]),
     "pnc_gemm_fuses_layernorm": (_I, [C.POINTER(GemmParams)]),
     "pnc_attn_views_f16": (_I, [C.POINTER(AttnParams), _P]),
+    "pnc_attn_views_split_f16": (_I, [C.POINTER(AttnSplitParams), _P]),
+    "pnc_attn_temporal_split_f16": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "pnc_softmax_rows_f16": (_I, [_P, _L, _I, _I, _F, _I, _I, _P, _L, _P]),
     "pnc_attn_temporal_f16": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "pnc_groupnorm_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
@@ -371,14 +380,8 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
         layernorm(out32, ldc32, M, N, ln_gamma, ln_beta, ln_eps, ln_out16, ldln)
 
 
-def attn_views(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H, W, views,
-               kvH, kvW, kv_views, kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal=False, k_halo=None, vt_halo=None):
-    """`k_halo` / `vt_halo`: pairs (left, right) of buffers with the geometry of k / vt whose view column 0 holds a neighbour rank's
-    view — kv view id -1 / kv_views in `segs` (PncAttnParams.k_halo)"""
-    p = AttnParams()
-    if k_halo is not None:
-        for i in range(2):
-            p.k_halo[i], p.vt_halo[i] = _ptr(k_halo[i]), _ptr(vt_halo[i])
+def _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
+                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal):
     p.q, p.ldq, p.k, p.ldk = _ptr(q), ldq, _ptr(k), ldk
     p.vt, p.ldvt, p.vt_gstride, p.o, p.ldo = _ptr(vt), ldvt, vt_gstride, _ptr(o), ldo
     p.groups, p.heads, p.H, p.W, p.views = groups, heads, H, W, views
@@ -389,10 +392,48 @@ def attn_views(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H
         for j, u in enumerate(s):
             p.seg[v][j] = u
     p.scale, p.causal = scale, int(causal)
+
+
+def attn_views(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H, W, views,
+               kvH, kvW, kv_views, kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal=False, k_halo=None, vt_halo=None):
+    """`k_halo` / `vt_halo`: pairs (left, right) of buffers with the geometry of k / vt whose view column 0 holds a neighbour rank's
+    view — kv view id -1 / kv_views in `segs` (PncAttnParams.k_halo)"""
+    p = AttnParams()
+    if k_halo is not None:
+        for i in range(2):
+            p.k_halo[i], p.vt_halo[i] = _ptr(k_halo[i]), _ptr(vt_halo[i])
+    _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
+                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal)
     nq = H * (W // views)
     nkeys = sum(len(sv) for sv in segs) * kv_valid
     _check(_timed("attn_views", 4.0 * groups * heads * nq * nkeys * 64, 0.0, load().pnc_attn_views_f16,
                   C.byref(p), _stream()), "pnc_attn_views_f16")
+
+
+def attn_views_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, groups, heads, H, W, views, kvH, kvW, kv_views,
+                     kv_rows_per_group, q_per_kv, kv_valid, segs, scale):
+    """pnc_attn_views_split_f16: the geometry of `attn_views` on split operands (every *_lo an fp16 plane with its hi plane's
+    leading dimension); V is ROW-major, laid out like K"""
+    f16 = torch.float16
+    sp = AttnSplitParams()
+    sp.struct_bytes = C.sizeof(AttnSplitParams)
+    _attn_params(sp.a, q, ldq, k, ldk, v, ldv, 0, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views, kv_rows_per_group,
+                 q_per_kv, kv_valid, segs, scale, False)
+    sp.q_lo, sp.k_lo = _ptr(q_lo, f16, "q_lo"), _ptr(k_lo, f16, "k_lo")
+    sp.v_lo, sp.o_lo = _ptr(v_lo, f16, "v_lo"), _ptr(o_lo, f16, "o_lo")
+    nq = H * (W // views)
+    nkeys = sum(len(sv) for sv in segs) * kv_valid
+    _check(_timed("attn_views_split", 12.0 * groups * heads * nq * nkeys * 64, 0.0, load().pnc_attn_views_split_f16,
+                  C.byref(sp), _stream()), "pnc_attn_views_split_f16")
+
+
+def attn_temporal_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, B, T, Npix, heads, scale):
+    f16 = torch.float16
+    nb = 16.0 * B * T * Npix * heads * 64
+    _check(_timed("attn_temporal_split", 0.0, nb, load().pnc_attn_temporal_split_f16,
+                  _ptr(q, f16, "q"), _ptr(q_lo, f16, "q_lo"), ldq, _ptr(k, f16, "k"), _ptr(k_lo, f16, "k_lo"), ldk,
+                  _ptr(v, f16, "v"), _ptr(v_lo, f16, "v_lo"), ldv, _ptr(o, f16, "o"), _ptr(o_lo, f16, "o_lo"), ldo,
+                  B, T, Npix, heads, scale, _stream()), "pnc_attn_temporal_split_f16")
 
 
 def softmax_rows(s32, lds, M, N, scale, p16, ldp, causal=False, n_valid=0):

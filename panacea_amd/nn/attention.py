@@ -81,24 +81,38 @@ class FeedForward(nn.Module, Packable):
         w1, b1 = E.pk_geglu(self.net[0].proj.weight, self.net[0].proj.bias)
         return dict(w1=w1, b1=b1, w2=E.pk_linear(self.net[2].weight), b2=E.pk_f32(self.net[2].bias))
 
-    def _run(self, rt: Runtime, x16, M, res32, out32=None, out16=None, out16_lo=None):
-        """out = FF(x16) + res32 -> out32 (may alias res32) and/or out16 (+ lo plane of a precise operand)."""
+    def _run(self, rt: Runtime, x16, M, res32, out32=None, out16=None, out16_lo=None, x16_lo=None):
+        """out = FF(x16) + res32 -> out32 (may alias res32) and/or out16 (+ lo plane of a precise operand).  `x16_lo`: lo plane
+        of the input (operand class `ln`); the GEGLU hidden state is split when the policy splits `ff_hidden`."""
         pk = self.packed()
         hid = rt.empty((M, self.inner_dim), torch.float16)
+        hid_lo = rt.lo_plane((M, self.inner_dim), "ff_hidden")
+        wide = {} if x16_lo is None else dict(a16_lo=x16_lo)
         rt.be.gemm(x16, pk["w1"], M=M, N=2 * self.inner_dim, K=self.dim, lda=self.dim, bias=pk["b1"],
-                   geglu=True, out16=hid, ldc16=self.inner_dim)
+                   geglu=True, out16=hid, ldc16=self.inner_dim, **wide, **({} if hid_lo is None else dict(out16_lo=hid_lo)))
+        wide = {} if hid_lo is None else dict(a16_lo=hid_lo)
         rt.be.gemm(hid, pk["w2"], M=M, N=self.dim_out, K=self.inner_dim, lda=self.inner_dim, bias=pk["b2"],
                    res1=res32, ldr1=self.dim_out, out32=out32, ldc32=self.dim_out, out16=out16,
-                   ldc16=self.dim_out, out16_lo=out16_lo)
+                   ldc16=self.dim_out, out16_lo=out16_lo, **wide)
 
 
 def _ln_kwargs(rt: Runtime, ln, M: int, C: int):
     """kwargs that make a GEMM also write LayerNorm(out32 rows) as fp16 (PncGemmParams.ln_*): fused into the epilogue where
     a workgroup owns whole rows (level 0), the library's LayerNorm kernel right after the GEMM otherwise.  -> (kwargs, x16)"""
-    if ln is None:
+    if ln is None or rt.prec.ln:         # (a split LayerNorm output: the standalone kernel writes its lo plane, `_ln_after`)
         return {}, None
     x16 = rt.empty((M, C), torch.float16)
     return dict(ln_gamma=ln[0], ln_beta=ln[1], ln_out16=x16, ldln=C, ln_eps=1e-5), x16
+
+
+def _ln_after(rt: Runtime, ln, t32, M: int, C: int, y16):
+    """-> (y16, y16_lo) of the LayerNorm that follows a residual GEMM: what the GEMM wrote (`_ln_kwargs`), or — the policy splits
+    `ln`: the fused-LayerNorm epilogue has no lo plane — the standalone LayerNorm kernel with its lo plane"""
+    if ln is None:
+        return None, None
+    if rt.prec.ln:
+        return E.layer_norm_split(rt, t32, M, C, ln[0], ln[1])
+    return y16, None
 
 
 class _AttentionBase(nn.Module, Packable):
@@ -141,6 +155,14 @@ class _AttentionBase(nn.Module, Packable):
             return hit
         pk = self.packed()
         C, D, rows = self.inner_dim, rt.ctx16.shape[1], rt.B * E.TEXT_PAD
+        if rt.prec.kv_text:
+            # split policy: K and V row-major with their lo planes, one [rows, 2C] block -> (k, k_lo, v, v_lo, ld)
+            kv, kv_lo = rt.empty((rows, 2 * C), torch.float16), rt.lo_plane((rows, 2 * C), "kv_text")
+            if "wkv" not in pk:                       # [W_k; W_v], packed once next to them
+                pk["wkv"] = torch.cat([pk["wk"], pk["wv"]]).contiguous()
+            rt.be.gemm(rt.ctx16, pk["wkv"], M=rows, N=2 * C, K=D, lda=D, out16=kv, ldc16=2 * C, out16_lo=kv_lo, a16_lo=rt.ctx16_lo)
+            f, fl = kv.view(-1), kv_lo.view(-1)
+            return f, fl, f[C:], fl[C:], 2 * C
         k = rt.empty((rows, C), torch.float16)
         vt = rt.empty((rt.B, C, E.TEXT_PAD), torch.float16)
         rt.be.gemm(rt.ctx16, pk["wk"], M=rows, N=C, K=D, lda=D, out16=k, ldc16=C)
@@ -148,10 +170,19 @@ class _AttentionBase(nn.Module, Packable):
                    t_gstride=C * E.TEXT_PAD, n_split=0)
         return k, C, vt, E.TEXT_PAD, C * E.TEXT_PAD
 
-    def _run_text(self, rt: Runtime, x16, F, H, W, res32, out32, ln=None):
-        """`ln` = (gamma, beta) of the LayerNorm that follows the residual add: its fp16 output is returned"""
+    def _run_text(self, rt: Runtime, x16, F, H, W, res32, out32, ln=None, x16_lo=None):
+        """`ln` = (gamma, beta) of the LayerNorm that follows the residual add: its fp16 output (hi, lo) is returned"""
         pk = self.packed()
         C, M = self.inner_dim, F * H * W
+        if rt.prec.q_text:
+            q, q_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "q_text")
+            rt.be.gemm(x16, pk["wq"], M=M, N=C, K=self.query_dim, lda=self.query_dim, out16=q, ldc16=C, out16_lo=q_lo, a16_lo=x16_lo)
+            k, k_lo, v, v_lo, ld = self._text_kv(rt)
+            o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
+            rt.be.attn_views_split(q, q_lo, C, k, k_lo, ld, v, v_lo, ld, o, o_lo, C, groups=F, heads=self.heads, H=H, W=W,
+                                   views=1, kvH=1, kvW=E.TEXT_PAD, kv_views=1, kv_rows_per_group=E.TEXT_PAD, q_per_kv=F // rt.B,
+                                   kv_valid=rt.n_text, segs=[[0]], scale=self.scale)
+            return self._out_proj(rt, o, o_lo, M, C, res32, out32, ln)
         q = rt.empty((M, C), torch.float16)
         rt.be.gemm(x16, pk["wq"], M=M, N=C, K=self.query_dim, lda=self.query_dim, out16=q, ldc16=C)
         k, ldk, vt, ldvt, vt_gs = self._text_kv(rt)
@@ -162,10 +193,27 @@ class _AttentionBase(nn.Module, Packable):
         lnkw, y16 = _ln_kwargs(rt, ln, M, self.query_dim)
         rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32,
                    ldr1=self.query_dim, out32=out32, ldc32=self.query_dim, **lnkw)
-        return y16
+        return y16, None
+
+    def _out_proj(self, rt: Runtime, o, o_lo, M, C, res32, out32, ln):
+        """split policy: to_out(o) + res on the split attention output, then the LayerNorm that follows -> (y16, y16_lo)"""
+        pk = self.packed()
+        rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32, ldr1=self.query_dim, out32=out32,
+                   ldc32=self.query_dim, a16_lo=o_lo)
+        return _ln_after(rt, ln, out32, M, self.query_dim, None)
+
+    def _qkv_split(self, rt: Runtime, x16, x16_lo, M):
+        """split policy: the fused QKV GEMM into ONE row-major [M, 3C] block + lo plane (the split attention kernels read V
+        row-major: the transposed V^T store of the fp16 path has no lo plane) -> (qkv, qkv_lo)"""
+        pk = self.packed()
+        C = self.inner_dim
+        qkv, qkv_lo = rt.empty((M, 3 * C), torch.float16), rt.lo_plane((M, 3 * C), "qkv")
+        rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qkv, ldc16=3 * C, out16_lo=qkv_lo,
+                   a16_lo=x16_lo)
+        return qkv.view(-1), qkv_lo.view(-1)
 
     # ---- spatial self-attention over width-sliced views (views = 1: plain attention)
-    def _run_views(self, rt: Runtime, x16, F, H, W, segs, res32, out32, ln=None):
+    def _run_views(self, rt: Runtime, x16, F, H, W, segs, res32, out32, ln=None, x16_lo=None):
         pk = self.packed()
         C, N = self.inner_dim, H * W
         M = F * N
@@ -173,6 +221,15 @@ class _AttentionBase(nn.Module, Packable):
         views = vs.n_local if vs is not None else len(segs)
         if W % views:
             raise ValueError(f"grid width {W} is not divisible into {views} views")
+        if rt.prec.qkv:
+            if rt.vshard is not None:
+                raise ValueError("the precise-wide operand policy does not run view-sharded")
+            f, fl = self._qkv_split(rt, x16, x16_lo, M)
+            o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
+            rt.be.attn_views_split(f, fl, 3 * C, f[C:], fl[C:], 3 * C, f[2 * C:], fl[2 * C:], 3 * C, o, o_lo, C, groups=F,
+                                   heads=self.heads, H=H, W=W, views=views, kvH=H, kvW=W, kv_views=views, kv_rows_per_group=N,
+                                   q_per_kv=1, kv_valid=H * (W // views), segs=segs, scale=self.scale)
+            return self._out_proj(rt, o, o_lo, M, C, res32, out32, ln)
         qk = rt.empty((M, 2 * C), torch.float16)
         vt = rt.empty((F, C, N), torch.float16)
         rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qk, ldc16=2 * C,
@@ -197,13 +254,19 @@ class _AttentionBase(nn.Module, Packable):
         lnkw, y16 = _ln_kwargs(rt, ln, M, self.query_dim)
         rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32,
                    ldr1=self.query_dim, out32=out32, ldc32=self.query_dim, **lnkw)
-        return y16
+        return y16, None
 
     # ---- temporal self-attention over the T frames of each pixel
-    def _run_temporal(self, rt: Runtime, x16, N, res32, out32, ln=None):
+    def _run_temporal(self, rt: Runtime, x16, N, res32, out32, ln=None, x16_lo=None):
         pk = self.packed()
         C = self.inner_dim
         M = rt.B * rt.T * N              # all T frames of N pixels per sample (N = pixels per rank when frame-sharded)
+        if rt.prec.qkv:
+            f, fl = self._qkv_split(rt, x16, x16_lo, M)
+            o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
+            rt.be.attn_temporal_split(f, fl, 3 * C, f[C:], fl[C:], 3 * C, f[2 * C:], fl[2 * C:], 3 * C, o, o_lo, C, B=rt.B, T=rt.T,
+                                      Npix=N, heads=self.heads, scale=self.scale)
+            return self._out_proj(rt, o, o_lo, M, C, res32, out32, ln)
         qkv = rt.empty((M, 3 * C), torch.float16)
         rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qkv, ldc16=3 * C)
         o = rt.empty((M, C), torch.float16)
@@ -213,7 +276,7 @@ class _AttentionBase(nn.Module, Packable):
         lnkw, y16 = _ln_kwargs(rt, ln, M, self.query_dim)
         rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32,
                    ldr1=self.query_dim, out32=out32, ldc32=self.query_dim, **lnkw)
-        return y16
+        return y16, None
 
 
 class CrossAttention(_AttentionBase):
@@ -278,7 +341,7 @@ class BasicTransformerBlock(nn.Module, Packable):
         pk = self.packed()
         return pk["norm1w"], pk["norm1b"]
 
-    def _run(self, rt: Runtime, t32, F, H, W, branch: str, last: bool, x16=None):
+    def _run(self, rt: Runtime, t32, F, H, W, branch: str, last: bool, x16=None, x16_lo=None):
         """t32 [M, dim] fp32 stream, updated in place; returns the fp16 copy (hi, lo) of the final x when `last`
         (operand class `ff_out`).  `x16`: norm1(t32) when the GEMM that produced t32 has already written it.  norm2 / norm3
         are written by the residual GEMMs that precede them (PncGemmParams.ln_*), not by LayerNorm launches of their own."""
@@ -286,28 +349,31 @@ class BasicTransformerBlock(nn.Module, Packable):
         C, N = self.dim, H * W
         M = F * N
         if x16 is None:
-            x16 = E.layer_norm(rt, t32, M, C, pk["norm1w"], pk["norm1b"])
+            if rt.prec.ln:
+                x16, x16_lo = E.layer_norm_split(rt, t32, M, C, pk["norm1w"], pk["norm1b"])
+            else:
+                x16 = E.layer_norm(rt, t32, M, C, pk["norm1w"], pk["norm1b"])
         ln2, ln3 = (pk["norm2w"], pk["norm2b"]), (pk["norm3w"], pk["norm3b"])
         nviews = rt.vshard.n_local if rt.vshard is not None else 6
         if branch == "temporal":
-            x16 = self.attn1._run_temporal(rt, x16, N, t32, t32, ln=ln2)
+            x16, x16_lo = self.attn1._run_temporal(rt, x16, N, t32, t32, ln=ln2, x16_lo=x16_lo)
         elif self.attn1.kind == "intra-view":
             ph, pw = panorama_grid(N, nviews)
-            x16 = self.attn1._run_views(rt, x16, F, ph, pw, INTRA_SEGS, t32, t32, ln=ln2)
+            x16, x16_lo = self.attn1._run_views(rt, x16, F, ph, pw, INTRA_SEGS, t32, t32, ln=ln2, x16_lo=x16_lo)
         elif self.attn1.kind == "inter-view":
             ph, pw = panorama_grid(N, nviews)
-            x16 = self.attn1._run_views(rt, x16, F, ph, pw, INTER_SEGS, t32, t32, ln=ln2)
+            x16, x16_lo = self.attn1._run_views(rt, x16, F, ph, pw, INTER_SEGS, t32, t32, ln=ln2, x16_lo=x16_lo)
         else:
             if rt.vshard is not None:
                 raise NotImplementedError("plain spatial self-attention spans the whole panorama; a view shard serves the "
                                           "intra-view / inter-view kinds")
-            x16 = self.attn1._run_views(rt, x16, F, H, W, [[0]], t32, t32, ln=ln2)
-        x16 = self.attn2._run_text(rt, x16, F, H, W, t32, t32, ln=ln3)
+            x16, x16_lo = self.attn1._run_views(rt, x16, F, H, W, [[0]], t32, t32, ln=ln2, x16_lo=x16_lo)
+        x16, x16_lo = self.attn2._run_text(rt, x16, F, H, W, t32, t32, ln=ln3, x16_lo=x16_lo)
         out16 = out16lo = None
         if last:
             out16 = rt.empty((M, C), torch.float16)
             out16lo = rt.lo_plane((M, C), "ff_out")
-        self.ff._run(rt, x16, M, t32, out32=None if last else t32, out16=out16, out16_lo=out16lo)
+        self.ff._run(rt, x16, M, t32, out32=None if last else t32, out16=out16, out16_lo=out16lo, x16_lo=x16_lo)
         return (out16, out16lo) if last else None
 
 
@@ -394,6 +460,7 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         Mb = Fb * Hb * Wb
         t32 = rt.empty((Mb, C), torch.float32)
         lnkw, x16 = _ln_kwargs(rt, blocks[0].norm1_params(), Mb, C)          # norm1 of the first block rides on proj_in
+        # (split `ln`: no fused LayerNorm; the first block runs its own with the lo plane)
         if branch == "temporal":
             # + position table indexed by t = frame % T (attention.py:1117-1118)
             rt.be.gemm(n16, pk["wi" + sfx], M=Mb, N=C, K=C, lda=C, bias=pk["bi" + sfx], rowbias=pk["pos"],
@@ -488,6 +555,15 @@ class TextKVProjector:
         rows, D = rt.B * E.TEXT_PAD, rt.ctx16.shape[1]
         if Dm != D:
             raise ValueError(f"context width {D} does not match the cross-attention context_dim {Dm}")
+        if rt.prec.kv_text:
+            # split policy: every output column row-major with its lo plane (the split attention kernels read V row-major)
+            ld = NKp + NT
+            kv, kv_lo = rt.empty((rows, ld), torch.float16), rt.lo_plane((rows, ld), "kv_text")
+            rt.be.gemm(rt.ctx16, w, M=rows, N=ld, K=D, lda=D, out16=kv, ldc16=ld, out16_lo=kv_lo, a16_lo=rt.ctx16_lo)
+            f, fl = kv.view(-1), kv_lo.view(-1)
+            for a, o in zip(self.sites, offs):
+                rt.text_kv[id(a)] = (f[o:], fl[o:], f[NKp + o:], fl[NKp + o:], ld)
+            return
         k = rt.empty((rows, NKp), torch.float16)
         vt = rt.empty((rt.B, NT, E.TEXT_PAD), torch.float16)
         rt.be.gemm(rt.ctx16, w, M=rows, N=NKp + NT, K=D, lda=D, out16=k, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,

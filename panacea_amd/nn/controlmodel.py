@@ -194,7 +194,9 @@ class ControlledUNetModel3D(UNetModel3D):
             self._project_text(rt)
             self.controlnet._project_text(rt)
             guided = self.controlnet._hint_stem(rt, hint.detach().to(torch.float32).contiguous())
-        return StepInvariants(rt.ctx16, rt.n_text, dict(rt.text_kv), guided, (context, hint), rt.prec)
+        # the sources are kept (for StepInvariants.rebuild) only where the policy can still change: an un-escalated "escalate" network
+        keep = self.on_range_exceeded == "escalate" and not self.escalated
+        return StepInvariants(rt.ctx16, rt.n_text, dict(rt.text_kv), guided, (context, hint), rt.prec, rt.ctx16_lo, keep_sources=keep)
 
     two_stream = True      # run the ControlNet branch on a second HIP stream, concurrently with the UNet encoder
     split_samples = False  # additionally run every sample of the batch (CFG half) as its own stream pair
@@ -240,12 +242,20 @@ class ControlledUNetModel3D(UNetModel3D):
 
     def _denoise_one(self, x, timesteps, context, hint, trace, side_idx, inv=None, fused=None):
         with torch.no_grad():
+            return self._evaluate(lambda collect: self._denoise_once(x, timesteps, context, hint, trace, side_idx, inv, fused, collect),
+                                  x.device)
+
+    def _denoise_once(self, x, timesteps, context, hint, trace, side_idx, inv, fused, collect):
+        with torch.no_grad():
             rt = runtime_for(x if fused is None else fused[1], self.num_frames, self.frame_shard, self.view_shard)
             rt.prec = E.precision(self.precision)
             rt.trace = trace
             if inv is not None:
+                if inv.prec != rt.prec and self.escalated:
+                    inv.rebuild(self)              # prepared under the policy this network escalated from: text K/V, lo planes
                 inv.check(rt, context, hint)
                 rt.ctx16, rt.n_text, rt.text_kv, rt.text_frozen = inv.ctx16, inv.n_text, dict(inv.text_kv), True
+                rt.ctx16_lo = inv.ctx16_lo
                 rt.guided = inv.guided
             else:
                 rt.set_context(context)
@@ -291,16 +301,28 @@ class ControlledUNetModel3D(UNetModel3D):
                     for j, c in enumerate(control):
                         trace[f"control.{j}"] = c.to_nchw()
                 out = self._run_unet(rt, x16, self._time_embedding(rt, timesteps), control, tokens=fused is not None)
-            self._range_monitor_collect(rt)          # (both networks' kernels are ordered before this point of the current stream)
+            if collect:
+                self._range_monitor_collect(rt)      # (both networks' kernels are ordered before this point of the current stream)
         return out if fused is not None else out.to(x.dtype)
 
 
 class StepInvariants:
     """Result of ControlledUNetModel3D.prepare(): tensors that are constant over the sampler steps of one sample."""
 
-    def __init__(self, ctx16, n_text, text_kv, guided, sources, prec=E.FAST):
+    def __init__(self, ctx16, n_text, text_kv, guided, sources, prec=E.FAST, ctx16_lo=None, keep_sources=False):
         self.ctx16, self.n_text, self.text_kv, self.guided, self.prec = ctx16, n_text, text_kv, guided, prec
+        self.ctx16_lo = ctx16_lo
         self._src = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in sources)
+        self._sources = tuple(sources) if keep_sources else None
+
+    def rebuild(self, net: "ControlledUNetModel3D"):
+        """prepare the same (context, hint) again under the network's CURRENT policy, in place (every holder of this object —
+        the hoisted cond / uc of a sampler — sees the new tensors): after an "escalate" switch, the text K/V and the context of
+        the old policy must not be reused (they carry no lo planes)"""
+        if self._sources is None:
+            raise ValueError(f"StepInvariants prepared under {self.prec.name} cannot be rebuilt: they were prepared by a network "
+                             "that was not in on_range_exceeded='escalate' mode; prepare them again")
+        self.__dict__.update(net.prepare(*self._sources).__dict__)
 
     def check(self, rt: Runtime, context, hint):
         """The invariants belong to ONE (context, hint) pair: refuse anything else instead of silently reusing them."""

@@ -382,6 +382,11 @@ class EmbProjector:
             rt.emb_proj[id(b)] = out[s0 * F:s1 * F].view(F, s1 - s0)
 
 
+def _capturing(device) -> bool:
+    """the current stream of `device` is being captured into a graph"""
+    return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+
 class _OwnBlocks:
     """The blocks a network runs itself (a ControlledUNetModel3D must not walk into its `.controlnet` child)."""
 
@@ -531,6 +536,15 @@ class UNetModel3D(nn.Module, Packable):
         stated, and gated, at 2.5e-3 with every operand class split."""
         gmin = min(((m.out_channels // 32) * m.num_frames for m in self.modules() if isinstance(m, ResBlock3D)), default=4)
         prec = self.precision
+        esc = self.__dict__.get("_escalated")
+        if E.precision(prec) == E.PRECISE_WIDE:
+            # every operand class split with fp16 lo planes: the range of the bound is fp16's own (measured 8.5e-6 eps in the CPU
+            # error budget of the heavy-tail weight set, DESIGN.md section 6)
+            out = {"policy": prec, "eps_max_abs": 1e-3 if gmin >= 4 else 2.5e-3, "values_per_temporal_group": gmin,
+                   "valid_for": "|operand| < 65504"}
+            if esc is not None:
+                out["escalated_from"], out["trigger_count"] = esc["from"], esc["trigger_count"]
+            return out
         if prec in ("fast",):
             return {"policy": prec, "eps_max_abs": None, "note": "plain fp16 operands: measured 2.0-2.6e-3, no stated bound"}
         if gmin >= 4:
@@ -561,10 +575,67 @@ class UNetModel3D(nn.Module, Packable):
     # next evaluation or when `lo_clamped` is asked for).  The reference has no counterpart (wrappers.py:37-70 runs fp32 on CPU / an
     # unguarded autocast on CUDA).
     range_monitor = True
-    # what happens when an evaluation left the range: "warn" (once per network) or "raise".  (Measured and NOT offered: switching to fp16
-    # lo planes on every class once the range is left — on the heavy-tail weight set the error only drops by a quarter, 1.3e-2 ->
-    # 9.9e-3 on the tiny network: the massive channels amplify the fp16 rounding of the operands that are never split.)
+    # what happens when an evaluation left the range: "warn" (once per network), "raise", or "escalate" (below).  (fp16 lo planes on the
+    # classes of `precise` alone only cut the heavy-tail error by a quarter, 1.3e-2 -> 9.9e-3 on the tiny network: the massive channels
+    # amplify the fp16 rounding of the operands `precise` never splits.  "precise-wide" splits those too: 3.9e-5 there.)
     on_range_exceeded = "warn"
+    # "escalate": an eager evaluation under an e4m3 policy drains the counters before it starts, reads its own clamp count
+    # synchronously after it, and — count > 0 — switches this network (and its ControlNet) to "precise-wide" for good and evaluates
+    # the same inputs again; that result is returned.  Costs one device synchronisation per evaluation until it has escalated.
+    RANGE_MODES = ("warn", "raise", "escalate")
+
+    @property
+    def escalated(self) -> bool:
+        """True once an "escalate" evaluation has switched this network to "precise-wide" """
+        return self.__dict__.get("_escalated") is not None
+
+    def _range_count_sync(self, device) -> int:
+        """the clamp count since the previous collect, read back now (one device synchronisation)"""
+        self._range_monitor_poll(wait=True)                  # (asynchronous collects of earlier evaluations first)
+        buf = torch.zeros(1, dtype=torch.int32, device=device)
+        E.backend().range_monitor_collect(buf)
+        return int(buf[0].item())
+
+    def _escalate(self, count: int):
+        """switch this network and its ControlNet to "precise-wide" (sticky); packed weights do not depend on the policy, the text
+        K/V, lo planes and workspaces of later evaluations are allocated under the new one"""
+        self.__dict__["_escalated"] = {"from": self.precision, "trigger_count": count}
+        st = self._range_state()
+        st["last"], st["evals"], st["total"] = count, st["evals"] + 1, st["total"] + count
+        self.precision = "precise-wide"
+
+    def _check_unsharded_policy(self):
+        """precise-wide and "escalate" are single-device features: the split attention kernels have no halo views and sharded
+        evaluations are not re-run"""
+        if self.frame_shard is None and self.view_shard is None:
+            return
+        if self.on_range_exceeded == "escalate" or E.precision(self.precision) == E.PRECISE_WIDE:
+            raise ValueError("the 'precise-wide' operand policy and on_range_exceeded='escalate' do not run frame- or view-sharded")
+
+    def _evaluate(self, once, device):
+        """once(collect) runs ONE evaluation under the current policy (collect: enqueue the asynchronous range-monitor collect at its
+        end) and returns its output; this wraps it in the escalate protocol (see on_range_exceeded)"""
+        if self.on_range_exceeded not in self.RANGE_MODES:
+            raise ValueError(f"on_range_exceeded must be one of {self.RANGE_MODES}, got {self.on_range_exceeded!r}")
+        self._check_unsharded_policy()
+        if self.on_range_exceeded == "escalate" and not self.escalated and _capturing(device):
+            # a captured graph replays kernels only: the monitor would never run again (graph.refuse_unescalated says the same
+            # before a capture starts when it is given the network; this holds however the graph is built)
+            raise ValueError("on_range_exceeded='escalate' is not monitored during graph replay: capture the network after it has "
+                             "escalated, or use 'warn' / 'raise'")
+        if (self.on_range_exceeded != "escalate" or self.escalated or not self.range_monitor or not E.precision(self.precision).lo8
+                or _capturing(device)):
+            return once(True)
+        self._range_count_sync(device)                       # drain: the count read below belongs to THIS evaluation
+        out = once(False)
+        n = self._range_count_sync(device)
+        if n <= 0:
+            st = self._range_state()
+            st["last"], st["evals"] = 0, st["evals"] + 1
+            return out
+        self._escalate(n)
+        return once(True)
+
 
     def _range_state(self) -> dict:
         st = self.__dict__.get("_range_st")
@@ -769,11 +840,16 @@ class UNetModel3D(nn.Module, Packable):
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"
         from .util import runtime_for
-        with torch.no_grad():
+
+        def once(collect):
             rt = runtime_for(x, self.num_frames, self.frame_shard, self.view_shard)
             rt.prec = E.precision(self.precision)
             rt.set_context(context)
             emb = self._time_embedding(rt, timesteps)
             out = self._run_unet(rt, self._stem_tokens(rt, x), emb, None)
-            self._range_monitor_collect(rt)
+            if collect:
+                self._range_monitor_collect(rt)
+            return out
+        with torch.no_grad():
+            out = self._evaluate(once, x.device)
         return out.to(x.dtype)

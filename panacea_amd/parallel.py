@@ -228,11 +228,22 @@ class Groups:
         return ShardedCFG(scale, self.cfg_pair, self.layout.half) if self.layout.cfg > 1 else VanillaCFG(scale)
 
 
+def _refuse_wide(model):
+    """sharded evaluations run neither the 'precise-wide' operand policy nor the escalate protocol (UNetModel3D._check_unsharded_policy)"""
+    from . import engine as E
+    prec = getattr(model, "precision", None)
+    if getattr(model, "on_range_exceeded", None) == "escalate" or (prec is not None and E.precision(prec) == E.PRECISE_WIDE):
+        raise ValueError("the 'precise-wide' operand policy and on_range_exceeded='escalate' do not run sharded (frame / view shards, "
+                         "ShardedCFG)")
+
+
 def apply_frame_shard(network, shard: Optional[FrameShard], side_shard: Optional[FrameShard] = None):
     """Tell the network (OpenAIWrapperControlLDM3D or ControlledUNetModel3D) that its batches carry this rank's frame
     group only.  `side_shard`: the same shard over the ControlNet's own process group (`Groups.frame_shard(side=True)`): with it
     the ControlNet runs on its side stream in the sharded layout too."""
     model = getattr(network, "diffusion_model", network)
+    if shard is not None:
+        _refuse_wide(model)
     model.frame_shard = shard
     if hasattr(model, "controlnet"):
         model.controlnet.frame_shard = side_shard if (shard is not None and side_shard is not None) else shard
@@ -243,6 +254,8 @@ def apply_view_shard(network, shard: Optional[ViewShard], side_shard: Optional[V
     """Tell the network that its batches carry this rank's band of views only (W / V columns of the latent, of `concat`
     and of the BEV hint).  `side_shard`: see apply_frame_shard."""
     model = getattr(network, "diffusion_model", network)
+    if shard is not None:
+        _refuse_wide(model)
     model.view_shard = shard
     if hasattr(model, "controlnet"):
         model.controlnet.view_shard = side_shard if (shard is not None and side_shard is not None) else shard

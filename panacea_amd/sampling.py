@@ -151,7 +151,16 @@ class _Sampler:
         decided from these, without a sync)"""
         return self.discretization(self.num_steps if num_steps is None else num_steps, device="cpu").tolist()
 
+    def _check_cfg_half(self, denoiser):
+        """parallel.ShardedCFG evaluates one CFG half per rank: each rank would escalate on its own half's count, so the pair could end
+        up on two policies.  The sharded guider refuses 'precise-wide' and 'escalate' wherever it meets the network."""
+        net = getattr(denoiser, "network", None)
+        if net is not None and getattr(self.guider, "half", None) is not None:
+            from .parallel import _refuse_wide
+            _refuse_wide(getattr(net, "diffusion_model", net))
+
     def denoise(self, x, denoiser, sigma, cond, uc):
+        self._check_cfg_half(denoiser)
         if self.guider is None:
             return denoiser(x, sigma, cond)
         return self.guider(denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc)), sigma)
@@ -182,6 +191,7 @@ class _Sampler:
         c_in = 1 / (sig_q ** 2 + 1.0) ** 0.5
         c_noise = den.sigma_to_idx(sig_q)                             # quantised c_noise = the table index
         half = getattr(self.guider, "half", None)
+        self._check_cfg_half(denoiser)
         if self.guider is None:
             cat, inv, nh = cond, cond.get("_invariants"), 1
         elif half is not None:
@@ -741,6 +751,8 @@ def hoist_invariants(network, guider, cond: Dict, uc: Dict):
     half = getattr(guider, "half", None)
     if half is not None:
         # parallel.ShardedCFG: this rank evaluates ONE CFG half with that half's own tensors (same objects every step)
+        from .parallel import _refuse_wide
+        _refuse_wide(model)
         src = dict(uc if half == 0 else cond)
         src["crossattn"] = src["crossattn"].to(model.controlnet.input_hint_block[0].weight.dtype)
         inv = model.prepare(src["crossattn"], src["cond_feat"])
