@@ -283,8 +283,10 @@ typedef struct PncAttnParams {
 
 int pnc_attn_views_f16(const PncAttnParams* p, void* stream);
 
-/* Temporal self-attention over the T frames of one pixel (head dim 64):
+/* Temporal self-attention over the T frames of one pixel (head dim 64), 1 <= T <= 16:
  *   row m = (b*T+t)*Npix + p; q/k/v fp16 with leading dims; out fp16.
+ *   T <= 8: VALU kernel, 8 lanes per (frame, head); 9 <= T <= 16: one wave per (b, pixel, head) on the 16x16 MFMA
+ *   (B * Npix * heads < 2^31).  No row beyond frame T - 1 of a sample is read.  Other T: PNC_EINVAL.
  *    -> CrossAttention self-attn on "(b h w) t c" (attention.py:229-291, 1106-1134) */
 int pnc_attn_temporal_f16(const void* q, int ldq, const void* k, int ldk,
                           const void* v, int ldv, void* o, int ldo,
@@ -338,12 +340,15 @@ int pnc_groupnorm_apply(const float* x, int ldx, int F, int Npix, int C,
  * combination of pnc_groupnorm_apply unchanged, so that kernel normalises a band with the statistics of the whole panorama.
  *    -> nn.GroupNorm over the (H, 6w) panorama when its views live on several ranks (diffusionmodules/util.py:276-283) */
 int pnc_groupnorm_combine(const float* in, int parts, int F, int nchunk, float* out, void* stream);
-/* Temporal GroupNorm(32,C)+SiLU: statistics over the (C/32, T) slab of ONE pixel
+/* Temporal GroupNorm(32,C)+SiLU: statistics over the (C/32, T) slab of ONE pixel, 1 <= T <= 16 (other T: PNC_EINVAL),
+ * C % 64 == 0, C <= 2048
  *    -> nn.GroupNorm applied on "(b h w) c t" (openaimodel.py:409-419,509-515) */
 int pnc_groupnorm_temporal_silu(const float* x, int B, int T, int Npix, int C,
                                 const float* gamma, const float* beta, float eps,
                                 void* y16, void* y16_lo, int lo_fmt, void* stream);
-/* The same split over the ranks of a frame group (engine.FrameShard, round 4), for the T local frames of every pixel:
+/* The same split over the ranks of a frame group (engine.FrameShard, round 4), for the T local frames of every pixel
+ * (1 <= T <= 16 local frames; T_total >= T has no upper limit here — it only enters as the count n of the normalisation —
+ * the product itself builds networks of at most 16 frames):
  *   mode 1: stats[((b*Npix + p)*32 + g)*2 + {0,1}] = {sum, sum of squares} over the (C/32, T) values this rank holds;
  *   mode 2: normalise + SiLU with `stats` = those sums added over the ranks and T_total = frames per sample over all ranks;
  *           t_pad = 1 writes y into the (T + 2)-frame layout PncGemmParams.t_halo reads (frame t at slot t + 1).

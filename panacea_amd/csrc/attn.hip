@@ -19,6 +19,7 @@
 //
 // 2. attn_temporal_kernel: self-attention over the T <= 8 frames of one pixel.  25 GFLOP per step
 //    in total, so it is a bandwidth-bound VALU kernel: 8 lanes per (token, head), 16-byte loads.
+//    attn_temporal_wide_kernel: the same for 9 <= T <= 16, one wave per (pixel, head) on the 16x16 MFMA.
 #include "common.h"
 #include <stdlib.h>
 
@@ -665,6 +666,111 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// temporal attention, 9 <= T <= 16: one wave per (b, pixel, head) on the 16x16 MFMA — the single-plane sibling of
+// attn_temporal_split_kernel (attn_split.hip).
+//   S^T = K . Q^T  (v_mfma_f32_16x16x32_f16: A = 16 keys x 64 channels, B = 64 channels x 16 queries, two k-steps)
+// leaves key = 4 * (lane >> 4) + reg, query = lane & 15 in the accumulator, which IS the B fragment of P^T in
+//   O^T = V^T . P^T (v_mfma_f32_16x16x16_f16: A = 16 channels x 16 keys, B = 16 keys x 16 queries)
+// so the softmax statistics are one value per lane (reduced over the four 16-lane groups) and nothing moves between lanes.
+// Q and K fragments are read straight from memory: lane (row = lane & 15, g = lane >> 4) takes the 32 bytes of channels
+// 16 g .. 16 g + 15 of its row — the order of the summed channels is free as long as both operands use the same one.  V^T needs
+// the keys of one channel in one lane: the wave parks its V rows (32 bytes per lane, four adjacent lanes per row) in a
+// wave-private LDS slab and reads them back with the transposing ds_read_b64_tr_b16.  The slab keeps, per row, the 8-byte
+// pieces in the order [32-channel block e][half h][p] for channels 32 e + 8 p + 4 h .. + 3: the four addresses (p = 0..3) of one
+// transposed read are then 32 contiguous bytes, the 160-byte row stride spreads the eight rows of a 32-lane half over all 64
+// banks, and the accumulators of (e, h = 0) and (e, h = 1) hold 8 consecutive channels of the lane's query row: 16-byte stores.
+// Frames t >= T (T = 9..15): their rows are never read (the address is clamped to frame 0), their scores are masked to -inf
+// before the maximum and their V rows are ZERO in the slab — a P of 0 does not silence a NaN or Inf read from padding.
+// ------------------------------------------------------------------------------------------
+constexpr int TW_ROW = 80;          // halves per V row of the slab: 160 bytes
+
+__global__ __launch_bounds__(256) void attn_temporal_wide_kernel(
+    const half_t* __restrict__ Q, int ldq, const half_t* __restrict__ Kp, int ldk,
+    const half_t* __restrict__ Vp, int ldv, half_t* __restrict__ O, int ldo,
+    int T, int Npix, int heads, float scale, unsigned nwork) {
+    __shared__ __attribute__((aligned(16))) half_t sv[4][16 * TW_ROW];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned w = blockIdx.x * 4u + (unsigned)wv;  // the launcher keeps nwork below 2^31: 32-bit divisions
+    if (w >= nwork) return;            // wave-uniform: the transposed read below needs all 64 lanes of the wave active
+    // work item -> (b, pixel, head); head fastest so neighbouring waves share DRAM pages
+    const unsigned bp = w / (unsigned)heads;
+    const int head = (int)(w - bp * (unsigned)heads);
+    const unsigned b = bp / (unsigned)Npix, pix = bp - b * (unsigned)Npix;
+    const int64_t row0 = (int64_t)b * T * Npix + pix;  // frame t of this pixel: row0 + t * Npix
+    const int col = head * 64;
+    const int r = lane & 15, g = lane >> 4;
+    const int64_t row = row0 + (int64_t)(r < T ? r : 0) * Npix;
+    const half_t* qp = Q + row * ldq + col + 16 * g;
+    const half_t* kp = Kp + row * ldk + col + 16 * g;
+    const half8v q0 = *reinterpret_cast<const half8v*>(qp), q1 = *reinterpret_cast<const half8v*>(qp + 8);
+    const half8v k0 = *reinterpret_cast<const half8v*>(kp), k1 = *reinterpret_cast<const half8v*>(kp + 8);
+    // V row lane >> 2, channels 16 vp .. 16 vp + 15 (vp = lane & 3) -> the slab, as four 8-byte pieces
+    const int vr = lane >> 2, vp = lane & 3;
+    const bool vok = vr < T;
+    const half_t* vptr = Vp + (row0 + (int64_t)(vok ? vr : 0) * Npix) * ldv + col + 16 * vp;
+    half8v v0 = *reinterpret_cast<const half8v*>(vptr), v1 = *reinterpret_cast<const half8v*>(vptr + 8);
+    if (!vok) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { v0[i] = (half_t)0; v1[i] = (half_t)0; }
+    }
+    half_t* slab = sv[wv];
+    {
+        // channels 16 vp + 8 pp + 4 h .. + 3  ->  position 32 e + 16 h + 4 p  with e = vp >> 1, p = 2 (vp & 1) + pp
+        half_t* d = slab + vr * TW_ROW + 32 * (vp >> 1) + 8 * (vp & 1);
+        *reinterpret_cast<half4v*>(d) = half4v{v0[0], v0[1], v0[2], v0[3]};             // pp = 0, h = 0
+        *reinterpret_cast<half4v*>(d + 16) = half4v{v0[4], v0[5], v0[6], v0[7]};        // pp = 0, h = 1
+        *reinterpret_cast<half4v*>(d + 4) = half4v{v1[0], v1[1], v1[2], v1[3]};         // pp = 1, h = 0
+        *reinterpret_cast<half4v*>(d + 20) = half4v{v1[4], v1[5], v1[6], v1[7]};        // pp = 1, h = 1
+    }
+    f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+    s = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, q0, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, q1, s, 0, 0, 0);
+    const float c = scale * 1.44269504088896340736f;
+    float sc[4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        sc[i] = (4 * g + i < T) ? s[i] * c : -INFINITY;
+        mx = fmaxf(mx, sc[i]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));            // finite: key 0 is always there
+    float l = 0.0f;
+    half4v ph;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float p = (4 * g + i < T) ? exp2f(sc[i] - mx) : 0.0f;
+        l += p;
+        ph[i] = (half_t)p;
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    // (one wave = one LDS slab: wave-level execution order makes the writes visible to the reads below)
+    __builtin_amdgcn_wave_barrier();
+    // transposed read: lane 4 q + p of a 16-lane group gives the address of key row 4 g + q, piece p; lane i of the group
+    // receives column i = 4 p' + c of the four rows, i.e. channel 32 e + 8 p' + 4 h + c of keys 4 g .. 4 g + 3
+    typedef __fp16 tr_half4v __attribute__((__vector_size__(4 * sizeof(__fp16))));      // the builtin's own vector type
+    typedef __attribute__((address_space(3))) tr_half4v lds_half4v;
+    const half_t* tr = slab + (4 * g + ((lane >> 2) & 3)) * TW_ROW + 4 * (lane & 3);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        f32x4 acc[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const half4v vt = __builtin_bit_cast(half4v, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_half4v*)(tr + 32 * e + 16 * h)));
+            acc[h] = __builtin_amdgcn_mfma_f32_16x16x16f16(vt, ph, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+        }
+        if (r < T) {
+            half8v o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { o[i] = (half_t)(acc[0][i] * inv); o[4 + i] = (half_t)(acc[1][i] * inv); }
+            *reinterpret_cast<half8v*>(O + row * ldo + col + 32 * e + 8 * g) = o;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int pnc_attn_views_f16(const PncAttnParams* pp, void* stream) {
@@ -758,9 +864,20 @@ extern "C" int pnc_attn_temporal_f16(const void* q, int ldq, const void* k, int 
                                      const void* v, int ldv, void* o, int ldo,
                                      int B, int T, int Npix, int heads, float scale, void* stream) {
     if (!q || !k || !v || !o) return PNC_EINVAL;
-    if (T < 1 || T > 8 || B < 1 || Npix < 1 || heads < 1) return PNC_EINVAL;
+    if (T < 1 || T > 16 || B < 1 || Npix < 1 || heads < 1) return PNC_EINVAL;
     if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return PNC_EALIGN;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return PNC_EALIGN;
+    if (T > 8) {                        // 9 .. 16 frames: one wave per (b, pixel, head) on the 16x16 MFMA
+        const int64_t nwork = (int64_t)B * Npix * heads;
+        if (nwork > 0x7fffffff) return PNC_EINVAL;
+        const int64_t blocks = (nwork + 3) / 4;
+        hipLaunchKernelGGL(attn_temporal_wide_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                           reinterpret_cast<hipStream_t>(stream),
+                           reinterpret_cast<const half_t*>(q), ldq, reinterpret_cast<const half_t*>(k), ldk,
+                           reinterpret_cast<const half_t*>(v), ldv, reinterpret_cast<half_t*>(o), ldo,
+                           T, Npix, heads, scale, (unsigned)nwork);
+        return pnc_launch_status();
+    }
     const int ppw = 8 / T;
     const int64_t nwork = (int64_t)B * ((Npix + ppw - 1) / ppw) * heads;
     const int64_t blocks = (nwork + 3) / 4;

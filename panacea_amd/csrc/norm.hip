@@ -184,8 +184,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
 // pixel are spread over the ranks of a frame group — 1 writes this rank's {sum, sum of squares} per (pixel, group), 2 normalises
 // the local frames with the sums added over the ranks (n = values per group over ALL T_total frames); t_pad: output frame t of
 // sample b goes to slot t + 1 of a (T + 2)-frame layout, the halo frames of the temporal conv around it.
-template <int T, int MODE = 0>
-__global__ __launch_bounds__(256) void gn_temporal_kernel(const float* __restrict__ x, int B, int Npix, int C,
+// T > 8 (9 .. 16 frames): 16 float4 per item — two items per lane would be 128 VGPRs of payload.  The block then has 512 threads
+// with ONE item each (NIT = 1): the same PB, the same LDS image and the same arithmetic per item, 64 VGPRs of payload per lane.
+template <int T, int MODE = 0, int NIT = (T <= 8 ? 2 : 1)>
+__global__ __launch_bounds__(512 / NIT) void gn_temporal_kernel(const float* __restrict__ x, int B, int Npix, int C,
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float eps,
                                                           half_t* __restrict__ y, void* __restrict__ ylo, int lo_fmt, int PB,
@@ -198,12 +200,13 @@ __global__ __launch_bounds__(256) void gn_temporal_kernel(const float* __restric
     const int64_t bp0 = (int64_t)blockIdx.x * PB;   // first (b*Npix + pixel) of the block
     const int64_t total = (int64_t)B * Npix;
     const int nwork = PB * C4;                      // <= 512 (host picks PB)
-    f32x4 v[2][T];
-    int64_t off[2], offo[2];
-    bool live[2];
+    constexpr int NT = 512 / NIT;                   // threads per block
+    f32x4 v[NIT][T];
+    int64_t off[NIT], offo[NIT];
+    bool live[NIT];
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int wi = tid + it * 256;
+    for (int it = 0; it < NIT; ++it) {
+        const int wi = tid + it * NT;
         const int pl = wi / C4, c4 = wi - pl * C4;
         const int64_t bp = bp0 + pl;
         live[it] = (wi < nwork) && (bp < total);
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(256) void gn_temporal_kernel(const float* __restric
         }
     }
     __syncthreads();
-    for (int gi = tid; gi < PB * GROUPS; gi += 256) {
+    for (int gi = tid; gi < PB * GROUPS; gi += NT) {
         const int pl = gi / GROUPS, g = gi - pl * GROUPS;
         float s = 0.0f, q = 0.0f;
         for (int j = 0; j < cpg2; ++j) {
@@ -250,9 +253,9 @@ __global__ __launch_bounds__(256) void gn_temporal_kernel(const float* __restric
     if constexpr (MODE == 1) return;
     __syncthreads();
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
+    for (int it = 0; it < NIT; ++it) {
         if (!live[it]) continue;
-        const int wi = tid + it * 256;
+        const int wi = tid + it * NT;
         const int pl = wi / C4, c4 = wi - pl * C4;
         const int ga = (c4 * 2) / cpg2, gb = (c4 * 2 + 1) / cpg2;
         const float ma = s_stat[(pl * GROUPS + ga) * 2], ra = s_stat[(pl * GROUPS + ga) * 2 + 1];
@@ -559,7 +562,7 @@ extern "C" int pnc_groupnorm_temporal_silu(const float* x, int B, int T, int Npi
                                            void* y16, void* y16_lo, int lo_fmt, void* stream) {
     if (!x || !gamma || !beta || !y16 || B < 1 || Npix < 1) return PNC_EINVAL;
     if (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3) return PNC_EINVAL;
-    if (C % 64 || C > 2048 || T < 1 || T > 8) return PNC_EINVAL;     // <= 512 four-channel items per pixel
+    if (C % 64 || C > 2048 || T < 1 || T > 16) return PNC_EINVAL;    // <= 512 four-channel items per pixel
     if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return PNC_EALIGN;
     if (((uintptr_t)y16 | (uintptr_t)y16_lo) & 7) return PNC_EALIGN;
     const int CP = C / 2;
@@ -569,10 +572,11 @@ extern "C" int pnc_groupnorm_temporal_silu(const float* x, int B, int T, int Npi
     const size_t lds = ((size_t)PB * CP * 2 + (size_t)PB * GROUPS * 2) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     half_t* y = reinterpret_cast<half_t*>(y16);
-#define PNC_GNT(TT) case TT: hipLaunchKernelGGL((gn_temporal_kernel<TT, 0>), dim3(blocks), dim3(256), lds, st, \
+#define PNC_GNT(TT) case TT: hipLaunchKernelGGL((gn_temporal_kernel<TT, 0>), dim3(blocks), dim3(TT <= 8 ? 256 : 512), lds, st, \
                                                x, B, Npix, C, gamma, beta, eps, y, y16_lo, lo_fmt, PB, (float*)nullptr, TT, 0); break;
     switch (T) {
         PNC_GNT(1) PNC_GNT(2) PNC_GNT(3) PNC_GNT(4) PNC_GNT(5) PNC_GNT(6) PNC_GNT(7) PNC_GNT(8)
+        PNC_GNT(9) PNC_GNT(10) PNC_GNT(11) PNC_GNT(12) PNC_GNT(13) PNC_GNT(14) PNC_GNT(15) PNC_GNT(16)
     }
 #undef PNC_GNT
     return pnc_launch_status();
@@ -583,7 +587,7 @@ extern "C" int pnc_groupnorm_temporal_part(const float* x, int B, int T, int Npi
                                            float* stats, int mode, int T_total,
                                            void* y16, void* y16_lo, int lo_fmt, int t_pad, void* stream) {
     if (!x || !stats || B < 1 || Npix < 1 || (mode != 1 && mode != 2)) return PNC_EINVAL;
-    if (C % 64 || C > 2048 || T < 1 || T > 8 || T_total < T || (t_pad != 0 && t_pad != 1)) return PNC_EINVAL;
+    if (C % 64 || C > 2048 || T < 1 || T > 16 || T_total < T || (t_pad != 0 && t_pad != 1)) return PNC_EINVAL;
     if (mode == 2 && (!gamma || !beta || !y16 || (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3))) return PNC_EINVAL;
     if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return PNC_EALIGN;
     if (((uintptr_t)y16 | (uintptr_t)y16_lo | (uintptr_t)stats) & 7) return PNC_EALIGN;
@@ -595,13 +599,14 @@ extern "C" int pnc_groupnorm_temporal_part(const float* x, int B, int T, int Npi
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     half_t* y = reinterpret_cast<half_t*>(y16);
 #define PNC_GNTP(TT) case TT:                                                                                              \
-        if (mode == 1) hipLaunchKernelGGL((gn_temporal_kernel<TT, 1>), dim3(blocks), dim3(256), lds, st, x, B, Npix, C, gamma, beta, \
+        if (mode == 1) hipLaunchKernelGGL((gn_temporal_kernel<TT, 1>), dim3(blocks), dim3(TT <= 8 ? 256 : 512), lds, st, x, B, Npix, C, gamma, beta, \
                                           eps, y, y16_lo, lo_fmt, PB, stats, T_total, t_pad);                              \
-        else hipLaunchKernelGGL((gn_temporal_kernel<TT, 2>), dim3(blocks), dim3(256), lds, st, x, B, Npix, C, gamma, beta, eps, y, \
+        else hipLaunchKernelGGL((gn_temporal_kernel<TT, 2>), dim3(blocks), dim3(TT <= 8 ? 256 : 512), lds, st, x, B, Npix, C, gamma, beta, eps, y, \
                                 y16_lo, lo_fmt, PB, stats, T_total, t_pad);                                                \
         break;
     switch (T) {
         PNC_GNTP(1) PNC_GNTP(2) PNC_GNTP(3) PNC_GNTP(4) PNC_GNTP(5) PNC_GNTP(6) PNC_GNTP(7) PNC_GNTP(8)
+        PNC_GNTP(9) PNC_GNTP(10) PNC_GNTP(11) PNC_GNTP(12) PNC_GNTP(13) PNC_GNTP(14) PNC_GNTP(15) PNC_GNTP(16)
     }
 #undef PNC_GNTP
     return pnc_launch_status();

@@ -24,6 +24,7 @@ from torch import nn
 
 from .. import engine as E
 from ..engine import Act, Packable, Runtime
+from .util import check_num_frames
 
 HEAD_DIM = 64
 INTRA_SEGS = [[0], [1], [2], [3], [4], [5]]
@@ -387,6 +388,7 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         super().__init__()
         if not use_linear:
             raise NotImplementedError("use_linear_in_transformer=False (1x1-conv projections) is not on the Panacea path")
+        num_frames = check_num_frames(num_frames, "SpatialTemporalTransformer")
         self.insert_crossview = insert_crossview
         self.num_frames = num_frames
         self.alpha = 1 if alpha == 1 else nn.Parameter(torch.rand(1, requires_grad=True))

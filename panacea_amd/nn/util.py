@@ -52,6 +52,20 @@ def linear(*args, **kwargs):
     return nn.Linear(*args, **kwargs)
 
 
+# ---- supported clip length --------------------------------------------------------------------
+MAX_FRAMES = 16          # frames per sample the temporal kernels take (pnc_attn_temporal_f16, pnc_groupnorm_temporal_*: T <= 16)
+
+
+def check_num_frames(num_frames: int, who: str) -> int:
+    """Refuse a clip length the temporal kernels do not take when the module is BUILT, not with a PNC_EINVAL from the middle of
+    the first evaluation (the reference's `num_frames` / FrameLength option has no upper limit; this path has)."""
+    if not 1 <= int(num_frames) <= MAX_FRAMES:
+        raise NotImplementedError(f"{who}: num_frames = {num_frames} is outside the supported range 1..{MAX_FRAMES} "
+                                  f"(the gfx950 temporal attention and temporal GroupNorm kernels hold at most {MAX_FRAMES} frames "
+                                  "of a pixel in one wave / one work item)")
+    return int(num_frames)
+
+
 # ---- API-boundary glue ------------------------------------------------------------------------
 def runtime_for(x: torch.Tensor, num_frames: int, shard=None, vshard=None) -> Runtime:
     """`shard`: engine.FrameShard when x carries only this rank's num_frames / G frames of every sample; `vshard`:

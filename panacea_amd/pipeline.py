@@ -21,7 +21,9 @@ SCALE_FACTOR = 0.18215
 def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
                   noise: torch.Tensor, num_steps: int = 25, cfg_scale: float = 5.0, hoist: bool = True,
                   scale_factor: float = SCALE_FACTOR, sampler=None) -> torch.Tensor:
-    """noise: (T, 4, h, w) unit-variance latents of ONE sample; returns (T, 3, 8h, 8w) frames.
+    """noise: (T, 4, h, w) unit-variance latents of ONE sample; returns (T, 3, 8h, 8w) frames.  T is taken from `noise` and has
+    to be the `num_frames` the network was built with (configs.with_frames), 1 <= T <= 16: the temporal kernels hold at most 16
+    frames of a pixel, and a network for a longer clip is refused when it is built.
     `sampler`: None = the YAML's 25-step Euler / CFG `cfg_scale` (num_steps, cfg_scale apply); a sampler mirror of
     panacea_amd.sampling; or a reference `sampler_config` dict (sampling.from_config; its num_steps, else `num_steps`)."""
     dev = noise.device

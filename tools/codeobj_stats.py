@@ -49,8 +49,10 @@ def kernels(elf: Path):
 
 def short(name: str) -> str:
     d = subprocess.check_output([CXXFILT, name], text=True).strip()
-    d = re.sub(r"\(.*$", "", d).replace("pnc_gemm::", "").replace("(anonymous namespace)::", "")
-    return re.sub(r"^void ", "", d)
+    if d == name and "DF16_" in name:          # a c++filt that does not know _Float16's mangling: demangle it as `half`
+        d = subprocess.check_output([CXXFILT, name.replace("DF16_", "Dh")], text=True).strip()
+    d = re.sub(r"^void ", "", d).replace("pnc_gemm::", "").replace("(anonymous namespace)::", "")   # before the cut at the arguments
+    return re.sub(r"\(.*$", "", d)
 
 
 def main():

@@ -6,6 +6,7 @@ per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference'
 
     python tools/sample.py --steps 5 --out gpurun_out/sample
     python tools/sample.py --sampler dpmpp2m --steps 15
+    python tools/sample.py --frames 16 --steps 5          (clips of 1 .. 16 frames; the default 8 is the released FrameLength)
 """
 import argparse, json, sys, time
 from pathlib import Path
@@ -29,9 +30,10 @@ def main():
     ap.add_argument("--seed", type=int, default=3407)
     ap.add_argument("--sampler", choices=sorted(SAMPLERS), default="euler")
     ap.add_argument("--cfg-scale", type=float, default=5.0)
+    ap.add_argument("--frames", type=int, default=8, choices=range(1, 17), metavar="1..16", help="frames per clip (num_frames)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    kw = configs.get("full")
+    kw = configs.with_frames(configs.get("full"), a.frames)
     net = build_network(kw)
     fs = model.FirstStageDecoder(4, VAE)
     if a.ckpt:
@@ -43,7 +45,8 @@ def main():
         net.diffusion_model.load_state_dict(synth.synth_state_dict(man), strict=True)
         fs.load_state_dict(synth.synth_state_dict({k: list(v.shape) for k, v in fs.state_dict().items()}), strict=True)
     net, fs = net.to(dev), fs.to(dev)
-    B, T, h, w = configs.SHAPES["full"]
+    _, _, h, w = configs.SHAPES["full"]
+    T = a.frames
     g = {k: v.to(dev) for k, v in synth.synth_inputs(2, T, h, w, context_dim=kw["context_dim"]).items()}
     cond = {"crossattn": g["crossattn"][1:2], "concat": g["concat"][T:], "cond_feat": g["cond_feat"][T:]}
     uc = {"crossattn": g["crossattn"][0:1], "concat": g["concat"][:T], "cond_feat": g["cond_feat"][:T]}
