@@ -384,6 +384,12 @@ int pnc_linear_smallm_segments(const float* a, int lda, const void* W, const flo
  * tabulated by the caller  (diffusionmodules/util.py:224-248) */
 int pnc_timestep_embedding(const int64_t* t, int F, int dim, const float* freqs,
                            float* out, void* stream);
+/* the same embedding from FLOAT timesteps: the c_noise of the continuous Denoiser (denoiser.py:6-28), of
+ * DiscreteDenoiser(quantize_c_noise=False) (denoiser.py:59-63) and of EDMScaling (0.25 * log(sigma), denoiser_scaling.py:12),
+ * which the reference's timestep_embedding takes as they are (util.py:224-248: `timesteps[:, None].float() * freqs[None]`).
+ * Per element the arithmetic of pnc_timestep_embedding after its conversion float(t): bit-identical to it for integer-valued t. */
+int pnc_timestep_embedding_f32(const float* t, int F, int dim, const float* freqs,
+                               float* out, void* stream);
 /* NCHW (fp32) -> channels-last fp16 with optional second source (channel concat) and zero padding to Cpad:
  *   out[f][p][c] = c<C1 ? a[f % a_frames][c][p]*a_scale[f] : c<C1+C2 ? b[f][c-C1][p] : 0
  * a_scale NULL = 1: the per-frame c_in of DiscreteDenoiser (denoiser.py:27-28) folded into the conversion; a_frames < F:
@@ -446,6 +452,16 @@ typedef struct PncSamplerStepParams {
     float* out_aux;
 } PncSamplerStepParams;
 int pnc_cfg_sampler_step(const PncSamplerStepParams* p, void* stream);
+/* The two exit kernels with a general skip term, for the parameterisations whose c_skip is not 1 — VScaling (v-prediction) and
+ * EDMScaling (denoiser_scaling.py:4-13, 25-31) under Denoiser / DiscreteDenoiser (denoiser.py:22-28):
+ *   D_h = eps_h * c_out + x * c_skip                 two products, each rounded on its own, then the sum (denoiser.py:28)
+ * c_skip [T] fp32 on the device; everything after D_h (CFG combine, the sampler's update, every operand and mode) is that of
+ * pnc_cfg_euler_step / pnc_cfg_sampler_step — one device function, so c_skip = 1 gives their bits.  A NULL c_skip is
+ * PNC_EINVAL (it is never read as 1: the eps path is the two entries above); PNC_EABI as pnc_cfg_sampler_step. */
+int pnc_cfg_euler_step_skip(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
+                            const float* x, const float* c_skip, const float* c_out, const float* sigma,
+                            const float* sigma_next, float* x_next, void* stream);
+int pnc_cfg_sampler_step_skip(const PncSamplerStepParams* p, const float* c_skip, void* stream);
 /* channels-last fp32 [F*Npix][ld] -> NCHW fp32 (first C columns) */
 int pnc_tokens_to_nchw_f32(const float* x, int ld, int F, int Npix, int C,
                            float* out, void* stream);

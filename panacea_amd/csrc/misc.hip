@@ -118,7 +118,10 @@ __global__ __launch_bounds__(256) void linear_smallm_seg_kernel(const float* __r
     }
 }
 
-__global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, int F, int dim,
+// TS = int64_t (table indices: quantised c_noise) or float (a continuous c_noise: Denoiser, quantize_c_noise = False): the same
+// arithmetic after the conversion float(t), so integer-valued float timesteps give the int64 kernel's bits
+template <typename TS>
+__global__ void timestep_embedding_kernel(const TS* __restrict__ t, int F, int dim,
                                           const float* __restrict__ freqs, float* __restrict__ out) {
     const int half = dim / 2;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -221,13 +224,15 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ x, c
 
 // Exit of a sampler step: eps tokens of the CFG batch -> next latent, one pass.  The arithmetic
 // follows the reference's sequence of fp32 roundings (no contraction into FMAs), so a trajectory matches the reference's
-// sampler to the last few ulps.
+// sampler to the last few ulps.  SKIP: the general-skip form (x * c_skip[t] rounded on its own, then the sum: denoiser.py:28) of
+// VScaling / EDMScaling; SKIP = false is the eps path (c_skip = 1, x enters the sum as it is) and reads no c_skip.
+template <bool SKIP>
 __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const float* __restrict__ eps, int ld, int T, int Npix, int C,
                                                              int cfg, float scale, const float* __restrict__ x,
                                                              const float* __restrict__ c_out,
                                                              const float* __restrict__ sigma,
                                                              const float* __restrict__ sigma_next,
-                                                             float* __restrict__ xn) {
+                                                             float* __restrict__ xn, const float* __restrict__ c_skip) {
     // every product and sum below is rounded on its own, like the reference's separate elementwise kernels.  The operators
     // are written out under `fp contract(off)` (HIP's __fmul_rn / __fadd_rn are plain inline operators compiled under the
     // default contract(fast), so they DO fuse into FMAs)
@@ -236,17 +241,19 @@ __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const float* __rest
     if (i >= (int64_t)T * Npix) return;
     const int64_t t = i / Npix, pix = i - t * Npix;
     const float sg = sigma[t], dt = sigma_next[t] - sg, co = c_out[t];
+    const float cs = SKIP ? c_skip[t] : 1.0f;
     const float* eu = eps + i * ld;                               // uncond half first (guiders.py:36)
     const float* ec = eps + ((int64_t)(cfg ? T : 0) * Npix + i) * ld;
     for (int c = 0; c < C; ++c) {
         const int64_t o = (t * C + c) * Npix + pix;
         const float xv = x[o];
+        const float xs = SKIP ? xv * cs : xv;                            // x * c_skip   (eps path: c_skip = 1)
         const float pc = ec[c] * co;
-        const float dc = pc + xv;                                        // eps * c_out + x * c_skip   (c_skip = 1)
+        const float dc = pc + xs;                                        // eps * c_out + x * c_skip
         float d = dc;
         if (cfg) {
             const float pu = eu[c] * co;
-            const float du = pu + xv;
+            const float du = pu + xs;
             const float g = scale * (dc - du);
             d = du + g;                                                  // x_u + scale * (x_c - x_u)
         }
@@ -257,13 +264,15 @@ __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const float* __rest
 }
 
 // Exit of a step of the other samplers (include/panacea_hip.h: pnc_cfg_sampler_step).  Same denoised as above, then the
-// mode's update, every operation rounded on its own in the reference's order.
-__global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerStepParams p) {
+// mode's update, every operation rounded on its own in the reference's order.  SKIP as above.
+template <bool SKIP>
+__global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerStepParams p, const float* __restrict__ c_skip) {
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)p.T * p.Npix) return;
     const int64_t t = i / p.Npix, pix = i - t * p.Npix;
     const float co = p.c_out[t];
+    const float cs = SKIP ? c_skip[t] : 1.0f;
     const float v0 = p.v[0] ? p.v[0][t] : 0.f, v1 = p.v[1] ? p.v[1][t] : 0.f, v2 = p.v[2] ? p.v[2][t] : 0.f;
     const float v3 = p.v[3] ? p.v[3][t] : 0.f, v4 = p.v[4] ? p.v[4][t] : 0.f;
     const float* eu = p.eps_tok + i * p.ld;
@@ -271,11 +280,12 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
     for (int c = 0; c < p.C; ++c) {
         const int64_t o = (t * p.C + c) * p.Npix + pix;
         const float xv = p.x[o];
+        const float xs = SKIP ? xv * cs : xv;
         const float pc = ec[c] * co;
-        float D = pc + xv;
+        float D = pc + xs;
         if (p.cfg) {
             const float pu = eu[c] * co;
-            const float du = pu + xv;
+            const float du = pu + xs;
             const float g = p.scale * (D - du);
             D = du + g;
         }
@@ -321,24 +331,24 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
             const float a = v0 * p.x0[o];
             const float b = v1 * D;
             const float xd = a - b;
-            const float xs = v2 > 0.f ? xd : p.aux[o];
+            const float xsel = v2 > 0.f ? xd : p.aux[o];
             const float ns = p.noise[o] * p.s_noise;
             const float up = ns * v3;
-            y = v4 > 0.f ? xs + up : xs;
+            y = v4 > 0.f ? xsel + up : xsel;
             break;
         }
         case PNC_SAMPLER_DPM2M: {
             const float a = v0 * xv;
             const float b = v1 * D;
-            const float xs = a - b;
-            y = xs;
+            const float xst = a - b;
+            y = xst;
             if (p.aux) {
                 const float m3 = v2 * D;
                 const float m4 = v3 * p.aux[o];
                 const float dd = m3 - m4;
                 const float b2 = v1 * dd;
                 const float xa = a - b2;
-                y = v4 > 0.f ? xa : xs;
+                y = v4 > 0.f ? xa : xst;
             }
             p.out_aux[o] = D;
             break;
@@ -360,20 +370,40 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
 
 }  // namespace
 
-extern "C" int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
-                                  const float* x, const float* c_out, const float* sigma, const float* sigma_next,
-                                  float* x_next, void* stream) {
+static int cfg_euler_step_launch(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale, const float* x,
+                                 const float* c_out, const float* sigma, const float* sigma_next, float* x_next,
+                                 const float* c_skip, bool skip, void* stream) {
     if (!eps_tok || !x || !c_out || !sigma || !sigma_next || !x_next || T < 1 || Npix < 1 || C < 1 || ld < C) return PNC_EINVAL;
+    if (skip && !c_skip) return PNC_EINVAL;                          // never "c_skip = 1": the eps path is pnc_cfg_euler_step
     const int64_t n = (int64_t)T * Npix;
-    hipLaunchKernelGGL(cfg_euler_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (skip)
+        hipLaunchKernelGGL(cfg_euler_step_kernel<true>, grid, block, 0, st, eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma,
+                           sigma_next, x_next, c_skip);
+    else
+        hipLaunchKernelGGL(cfg_euler_step_kernel<false>, grid, block, 0, st, eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma,
+                           sigma_next, x_next, static_cast<const float*>(nullptr));
     return pnc_launch_status();
 }
 
-extern "C" int pnc_cfg_sampler_step(const PncSamplerStepParams* pp, void* stream) {
+extern "C" int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
+                                  const float* x, const float* c_out, const float* sigma, const float* sigma_next,
+                                  float* x_next, void* stream) {
+    return cfg_euler_step_launch(eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next, nullptr, false, stream);
+}
+
+extern "C" int pnc_cfg_euler_step_skip(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
+                                       const float* x, const float* c_skip, const float* c_out, const float* sigma,
+                                       const float* sigma_next, float* x_next, void* stream) {
+    return cfg_euler_step_launch(eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip, true, stream);
+}
+
+static int cfg_sampler_step_launch(const PncSamplerStepParams* pp, const float* c_skip, bool skip, void* stream) {
     if (!pp || pp->struct_bytes != (int32_t)sizeof(PncSamplerStepParams)) return PNC_EABI;
     const PncSamplerStepParams& p = *pp;
     if (!p.eps_tok || !p.x || !p.c_out || !p.out || p.T < 1 || p.Npix < 1 || p.C < 1 || p.ld < p.C) return PNC_EINVAL;
+    if (skip && !c_skip) return PNC_EINVAL;                          // never "c_skip = 1": the eps path is pnc_cfg_sampler_step
     int nv = 0;                                                      // per-frame vectors the mode reads
     bool ok = true;
     switch (p.mode) {
@@ -393,9 +423,21 @@ extern "C" int pnc_cfg_sampler_step(const PncSamplerStepParams* pp, void* stream
     for (int k = 0; ok && k < nv; ++k) ok = p.v[k] != nullptr;
     if (!ok) return PNC_EINVAL;
     const int64_t n = (int64_t)p.T * p.Npix;
-    hipLaunchKernelGGL(cfg_sampler_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), p);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (skip)
+        hipLaunchKernelGGL(cfg_sampler_step_kernel<true>, grid, block, 0, st, p, c_skip);
+    else
+        hipLaunchKernelGGL(cfg_sampler_step_kernel<false>, grid, block, 0, st, p, static_cast<const float*>(nullptr));
     return pnc_launch_status();
+}
+
+extern "C" int pnc_cfg_sampler_step(const PncSamplerStepParams* pp, void* stream) {
+    return cfg_sampler_step_launch(pp, nullptr, false, stream);
+}
+
+extern "C" int pnc_cfg_sampler_step_skip(const PncSamplerStepParams* pp, const float* c_skip, void* stream) {
+    return cfg_sampler_step_launch(pp, c_skip, true, stream);
 }
 
 extern "C" const char* pnc_version(void) { return "panacea_hip 0.4.0 gfx950"; }
@@ -452,7 +494,16 @@ extern "C" int pnc_timestep_embedding(const int64_t* t, int F, int dim, const fl
                                       float* out, void* stream) {
     if (!t || !out || !freqs || F < 1 || dim < 2) return PNC_EINVAL;
     const int n = F * (dim / 2);
-    hipLaunchKernelGGL(timestep_embedding_kernel, dim3((n + 255) / 256), dim3(256), 0,
+    hipLaunchKernelGGL(timestep_embedding_kernel<int64_t>, dim3((n + 255) / 256), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), t, F, dim, freqs, out);
+    return pnc_launch_status();
+}
+
+extern "C" int pnc_timestep_embedding_f32(const float* t, int F, int dim, const float* freqs,
+                                          float* out, void* stream) {
+    if (!t || !out || !freqs || F < 1 || dim < 2) return PNC_EINVAL;
+    const int n = F * (dim / 2);
+    hipLaunchKernelGGL(timestep_embedding_kernel<float>, dim3((n + 255) / 256), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), t, F, dim, freqs, out);
     return pnc_launch_status();
 }

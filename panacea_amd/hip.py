@@ -132,9 +132,12 @@ _SIGNATURES = {
     "pnc_linear_smallm": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "pnc_linear_smallm_segments": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "pnc_timestep_embedding": (_I, [_P, _I, _I, _P, _P, _P]),
+    "pnc_timestep_embedding_f32": (_I, [_P, _I, _I, _P, _P, _P]),
     "pnc_nchw_to_tokens_f16": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pnc_cfg_euler_step": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "pnc_cfg_sampler_step": (_I, [C.POINTER(SamplerStepParams), _P]),
+    "pnc_cfg_euler_step_skip": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "pnc_cfg_sampler_step_skip": (_I, [C.POINTER(SamplerStepParams), _P, _P]),
     "pnc_tokens_to_nchw_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "pnc_concat_add": (_I, [_P, _I, _P, _P, _I, _L, _P, _P, _P, _I, _P]),
     "pnc_concat_add_stats": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
@@ -508,21 +511,34 @@ def timestep_embedding(t_i64, F, dim, freqs, out32):
            "pnc_timestep_embedding")
 
 
+def timestep_embedding_f32(t_f32, F, dim, freqs, out32):
+    """pnc_timestep_embedding_f32: float timesteps (a continuous c_noise), evaluated as given"""
+    _check(load().pnc_timestep_embedding_f32(_ptr(t_f32, torch.float32, "t"), F, dim, _ptr(freqs), _ptr(out32), _stream()),
+           "pnc_timestep_embedding_f32")
+
+
 def nchw_to_tokens_f16(a32, C1, b32, C2, F, Npix, Cpad, out16, out16_lo=None, a_scale=None, a_frames=0):
     _check(_timed("layout", 0.0, F * Npix * (4.0 * (C1 + C2) + 2.0 * Cpad), load().pnc_nchw_to_tokens_f16, _ptr(a32),
                   C1, _ptr(a_scale), a_frames or F, _ptr(b32), C2, F, Npix, Cpad, _ptr(out16), _ptr(out16_lo), _stream()),
            "pnc_nchw_to_tokens_f16")
 
 
-def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next):
+def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip=None):
+    """`c_skip`: a [T] fp32 vector selects pnc_cfg_euler_step_skip (D = eps * c_out + x * c_skip); None = the eps path"""
+    if c_skip is not None:
+        _check(_timed("elementwise", 0.0, T * Npix * Cch * (16.0 if cfg else 12.0), load().pnc_cfg_euler_step_skip, _ptr(eps_tok),
+                      ld, T, Npix, Cch, int(cfg), float(scale), _ptr(x), _ptr(c_skip, torch.float32, "c_skip"), _ptr(c_out),
+                      _ptr(sigma), _ptr(sigma_next), _ptr(x_next), _stream()), "pnc_cfg_euler_step_skip")
+        return
     _check(_timed("elementwise", 0.0, T * Npix * Cch * (16.0 if cfg else 12.0), load().pnc_cfg_euler_step, _ptr(eps_tok), ld, T,
                   Npix, Cch, int(cfg), float(scale), _ptr(x), _ptr(c_out), _ptr(sigma), _ptr(sigma_next), _ptr(x_next),
                   _stream()), "pnc_cfg_euler_step")
 
 
 def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux=None, x0=None, aux=None,
-                     hist=(), noise=None, s_noise=1.0):
-    """pnc_cfg_sampler_step: `v` = the mode's per-frame [T] fp32 vectors in header order, `hist` = previous LMS d planes newest first"""
+                     hist=(), noise=None, s_noise=1.0, c_skip=None):
+    """pnc_cfg_sampler_step: `v` = the mode's per-frame [T] fp32 vectors in header order, `hist` = previous LMS d planes newest first;
+    `c_skip`: a [T] fp32 vector selects pnc_cfg_sampler_step_skip (D = eps * c_out + x * c_skip); None = the eps path"""
     p = SamplerStepParams()
     p.struct_bytes = C.sizeof(SamplerStepParams)
     f32 = torch.float32
@@ -538,8 +554,12 @@ def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, o
         p.hist[k] = _ptr(t, f32, f"hist[{k}]")
     p.n_hist, p.s_noise = len(hist), float(s_noise)
     planes = 3 + (x0 is not None) + (aux is not None) + (noise is not None) + (out_aux is not None) + len(hist)
-    _check(_timed("elementwise", 0.0, T * Npix * Cch * (4.0 * planes + (4.0 if cfg else 0.0)), load().pnc_cfg_sampler_step,
-                  C.byref(p), _stream()), "pnc_cfg_sampler_step")
+    nbytes = T * Npix * Cch * (4.0 * planes + (4.0 if cfg else 0.0))
+    if c_skip is not None:
+        _check(_timed("elementwise", 0.0, nbytes, load().pnc_cfg_sampler_step_skip, C.byref(p), _ptr(c_skip, f32, "c_skip"),
+                      _stream()), "pnc_cfg_sampler_step_skip")
+        return
+    _check(_timed("elementwise", 0.0, nbytes, load().pnc_cfg_sampler_step, C.byref(p), _stream()), "pnc_cfg_sampler_step")
 
 
 def tokens_to_nchw_f32(x32, ld, F, Npix, Cch, out32):

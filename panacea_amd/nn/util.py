@@ -16,7 +16,10 @@ def checkpoint(func, inputs, params, flag):
 
 
 def timestep_embedding(timesteps, dim, max_period=10000, repeat_only=False):
-    """util.py:224-248 — sinusoidal embedding [cos | sin] in fp32, computed on the device of `timesteps`."""
+    """util.py:224-248 — sinusoidal embedding [cos | sin] in fp32, computed on the device of `timesteps`.  Integer timesteps
+    (the table index of a quantised c_noise) take pnc_timestep_embedding; floating-point ones (the continuous Denoiser,
+    quantize_c_noise=False, EDMScaling's 0.25 log sigma) are evaluated as given, in fp32, by pnc_timestep_embedding_f32 — the
+    reference does `timesteps[:, None].float() * freqs[None]` on either."""
     if repeat_only:
         return timesteps[:, None].expand(-1, dim)
     if max_period != 10000:
@@ -24,6 +27,9 @@ def timestep_embedding(timesteps, dim, max_period=10000, repeat_only=False):
     F = timesteps.shape[0]
     be = E.backend()
     out = torch.zeros((F, dim), device=timesteps.device, dtype=torch.float32)
+    if timesteps.is_floating_point():
+        be.timestep_embedding_f32(timesteps.to(torch.float32).contiguous(), F, dim, E.timestep_freqs(dim, timesteps.device), out)
+        return out
     be.timestep_embedding(timesteps.to(torch.int64).contiguous(), F, dim, E.timestep_freqs(dim, timesteps.device), out)
     return out
 

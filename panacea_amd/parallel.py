@@ -237,6 +237,18 @@ def _refuse_wide(model):
                          "ShardedCFG)")
 
 
+def _refuse_denoiser(den):
+    """ShardedCFG pairs run the shipped parameterisation only: EpsScaling with a quantised c_noise.  A denoiser mirror with
+    VScaling / EDMScaling, or one that hands the network a float c_noise, is refused (`den` None: a plain callable, not inspected)."""
+    from . import sampling as S
+    if den is None:
+        return
+    if not isinstance(den.scaling, S.EpsScaling) or not getattr(den, "quantize_c_noise", False):
+        raise NotImplementedError(f"parallel.ShardedCFG runs EpsScaling with a quantised c_noise only (got {type(den).__name__} with "
+                                  f"{type(den.scaling).__name__}, quantize_c_noise={getattr(den, 'quantize_c_noise', False)}); "
+                                  "use VanillaCFG for the other denoiser parameterisations")
+
+
 def apply_frame_shard(network, shard: Optional[FrameShard], side_shard: Optional[FrameShard] = None):
     """Tell the network (OpenAIWrapperControlLDM3D or ControlledUNetModel3D) that its batches carry this rank's frame
     group only.  `side_shard`: the same shard over the ControlNet's own process group (`Groups.frame_shard(side=True)`): with it

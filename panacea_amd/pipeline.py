@@ -1,6 +1,6 @@
 """Latents-in, frames-out composition of the pieces this package owns (hot path + f1 + f2 + f4):
 
-    cond / uc  ->  EulerEDMSampler (or any sampler mirror) + VanillaCFG + DiscreteDenoiser around the ControlNet-UNet (step invariants hoisted)
+    cond / uc  ->  EulerEDMSampler (or any sampler mirror) + VanillaCFG + DiscreteDenoiser (or any denoiser mirror) around the ControlNet-UNet (step invariants hoisted)
                ->  z / scale_factor  ->  FirstStageDecoder  ->  frames in [-1, 1]  (-> checkpoint.save_view_frames / save_gif)
 
 which is what `DiffusionEngine3D.sample` + `decode_first_stage` do around the network (diffusion.py:138-151, 242-249;
@@ -20,14 +20,23 @@ SCALE_FACTOR = 0.18215
 
 def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
                   noise: torch.Tensor, num_steps: int = 25, cfg_scale: float = 5.0, hoist: bool = True,
-                  scale_factor: float = SCALE_FACTOR, sampler=None) -> torch.Tensor:
+                  scale_factor: float = SCALE_FACTOR, sampler=None, denoiser=None) -> torch.Tensor:
     """noise: (T, 4, h, w) unit-variance latents of ONE sample; returns (T, 3, 8h, 8w) frames.  T is taken from `noise` and has
     to be the `num_frames` the network was built with (configs.with_frames), 1 <= T <= 16: the temporal kernels hold at most 16
     frames of a pixel, and a network for a longer clip is refused when it is built.
     `sampler`: None = the YAML's 25-step Euler / CFG `cfg_scale` (num_steps, cfg_scale apply); a sampler mirror of
-    panacea_amd.sampling; or a reference `sampler_config` dict (sampling.from_config; its num_steps, else `num_steps`)."""
+    panacea_amd.sampling; or a reference `sampler_config` dict (sampling.from_config; its num_steps, else `num_steps`).
+    `denoiser`: None = the YAML's DiscreteDenoiser with EpsScaling; a denoiser mirror of panacea_amd.sampling (Denoiser or
+    DiscreteDenoiser with EpsScaling / VScaling / EDMScaling); or a reference `denoiser_config` dict
+    (sampling.denoiser_from_config)."""
     dev = noise.device
-    den = sampling.DiscreteDenoiser().to(dev)
+    if denoiser is None:
+        den = sampling.DiscreteDenoiser()
+    else:
+        den = sampling.denoiser_from_config(denoiser) if isinstance(denoiser, dict) else denoiser
+        if not isinstance(den, sampling.Denoiser):
+            raise TypeError(f"denoiser: a panacea_amd.sampling denoiser mirror or a denoiser_config dict (got {type(den).__name__})")
+    den = den.to(dev)
     if sampler is None:
         smp = sampling.EulerEDMSampler(num_steps, guider=sampling.VanillaCFG(cfg_scale), device=dev)
     else:

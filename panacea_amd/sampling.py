@@ -3,8 +3,9 @@ eps-scaling, classifier-free guidance and the Euler sampler of `configs/inferenc
 
 Host-side mirrors with the reference's names and call signatures
   LegacyDDPMDiscretization   sgm/modules/diffusionmodules/discretizer.py:42-69
-  EpsScaling                 .../denoiser_scaling.py:16-22
-  DiscreteDenoiser           .../denoiser.py:31-63
+  EDMDiscretization          .../discretizer.py:28-39
+  EpsScaling, VScaling, EDMScaling   .../denoiser_scaling.py:4-31
+  Denoiser, DiscreteDenoiser .../denoiser.py:6-63 (`denoiser_from_config` builds either from the YAML's denoiser_config)
   VanillaCFG                 .../guiders.py:8-40 (+ sampling_utils.py:7-9)
   EulerEDMSampler            .../sampling.py:27-133,214-218 (+ churn)
   HeunEDMSampler, EulerAncestralSampler, DPMPP2SAncestralSampler, DPMPP2MSampler, LinearMultistepSampler
@@ -54,6 +55,30 @@ class LegacyDDPMDiscretization:
         return s if not flip else torch.flip(s, (0,))
 
 
+class EDMDiscretization:
+    """discretizer.py:28-39 — Karras et al.'s rho-schedule: sigma_i = (smax^(1/rho) + i/(n-1) (smin^(1/rho) - smax^(1/rho)))^rho,
+    the ramp and the power in fp32 torch ops, the two roots Python floats.  The n values are computed on the HOST and moved to
+    `device`: a device's linspace and powf are not the host's to the bit, and the samplers decide their branches from the host copy
+    of the schedule (`_Sampler.host_sigmas`) — so the device holds exactly the sigmas the host reasons about, on any device.  At
+    sigma_max = 80 the initial latent is ~250, where one ulp of sigma moves a 3-step Heun trajectory by several 1e-5."""
+
+    def __init__(self, sigma_min=0.02, sigma_max=80.0, rho=7.0):
+        self.sigma_min, self.sigma_max, self.rho = sigma_min, sigma_max, rho
+
+    def get_sigmas(self, n, device="cpu"):
+        ramp = torch.linspace(0, 1, n)
+        lo, hi = self.sigma_min ** (1 / self.rho), self.sigma_max ** (1 / self.rho)
+        return ((hi + ramp * (lo - hi)) ** self.rho).to(device)
+
+    def __call__(self, n, do_append_zero=True, device="cpu", flip=False):
+        s = self.get_sigmas(n, device=device)
+        if do_append_zero:
+            s = torch.cat([s, s.new_zeros([1])])
+        return s if not flip else torch.flip(s, (0,))
+
+
+# The scalings return (c_skip, c_out, c_in, c_noise).  Each coefficient is the reference's torch expression with its operations in
+# the reference's order: a fused step computes its [T] vectors with these very calls, so they are the plain step's bits.
 class EpsScaling:
     """denoiser_scaling.py:16-22"""
 
@@ -61,14 +86,62 @@ class EpsScaling:
         return torch.ones_like(sigma), -sigma, 1 / (sigma ** 2 + 1.0) ** 0.5, sigma.clone()
 
 
-class DiscreteDenoiser(nn.Module):
-    """denoiser.py:31-63 with EpsScaling: snaps sigma to the 1000-entry table and hands the network its INDEX."""
+class VScaling:
+    """denoiser_scaling.py:25-31 — v-prediction: c_skip = 1 / (sigma^2 + 1), c_out = -sigma / sqrt(sigma^2 + 1)"""
 
-    def __init__(self, num_idx=1000, discretization=None, do_append_zero=False, quantize_c_noise=True, flip=True):
+    def __call__(self, sigma):
+        return 1.0 / (sigma ** 2 + 1.0), -sigma / (sigma ** 2 + 1.0) ** 0.5, 1.0 / (sigma ** 2 + 1.0) ** 0.5, sigma.clone()
+
+
+class EDMScaling:
+    """denoiser_scaling.py:4-13 — Karras et al.'s preconditioning; c_noise = log(sigma) / 4 is a float"""
+
+    def __init__(self, sigma_data=0.5):
+        self.sigma_data = sigma_data
+
+    def __call__(self, sigma):
+        sd = self.sigma_data
+        return (sd ** 2 / (sigma ** 2 + sd ** 2), sigma * sd / (sigma ** 2 + sd ** 2) ** 0.5, 1 / (sigma ** 2 + sd ** 2) ** 0.5,
+                0.25 * sigma.log())
+
+
+class Denoiser(nn.Module):
+    """denoiser.py:6-28 — the continuous denoiser: sigma is used as it comes, and the network is handed the scaling's c_noise as
+    a FLOAT (nn.util.timestep_embedding evaluates it in fp32)."""
+
+    def __init__(self, scaling=None):
         super().__init__()
+        self.scaling = scaling or EpsScaling()
+
+    def possibly_quantize_sigma(self, sigma):
+        return sigma
+
+    def possibly_quantize_c_noise(self, c_noise):
+        return c_noise
+
+    def coefficients(self, sigma):
+        """(c_skip, c_out, c_in, c_noise) for a [T] sigma, as __call__ forms them (the fused step's per-frame vectors)"""
+        c_skip, c_out, c_in, c_noise = self.scaling(self.possibly_quantize_sigma(sigma))
+        return c_skip, c_out, c_in, self.possibly_quantize_c_noise(c_noise)
+
+    def __call__(self, network: Callable, input: torch.Tensor, sigma: torch.Tensor, cond: Dict) -> torch.Tensor:
+        sigma = self.possibly_quantize_sigma(sigma)
+        shape = sigma.shape
+        sigma = append_dims(sigma, input.ndim)
+        c_skip, c_out, c_in, c_noise = self.scaling(sigma)
+        c_noise = self.possibly_quantize_c_noise(c_noise.reshape(shape))
+        return network(input * c_in, c_noise, cond) * c_out + input * c_skip
+
+
+class DiscreteDenoiser(Denoiser):
+    """denoiser.py:31-63: snaps sigma to the `num_idx`-entry table of the discretization; with quantize_c_noise (the default) the
+    network is handed the table INDEX of c_noise, else the float c_noise of the snapped sigma.  `scaling`: EpsScaling (default),
+    VScaling or EDMScaling."""
+
+    def __init__(self, num_idx=1000, discretization=None, do_append_zero=False, quantize_c_noise=True, flip=True, scaling=None):
+        super().__init__(scaling)
         disc = discretization or LegacyDDPMDiscretization()
         self.register_buffer("sigmas", disc(num_idx, do_append_zero=do_append_zero, flip=flip))
-        self.scaling = EpsScaling()
         self.quantize_c_noise = quantize_c_noise
 
     def sigma_to_idx(self, sigma):
@@ -77,15 +150,11 @@ class DiscreteDenoiser(nn.Module):
     def idx_to_sigma(self, idx):
         return self.sigmas[idx]
 
-    def __call__(self, network: Callable, input: torch.Tensor, sigma: torch.Tensor, cond: Dict) -> torch.Tensor:
-        sigma = self.idx_to_sigma(self.sigma_to_idx(sigma))
-        shape = sigma.shape
-        sigma = append_dims(sigma, input.ndim)
-        c_skip, c_out, c_in, c_noise = self.scaling(sigma)
-        c_noise = c_noise.reshape(shape)
-        if self.quantize_c_noise:
-            c_noise = self.sigma_to_idx(c_noise)
-        return network(input * c_in, c_noise, cond) * c_out + input * c_skip
+    def possibly_quantize_sigma(self, sigma):
+        return self.idx_to_sigma(self.sigma_to_idx(sigma))
+
+    def possibly_quantize_c_noise(self, c_noise):
+        return self.sigma_to_idx(c_noise) if self.quantize_c_noise else c_noise
 
 
 class VanillaCFG:
@@ -125,7 +194,7 @@ class BoundDenoiser:
     c_in scaling and the CFG batch doubling folded into the network's entry kernel, c_out / c_skip + CFG combine + Euler
     update in ONE exit kernel on the network's channels-last output.  Calling it is exactly the lambda."""
 
-    def __init__(self, denoiser: "DiscreteDenoiser", network):
+    def __init__(self, denoiser: "Denoiser", network):
         self.denoiser, self.network = denoiser, network
 
     def __call__(self, x, sigma, cond):
@@ -153,10 +222,14 @@ class _Sampler:
 
     def _check_cfg_half(self, denoiser):
         """parallel.ShardedCFG evaluates one CFG half per rank: each rank would escalate on its own half's count, so the pair could end
-        up on two policies.  The sharded guider refuses 'precise-wide' and 'escalate' wherever it meets the network."""
+        up on two policies.  The sharded guider refuses 'precise-wide' and 'escalate' wherever it meets the network, and any
+        denoiser but EpsScaling with a quantised c_noise."""
+        if getattr(self.guider, "half", None) is None:
+            return
+        from .parallel import _refuse_denoiser, _refuse_wide
+        _refuse_denoiser(getattr(denoiser, "denoiser", None))
         net = getattr(denoiser, "network", None)
-        if net is not None and getattr(self.guider, "half", None) is not None:
-            from .parallel import _refuse_wide
+        if net is not None:
             _refuse_wide(getattr(net, "diffusion_model", net))
 
     def denoise(self, x, denoiser, sigma, cond, uc):
@@ -177,19 +250,22 @@ class _Sampler:
         # band the rank holds; a CFG pair (parallel.ShardedCFG: `half`, `group`) all-gathers its eps halves in front of the
         # exit kernel instead of the denoised halves behind it
         guider_ok = type(self.guider) in (VanillaCFG, type(None)) or (isinstance(self.guider, VanillaCFG) and hasattr(self.guider, "half"))
-        return (hasattr(model, "denoise_tokens") and guider_ok and isinstance(den, DiscreteDenoiser)
-                and isinstance(den.scaling, EpsScaling) and den.quantize_c_noise
+        # any denoiser mirror with any scaling mirror, quantised or float c_noise: the exit kernels take c_skip as a [T] vector
+        # (pnc_cfg_*_step_skip) and the network embeds a float timestep as given
+        return (hasattr(model, "denoise_tokens") and guider_ok and isinstance(den, Denoiser)
+                and type(den.scaling) in (EpsScaling, VScaling, EDMScaling)
                 and "concat" in cond and cond.get("vector") is None)
 
     def _fused_eps(self, sigma, denoiser, x, cond, uc) -> "_Eps":
-        """The network half of a fused step: three tiny torch ops (table snap of T sigmas) + the network with c_in and the CFG
-        batch doubling in its entry kernel.  Returns the channels-last fp32 eps tokens with what an exit kernel needs."""
+        """The network half of a fused step: a few tiny torch ops on T sigmas (the denoiser's own snap and scaling) + the network
+        with c_in and the CFG batch doubling in its entry kernel.  Returns the channels-last fp32 eps tokens with what an exit
+        kernel needs."""
         den, model = denoiser.denoiser, denoiser.network.diffusion_model
         T = x.shape[0]
-        idx = den.sigma_to_idx(sigma)
-        sig_q = den.idx_to_sigma(idx)                                 # denoiser.py:24
-        c_in = 1 / (sig_q ** 2 + 1.0) ** 0.5
-        c_noise = den.sigma_to_idx(sig_q)                             # quantised c_noise = the table index
+        # denoiser.py:23-27 on the [T] vector: sigma snapped where the denoiser snaps, the scaling's four coefficients, c_noise the
+        # table index (int64) or the float the scaling gives
+        c_skip, c_out, c_in, c_noise = den.coefficients(sigma)
+        c_skip = None if isinstance(den.scaling, EpsScaling) else c_skip.contiguous()     # eps: c_skip = 1, the kernels without it
         half = getattr(self.guider, "half", None)
         self._check_cfg_half(denoiser)
         if self.guider is None:
@@ -222,23 +298,29 @@ class _Sampler:
             both = torch.empty((2 * send.shape[0], send.shape[1]), dtype=send.dtype, device=send.device)   # [uncond half; cond half]
             dist.all_gather_into_tensor(both, send, group=self.guider.group)
             eps32, cfg = both.to(mine.device), True
-        return _Eps(eps32, eps.C, T, eps.N, x.shape[1], cfg, float(self.guider.scale) if cfg else 0.0, x32, (-sig_q).contiguous())
+        return _Eps(eps32, eps.C, T, eps.N, x.shape[1], cfg, float(self.guider.scale) if cfg else 0.0, x32, c_out.contiguous(), c_skip)
 
 
 class _Eps:
     """eps tokens of one network evaluation: tok [(cfg ? 2 : 1) * T * Npix][ld] fp32, x = the fp32 NCHW latent the network saw,
-    c_out = -sigma snapped to the table"""
-    __slots__ = ("tok", "ld", "T", "Npix", "C", "cfg", "scale", "x", "c_out")
+    c_out [T] = the scaling's c_out of the (snapped) sigma (EpsScaling: -sigma), c_skip [T] = its c_skip, or None for EpsScaling
+    (c_skip = 1: the exit kernels without a skip vector)"""
+    __slots__ = ("tok", "ld", "T", "Npix", "C", "cfg", "scale", "x", "c_out", "c_skip")
 
-    def __init__(self, tok, ld, T, Npix, C, cfg, scale, x, c_out):
+    def __init__(self, tok, ld, T, Npix, C, cfg, scale, x, c_out, c_skip=None):
         self.tok, self.ld, self.T, self.Npix, self.C, self.cfg, self.scale, self.x, self.c_out = tok, ld, T, Npix, C, cfg, scale, x, c_out
+        self.c_skip = c_skip
+
+    def skip_kw(self) -> Dict:
+        """`c_skip=` for the backend's exit kernels, passed exactly when the scaling is not EpsScaling"""
+        return {} if self.c_skip is None else {"c_skip": self.c_skip}
 
     def step(self, mode, v, out_aux=None, **kw) -> torch.Tensor:
         """pnc_cfg_sampler_step on these tokens; returns `out` (a new fp32 latent)"""
         from . import engine as E
         out = torch.empty_like(self.x)
         E.backend().cfg_sampler_step(mode, self.tok, self.ld, self.T, self.Npix, self.C, self.cfg, self.scale, self.x, self.c_out,
-                                     [t.contiguous() for t in v], out, out_aux=out_aux, **kw)
+                                     [t.contiguous() for t in v], out, out_aux=out_aux, **kw, **self.skip_kw())
         return out
 
 
@@ -276,7 +358,7 @@ class EulerEDMSampler(_EDM):
         e = self._fused_eps(sigma, denoiser, x, cond, uc)
         out = torch.empty_like(e.x)
         E.backend().cfg_euler_step(e.tok, e.ld, e.T, e.Npix, e.C, e.cfg, e.scale, e.x, e.c_out, sigma.contiguous(),
-                                   next_sigma.contiguous(), out)
+                                   next_sigma.contiguous(), out, **e.skip_kw())
         return out.to(x.dtype)
 
     def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0):
@@ -705,9 +787,52 @@ SAMPLERS = {"EulerEDMSampler": EulerEDMSampler, "HeunEDMSampler": HeunEDMSampler
 _REF_SAMPLING = "sgm.modules.diffusionmodules.sampling."
 
 
+DISCRETIZATIONS = {"LegacyDDPMDiscretization": LegacyDDPMDiscretization, "EDMDiscretization": EDMDiscretization}
+SCALINGS = {"EpsScaling": EpsScaling, "VScaling": VScaling, "EDMScaling": EDMScaling}
+_REF = "sgm.modules.diffusionmodules."
+
+
+def _mirror_of(cfg: Optional[Dict], module: str, table: Dict, default: str, what: str):
+    """the mirror class a reference `{target, params}` block names, with its params"""
+    cfg = cfg or {"target": _REF + module + "." + default}
+    target = str(cfg.get("target", ""))
+    prefix = _REF + module + "."
+    name = target[len(prefix):] if target.startswith(prefix) else None
+    if name not in table:
+        raise NotImplementedError(f"{what} {target!r} has no mirror in panacea_amd.sampling "
+                                  f"(supported: {', '.join(prefix + n for n in table)})")
+    return table[name], dict(cfg.get("params") or {})
+
+
+def _discretization_from_config(disc_cfg: Optional[Dict]):
+    cls, kw = _mirror_of(disc_cfg, "discretizer", DISCRETIZATIONS, "LegacyDDPMDiscretization", "discretization")
+    return cls(**kw)
+
+
+def denoiser_from_config(denoiser_config: Optional[Dict]) -> Denoiser:
+    """The mirror of the reference's YAML `denoiser_config` (configs/inference_nuscenes.yaml:12-22): `target` Denoiser or
+    DiscreteDenoiser of sgm.modules.diffusionmodules.denoiser, `params` with scaling_config (EpsScaling / VScaling / EDMScaling)
+    and, for the discrete one, num_idx, discretization_config, do_append_zero, quantize_c_noise, flip.  `weighting_config` is the
+    training loss weight: accepted and ignored.  None = the shipped YAML's DiscreteDenoiser()."""
+    if denoiser_config is None:
+        return DiscreteDenoiser()
+    cls, params = _mirror_of(denoiser_config, "denoiser", {"Denoiser": Denoiser, "DiscreteDenoiser": DiscreteDenoiser},
+                             "DiscreteDenoiser", "denoiser")
+    params.pop("weighting_config", None)
+    s_cls, s_kw = _mirror_of(params.pop("scaling_config", None), "denoiser_scaling", SCALINGS, "EpsScaling", "scaling")
+    scaling = s_cls(**s_kw)
+    if cls is Denoiser:
+        if params:
+            raise TypeError(f"Denoiser takes weighting_config and scaling_config only (got {sorted(params)})")
+        return Denoiser(scaling)
+    disc = _discretization_from_config(params.pop("discretization_config", None))
+    return DiscreteDenoiser(discretization=disc, scaling=scaling, **params)
+
+
 def from_config(sampler_config: Dict, device="cuda") -> _Sampler:
     """The mirror of the reference's YAML `sampler_config` (configs/inference_nuscenes.yaml:115-126): `target` one of the six
-    samplers of sgm.modules.diffusionmodules.sampling, `params` with num_steps, discretization_config (LegacyDDPMDiscretization),
+    samplers of sgm.modules.diffusionmodules.sampling, `params` with num_steps, discretization_config (LegacyDDPMDiscretization
+    or EDMDiscretization),
     guider_config (VanillaCFG or IdentityGuider) and the sampler's own kwargs (s_churn, eta, s_noise, order, ...)."""
     target = sampler_config.get("target", "")
     name = target[len(_REF_SAMPLING):] if target.startswith(_REF_SAMPLING) else None
@@ -716,10 +841,7 @@ def from_config(sampler_config: Dict, device="cuda") -> _Sampler:
                                   f"(supported: {', '.join(_REF_SAMPLING + n for n in SAMPLERS)})")
     params = dict(sampler_config.get("params") or {})
     params.pop("verbose", None)
-    disc_cfg = params.pop("discretization_config", None) or {"target": "sgm.modules.diffusionmodules.discretizer.LegacyDDPMDiscretization"}
-    if not str(disc_cfg.get("target", "")).endswith("LegacyDDPMDiscretization"):
-        raise NotImplementedError(f"discretization {disc_cfg.get('target')!r} has no mirror (LegacyDDPMDiscretization only)")
-    disc = LegacyDDPMDiscretization(**dict(disc_cfg.get("params") or {}))
+    disc = _discretization_from_config(params.pop("discretization_config", None))
     g_cfg = params.pop("guider_config", None)
     g_target = str((g_cfg or {}).get("target", "IdentityGuider"))
     if g_target.endswith("VanillaCFG"):

@@ -6,6 +6,8 @@ per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference'
 
     python tools/sample.py --steps 5 --out gpurun_out/sample
     python tools/sample.py --sampler dpmpp2m --steps 15
+    python tools/sample.py --prediction v --steps 5       (a v-prediction checkpoint; `edm` = EDMScaling + the continuous Denoiser)
+    python tools/sample.py --prediction edm --discretization edm --sampler heun --steps 18
     python tools/sample.py --frames 16 --steps 5          (clips of 1 .. 16 frames; the default 8 is the released FrameLength)
 """
 import argparse, json, sys, time
@@ -20,6 +22,19 @@ VAE = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3,
            num_res_blocks=2, attn_resolutions=[], dropout=0.0)
 SAMPLERS = {"euler": "EulerEDMSampler", "heun": "HeunEDMSampler", "euler_a": "EulerAncestralSampler",
             "dpmpp2s_a": "DPMPP2SAncestralSampler", "dpmpp2m": "DPMPP2MSampler", "lms": "LinearMultistepSampler"}
+P = "sgm.modules.diffusionmodules."
+DISCRETIZATIONS = {"ddpm": "LegacyDDPMDiscretization", "edm": "EDMDiscretization"}
+
+
+def denoiser_config(prediction: str) -> dict:
+    """the reference-style denoiser_config of a parameterisation: eps / v = DiscreteDenoiser on the DDPM table with EpsScaling /
+    VScaling (what an SD eps or v checkpoint was trained under), edm = the continuous Denoiser with EDMScaling"""
+    if prediction == "edm":
+        return {"target": P + "denoiser.Denoiser", "params": {"scaling_config": {"target": P + "denoiser_scaling.EDMScaling"}}}
+    scaling = {"eps": "EpsScaling", "v": "VScaling"}[prediction]
+    return {"target": P + "denoiser.DiscreteDenoiser",
+            "params": {"num_idx": 1000, "scaling_config": {"target": P + "denoiser_scaling." + scaling},
+                       "discretization_config": {"target": P + "discretizer.LegacyDDPMDiscretization"}}}
 
 
 def main():
@@ -30,6 +45,8 @@ def main():
     ap.add_argument("--seed", type=int, default=3407)
     ap.add_argument("--sampler", choices=sorted(SAMPLERS), default="euler")
     ap.add_argument("--cfg-scale", type=float, default=5.0)
+    ap.add_argument("--prediction", choices=["eps", "v", "edm"], default="eps", help="denoiser parameterisation")
+    ap.add_argument("--discretization", choices=sorted(DISCRETIZATIONS), default="ddpm", help="the sampler's sigma schedule")
     ap.add_argument("--frames", type=int, default=8, choices=range(1, 17), metavar="1..16", help="frames per clip (num_frames)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -52,13 +69,15 @@ def main():
     uc = {"crossattn": g["crossattn"][0:1], "concat": g["concat"][:T], "cond_feat": g["cond_feat"][:T]}
     noise = torch.randn(T, 4, h, w, generator=torch.Generator().manual_seed(a.seed)).to(dev)
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    smp = sampling.from_config({"target": "sgm.modules.diffusionmodules.sampling." + SAMPLERS[a.sampler],
-                                "params": {"num_steps": a.steps, "guider_config": {
-                                    "target": "sgm.modules.diffusionmodules.guiders.VanillaCFG", "params": {"scale": a.cfg_scale}}}},
+    smp = sampling.from_config({"target": P + "sampling." + SAMPLERS[a.sampler],
+                                "params": {"num_steps": a.steps,
+                                           "discretization_config": {"target": P + "discretizer." + DISCRETIZATIONS[a.discretization]},
+                                           "guider_config": {"target": P + "guiders.VanillaCFG", "params": {"scale": a.cfg_scale}}}},
                                device=dev)
-    frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp)
+    frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
+                                    denoiser=denoiser_config(a.prediction))
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print(f"{a.sampler}: {a.steps} steps + decode of {T} frames {tuple(frames.shape)}: {dt:.2f} s "
+    print(f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.steps} steps + decode of {T} frames {tuple(frames.shape)}: {dt:.2f} s "
           f"(range {frames.min().item():.2f} .. {frames.max().item():.2f}, finite={bool(torch.isfinite(frames).all())})")
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
     checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=frames.shape[-1] // 6)
