@@ -37,7 +37,10 @@ const char* pnc_version(void);
  * (round 4: + pnc_groupnorm_combine, + PNC_OPT_ATTN_DEFER_MAX, PNC_OPT_GEMM_PERSIST is a bit set, - pnc_ff_chain_*;
  *  round 5 (5, 6): + pnc_concat_add_stats, + PNC_OPT_GEMM_STAGGER, + pnc_linear_smallm_segments;
  *  round 6 (7): + PNC_OPT_ATTN_SUM_TRIGGER;
- *  8: + pnc_cfg_sampler_step / PncSamplerStepParams) */
+ *  8: + pnc_cfg_sampler_step / PncSamplerStepParams;
+ *  still 8 (additive, no struct / prototype / option changes): PncGemmParams.W_lo next to an fp16 A_lo is the fp16 lo plane of the
+ *  weights, + pnc_linear_smallm_split / pnc_linear_smallm_segments_split.  One check is stricter for existing callers: a non-NULL
+ *  PncGemmParams.W_lo with A_lo = NULL, which pnc_gemm_f16 used to ignore, is now PNC_EINVAL — clear the field with A_lo) */
 #define PNC_ABI_VERSION 8
 int pnc_abi_version(void);
 /* hex SHA-256 of the sources + compile flags the library was built from (panacea_amd/build.py computes the same digest over
@@ -211,7 +214,19 @@ typedef struct PncGemmParams {
      * and 16-byte chunks of 16 consecutive k: PNC_A_PLAIN lda % 16 == 0 and K % 16 == 0; the conv gathers Cin % 64 == 0. */
     int32_t a_lo_fmt;
     int32_t out_lo_fmt;
-    int32_t ldw_lo;             /* bytes between rows of W_lo (0 = K) */
+    /* SPLIT WEIGHTS (a_lo_fmt = PNC_LO_F16, A_lo != NULL): a non-NULL W_lo is the fp16 lo plane of the weights,
+     *   the weights w = W_hi + 2^-11 * W_lo,  W_hi = W = fp16(w),  W_lo[n][k] = fp16((w - fp16(w)) * 2^11),
+     * in W's layout, K order and leading dimension, 16-byte aligned; w_lo_exp is ignored.  The lo pass then runs a second set of K
+     * tiles, A's hi plane against W_lo, into the same accumulators ahead of the one 2^-11 scaling:
+     *   A w ~= A_hi W_hi + 2^-11 (A_lo W_hi + A_hi W_lo)      (the 2^-22 A_lo W_lo term is dropped; valid for |w| < 65504)
+     * — three times the MFMA work of the plain launch.  A misaligned W_lo is PNC_EALIGN.  A non-NULL W_lo without A_lo is
+     * PNC_EINVAL whatever a_lo_fmt says (before split weights such a pointer was ignored: callers that reuse a struct clear it).
+     * Next to an e4m3 A_lo, W_lo is the e4m3 plane described above in every kernel; the 3x3 halo-tile kernel has no e4m3 pass and is
+     * not selected for such a launch (the per-tap kernel runs it).
+     * ldw_lo has the unit of the plane it strides.  e4m3 W_lo: BYTES between its rows, 0 = K.  fp16 W_lo: ELEMENTS between its
+     * rows, and since the plane has W's leading dimension the only accepted values are 0 and ldw (K when ldw = 0); anything else
+     * is PNC_EINVAL. */
+    int32_t ldw_lo;
     const void* W_lo;
     int32_t w_lo_exp;
     /* PNC_A_CONV1D_T: 1 = A (and A_lo) hold T + 2 frames per sample, row (b, t, pixel) at ((b (T + 2) + t + 1) Npix + pixel): the
@@ -370,6 +385,10 @@ int pnc_layernorm(const float* x, int ldx, int M, int C,
 int pnc_linear_smallm(const float* a, int lda, const void* W, const float* bias,
                       float* out, int ldo, int M, int N, int K, int silu_in, int silu_out,
                       void* stream);
+/* pnc_linear_smallm with SPLIT WEIGHTS: W_lo (fp16 [N][K], or NULL = pnc_linear_smallm bit for bit) is the lo plane of W as in
+ * PncGemmParams.W_lo; the kernel joins w = W + 2^-11 W_lo in fp32 before the products (the activations are fp32 here) */
+int pnc_linear_smallm_split(const float* a, int lda, const void* W, const void* W_lo, const float* bias,
+                            float* out, int ldo, int M, int N, int K, int silu_in, int silu_out, void* stream);
 /* The same linear for nseg sites in ONE launch (ABI 6): W [N][K] holds the sites' weight rows back to back, seg_start[0 .. nseg]
  * (HOST array, ascending, seg_start[0] = 0, seg_start[nseg] = N, every entry % 4 == 0, nseg <= PNC_SMALLM_MAX_SEGS) names each
  * site's column range, and the output is one contiguous [Mtot][width_s] block per site, blocks back to back:
@@ -380,6 +399,10 @@ int pnc_linear_smallm(const float* a, int lda, const void* W, const float* bias,
 int pnc_linear_smallm_segments(const float* a, int lda, const void* W, const float* bias, float* out, int M,
                                int m0, int Mtot, int N, int K, const int32_t* seg_start, int nseg, int silu_in,
                                int silu_out, void* stream);
+/* ... and with split weights (W_lo as in pnc_linear_smallm_split; NULL = pnc_linear_smallm_segments bit for bit) */
+int pnc_linear_smallm_segments_split(const float* a, int lda, const void* W, const void* W_lo, const float* bias, float* out,
+                                     int M, int m0, int Mtot, int N, int K, const int32_t* seg_start, int nseg, int silu_in,
+                                     int silu_out, void* stream);
 /* sinusoidal timestep embedding out[f] = [cos(t*freqs) | sin(t*freqs)], fp32; freqs[dim/2] is
  * tabulated by the caller  (diffusionmodules/util.py:224-248) */
 int pnc_timestep_embedding(const int64_t* t, int F, int dim, const float* freqs,

@@ -199,6 +199,13 @@ static int validate(const PncGemmParams& p) {
         if (p.K % 16 || (p.ldw_lo != 0 && (p.ldw_lo < p.K || p.ldw_lo % 16))) return PNC_EALIGN;
         if (p.a_mode == PNC_A_PLAIN ? (p.lda % 16 != 0) : (p.Cin % 64 != 0)) return PNC_EALIGN;
     }
+    if (p.W_lo && !(p.A_lo && p.a_lo_fmt == PNC_LO_E4M3)) {
+        // split weights: the fp16 lo plane of W (W's layout and leading dimension; w_lo_exp is ignored).  Its products join the lo
+        // pass of an fp16 A_lo, so a W_lo without one is inconsistent
+        if (!p.A_lo) return PNC_EINVAL;
+        if ((uintptr_t)p.W_lo & 15) return PNC_EALIGN;
+        if (p.ldw_lo != 0 && p.ldw_lo != (p.ldw ? p.ldw : p.K)) return PNC_EINVAL;
+    }
     if (!p.out32 && !p.out16 && !p.out16t) return PNC_EINVAL;
     if (p.ln_out16) {           // fused / trailing LayerNorm of the fp32 output rows (same limits as pnc_layernorm)
         if (!p.out32 || p.geglu || p.out16t || !p.ln_gamma || !p.ln_beta) return PNC_EINVAL;

@@ -25,6 +25,9 @@
 // "Precise" operands (A_lo != NULL): A = A_hi + 2^-11 * A_lo with both planes fp16.  The K loop first runs over the lo
 // plane, scales the accumulators by 2^-11 (exact), then runs over the hi plane: a 22-bit activation operand at twice
 // the MFMA work, same tile machinery.
+// Split WEIGHTS on top (W_lo != NULL next to an fp16 A_lo): W = W_hi + 2^-11 * W_lo, both planes fp16 in W's layout.  The lo pass
+// gets a second run of K tiles, (A_hi, W_lo), into the same accumulators ahead of the one 2^-11 scaling:
+// A W ~= A_hi W_hi + 2^-11 (A_lo W_hi + A_hi W_lo); the 2^-22 A_lo W_lo term is dropped.  Three times the MFMA work.
 #pragma once
 #include "common.h"
 #include <atomic>
@@ -849,7 +852,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_glds_kernel(const PncGemm
     const bool lo8 = A_lo && p.a_lo_fmt == PNC_LO_E4M3;
     const int nlo_all = lo8 ? (p.K + BK8 - 1) / BK8 : ntiles_all;
     const int kt_begin_lo = (int)((int64_t)kslice * nlo_all / ksplit);
-    const int nt_lo = A_lo ? (int)((int64_t)(kslice + 1) * nlo_all / ksplit) - kt_begin_lo : 0;
+    const int nt_alo = A_lo ? (int)((int64_t)(kslice + 1) * nlo_all / ksplit) - kt_begin_lo : 0;
+    // split weights (fp16 W_lo next to an fp16 A_lo): the lo pass runs the slice's K tiles a second time, A's hi plane against W_lo,
+    // before the scaling — a slice of a split-K launch runs its own K range in all three parts
+    const bool wl16 = A_lo && !lo8 && p.W_lo != nullptr;
+    const int nt_lo = wl16 ? 2 * nt_alo : nt_alo;
     const int ntot = ntiles + nt_lo;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -876,9 +883,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_glds_kernel(const PncGemm
     const buffer_rsrc_t rs_a = make_rsrc(A + a_origin, 0x7FFFFF00u);
     const buffer_rsrc_t rs_alo = make_rsrc(lo8 ? static_cast<const void*>(reinterpret_cast<const char*>(p.A_lo) + a_origin)
                                                : static_cast<const void*>((A_lo ? A_lo : A) + a_origin), 0x7FFFFF00u);
-    const buffer_rsrc_t rs_w = make_rsrc(Wt + (int64_t)n0 * p.ldw, 0x7FFFFF00u);
+    const buffer_rsrc_t rs_whi = make_rsrc(Wt + (int64_t)n0 * p.ldw, 0x7FFFFF00u);
     const buffer_rsrc_t rs_wlo = make_rsrc(lo8 ? static_cast<const void*>(reinterpret_cast<const char*>(p.W_lo) + (int64_t)n0 * p.ldw_lo)
-                                               : static_cast<const void*>(Wt + (int64_t)n0 * p.ldw), 0x7FFFFF00u);
+                                               : static_cast<const void*>((wl16 ? reinterpret_cast<const half_t*>(p.W_lo) : Wt) + (int64_t)n0 * p.ldw),
+                                           0x7FFFFF00u);
     unsigned woff[B_IT], aoff[A_IT];
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
@@ -922,8 +930,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_glds_kernel(const PncGemm
             }
             return;
         }
-        const int kt = (lo ? kt_begin_lo : kt_begin - nt_lo) + kt_local;
-        const buffer_rsrc_t rs = lo ? rs_alo : rs_a;
+        const bool wl = lo && kt_local >= nt_alo;        // (uniform) second part of an fp16 lo pass: (A hi plane, W lo plane)
+        const int kt = (lo ? kt_begin_lo - (wl ? nt_alo : 0) : kt_begin - nt_lo) + kt_local;
+        // (one flat select per resource on a precomputed flag: with a short-circuit condition or a nested select here hipcc kept the
+        // closure, and with it the parameter block, in scratch memory — 624 B per lane in every variant)
+        const bool alo = lo & !wl;
+        const buffer_rsrc_t rs = alo ? rs_alo : rs_a;
+        const buffer_rsrc_t rs_w = wl ? rs_wlo : rs_whi;
         const int kc = kt * BK + schunk * 8;
         const unsigned ks = (unsigned)kt * (BK * 2);     // the K tile as the scalar byte offset of plain rows
         if (kt != kt_tail) {                             // (uniform) no per-lane predicate on the K index
@@ -1185,7 +1198,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_glds_kernel(const PncGemm
 #pragma unroll
                         for (int q = QA; q < QB; ++q) {
                             if (q < A_IT) glds16_buf(rs_a, aoff[q < A_IT ? q : 0], ks, sa + q * (RPI * 128));
-                            else glds16_buf(rs_w, woff[q >= A_IT ? q - A_IT : 0], ks, sb + (q - A_IT) * (RPI * 128));
+                            else glds16_buf(rs_whi, woff[q >= A_IT ? q - A_IT : 0], ks, sb + (q - A_IT) * (RPI * 128));
                         }
                     }
                     if (ph == 3) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

@@ -18,7 +18,8 @@
 // (whole 64-channel W stages would need 2 x 41.5 + 2 x 40 = 163 KB).  Counted vmcnt waits + one raw s_barrier per half
 // tile, placed in the middle of its MFMA stream (software pipeline below): two half tiles in flight, one landed.
 // The K order (slice, tap, channel) is the per-tap kernel's, so are the products: results are bit-identical to its
-// (precise operands included: the lo plane's pass runs first, the accumulators are scaled by 2^-11, then the hi plane's).
+// (precise operands included: the lo plane's pass runs first, the accumulators are scaled by 2^-11, then the hi plane's; with split
+// weights — PncGemmParams.W_lo — the lo pass is two runs of the slices, (A lo, W) then (A hi, W lo), ahead of the one scaling).
 // The epilogue is gemm_kernel.h's epi_fast with a row map (RowHalo): tile-local row -> pixel of the frame.
 #include "gemm_kernel.h"
 
@@ -99,6 +100,9 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
     const buffer_rsrc_t rs_a = make_rsrc(A + img_base, frame_bytes);
     const buffer_rsrc_t rs_lo = make_rsrc((A_lo ? A_lo : A) + img_base, frame_bytes);
     const buffer_rsrc_t rs_w = make_rsrc(Wt + (int64_t)n0 * p.ldw, 0x7FFFFF00u);
+    // split weights: W's lo plane (W's layout and leading dimension), read by the second run of the lo pass
+    const bool wl16 = A_lo && p.W_lo != nullptr;
+    const buffer_rsrc_t rs_wlo = make_rsrc((wl16 ? reinterpret_cast<const half_t*>(p.W_lo) : Wt) + (int64_t)n0 * p.ldw, 0x7FFFFF00u);
 
     // ---- halo DMA: piece b = halo rows 8b .. 8b+7; lane l fills slot (l&7) of row 8b + (l>>3) with the source chunk
     // slot ^ ((hx>>1)&7), hx = the row's halo COLUMN.  The 16 lanes of a ds_read_b128 group read 16 consecutive pixels of
@@ -129,11 +133,12 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
         const int c4 = (slot & 3) ^ ((R >> 1) & 3);
         woff[i] = (n0 + nl < p.N) ? (unsigned)(nl * p.ldw + c4 * 8) * 2u : PNC_BUF_OOB;
     }
-    auto issue_w = [&](int k, int stage) {
+    auto issue_w = [&](int k, int stage, bool wlo = false) {      // wlo (uniform): the half tile of W's lo plane
         char* sb = wring + stage * WHB + wave * 1024;
+        const buffer_rsrc_t rs = wlo ? rs_wlo : rs_w;
 #pragma unroll
         for (int i = 0; i < W_IT; ++i)
-            if (wave + NW * i < WBLK) glds16_buf(rs_w, woff[i], (unsigned)k << 6, sb + i * (NW * 1024));
+            if (wave + NW * i < WBLK) glds16_buf(rs, woff[i], (unsigned)k << 6, sb + i * (NW * 1024));
     };
 
     f32x16 acc[MI][NI];
@@ -205,11 +210,15 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_IT - 1) : "memory");
     };
 
-    // Slices in execution order: with a precise operand the lo plane's nslices first, then the hi plane's
+    // Slices in execution order: with a precise operand the lo plane's nslices first, then the hi plane's; with split weights the
+    // hi plane's slices run twice — against W's lo plane (still part of the lo pass), then against W
     const int nslices = p.Cin >> 6, nq1 = nslices * IPS;              // half tiles of one pass
-    const int ns_tot = A_lo ? 2 * nslices : nslices, nq = ns_tot * IPS;
+    const int npass = A_lo ? (wl16 ? 3 : 2) : 1;
+    const int ns_tot = npass * nslices, nq = ns_tot * IPS;
+    const int nq_lo = (npass - 1) * nq1;                              // half tiles of the lo pass: the accumulators are scaled after them
     auto slice_plane = [&](int gs) { return A_lo && gs < nslices; };      // true: the lo plane
-    auto slice_cc = [&](int gs) { return gs >= nslices ? gs - nslices : gs; };
+    auto slice_cc = [&](int gs) { return gs >= 2 * nslices ? gs - 2 * nslices : (gs >= nslices ? gs - nslices : gs); };
+    int wpass = 0;                                                    // pass of the W half tile the loops issue next (1 = W's lo plane when wl16)
 
     // STAGGERED schedule (round 5, PNC_OPT_GEMM_STAGGER; gemm_kernel.h has the story): one PHASE per k-step —
     //     fragment reads of the k-step [+ DMA in the odd phases] | s_barrier | MI x NI MFMAs | s_barrier —
@@ -225,8 +234,8 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
         for (int i = 0; i < H_IT; ++i)
             if (wave + NW * i >= pc_lo && wave + NW * i < pc_hi && wave + NW * i < HBLK) issue_halo(slice_plane(0), 0, 0, wave + NW * i);
         issue_w(0, 0);
-        if (nq > 1) issue_w(1 % nq1, 1);
-        if (nq > 2) issue_w(2 % nq1, 2);
+        if (nq > 1) issue_w(1, 1);                              // (nq1 >= 18: the first three half tiles are of pass 0)
+        if (nq > 2) issue_w(2, 2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (grp == 1) __builtin_amdgcn_s_barrier();
@@ -251,17 +260,17 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
                 issue_halo(slice_plane(gs + 1), slice_cc(gs + 1), (gs + 1) & 1, wave + NW * r);
             if (q >= 1) {
                 if (q + 2 < nq) {
-                    issue_w(w2, st == 0 ? 2 : st - 1);         // the stage of half tile q - 1 = (q + 2) mod 3
+                    issue_w(w2, st == 0 ? 2 : st - 1, wl16 && wpass == 1);         // the stage of half tile q - 1 = (q + 2) mod 3
                     wait_all_but_last_w();
                 } else {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
-                w2 = (w2 + 1 == nq1) ? 0 : w2 + 1;
+                if (++w2 == nq1) { w2 = 0; ++wpass; }
             }
             bar1();
             if (wave_on) mfmas(B1);
             bar2();
-            if (A_lo && q + 1 == nq1) {
+            if (A_lo && q + 1 == nq_lo) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -323,8 +332,8 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
             if (addr_late) issue_halo(slice_plane(gs + 1), slice_cc(gs + 1), (gs + 1) & 1, wave + NW * r);
             else request_halo(slice_plane(gs + 1), slice_cc(gs + 1), (gs + 1) & 1, wave + NW * r, hoff);
         }
-        if (q + 3 < nq) issue_w(w3, st);
-        w3 = (w3 + 1 == nq1) ? 0 : w3 + 1;
+        if (q + 3 < nq) issue_w(w3, st, wl16 && wpass == 1);
+        if (++w3 == nq1) { w3 = 0; ++wpass; }
         if (wave_on) {
             if (q + 1 < nq) {
                 if (addr_late) frags(gs1 & 1, r1 >> 1, r1 & 1, st1, 0, B0);
@@ -336,7 +345,7 @@ __global__ __launch_bounds__(512) void stencil_tile_kernel(const PncGemmParams p
             if (!addr_late) frag_addr(gs1 & 1, r1 >> 1, r1 & 1, st1, 1, ta, tb);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (A_lo && q + 1 == nq1) {
+        if (A_lo && q + 1 == nq_lo) {
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -418,7 +427,9 @@ int conv3x3_tile_geometry(const PncGemmParams& p, unsigned epi) {
     if (!opt) return 0;
     if (p.stride != 1 || p.upsample || p.conv_pad_br || (p.Cin & 63) || p.Hin != p.Hout || p.Win != p.Wout) return 0;
     if (p.K != 9 * p.Cin || p.M % (p.Hout * p.Wout)) return 0;
-    if (p.A_lo && p.a_lo_fmt != PNC_LO_F16) return 0;            // the tile kernel's lo pass reads fp16 planes (same MFMA as the hi pass)
+    // the tile kernel's lo pass reads fp16 planes (same MFMA as the hi pass): an e4m3 A_lo / W_lo pair is never selected here and
+    // runs on the per-tap kernel, where W_lo keeps its e4m3 meaning
+    if (p.A_lo && p.a_lo_fmt != PNC_LO_F16) return 0;
     if (epi != E_O16 && epi != E_O32 && epi != (E_O32 | E_O16) && epi != (E_R1 | E_O32) && epi != (E_R1 | E_O32 | E_O16)) return 0;
     int tws = 0;
     if ((p.Hout % 16) == 0 && (p.Wout % 16) == 0) tws = 4;

@@ -10,6 +10,7 @@ constexpr int SM_MAXM = 16;
 // one wave per output column n: out[m][n] = sum_k f(a[m][k]) W[n][k] + bias[n]
 __global__ __launch_bounds__(256) void linear_smallm_kernel(const float* __restrict__ a, int lda,
                                                             const half_t* __restrict__ W,
+                                                            const half_t* __restrict__ W_lo,
                                                             const float* __restrict__ bias,
                                                             float* __restrict__ out, int ldo, int M, int N,
                                                             int K, int silu_in, int silu_out) {
@@ -24,6 +25,11 @@ __global__ __launch_bounds__(256) void linear_smallm_kernel(const float* __restr
         float wf[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) wf[e] = (float)w[e];
+        if (W_lo) {             // (uniform) split weights: W = W_hi + 2^-11 W_lo, joined in fp32 (the activations are fp32 here)
+            const half8v wl = *reinterpret_cast<const half8v*>(W_lo + (int64_t)n * K + k0);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) wf[e] = fmaf((float)wl[e], 1.0f / 2048.0f, wf[e]);
+        }
 #pragma unroll
         for (int m = 0; m < SM_MAXM; ++m) {
             if (m < M) {
@@ -63,6 +69,7 @@ struct SmallmSegs {
 
 __global__ __launch_bounds__(256) void linear_smallm_seg_kernel(const float* __restrict__ a, int lda,
                                                                 const half_t* __restrict__ W,
+                                                                const half_t* __restrict__ W_lo,
                                                                 const float* __restrict__ bias,
                                                                 float* __restrict__ out, int M, int m0, int Mtot, int N,
                                                                 int K, int silu_in, int silu_out, SmallmSegs segs) {
@@ -81,6 +88,11 @@ __global__ __launch_bounds__(256) void linear_smallm_seg_kernel(const float* __r
             const half8v w = *reinterpret_cast<const half8v*>(W + (int64_t)(n0 + c) * K + k0);
 #pragma unroll
             for (int e = 0; e < 8; ++e) wf[c][e] = (float)w[e];
+            if (W_lo) {         // (uniform) split weights, as in linear_smallm_kernel
+                const half8v wl = *reinterpret_cast<const half8v*>(W_lo + (int64_t)(n0 + c) * K + k0);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) wf[c][e] = fmaf((float)wl[e], 1.0f / 2048.0f, wf[c][e]);
+            }
         }
 #pragma unroll
         for (int m = 0; m < SM_MAXM; ++m) {
@@ -459,24 +471,36 @@ extern "C" int pnc_set_option(int option, int value) {
     return g_options[option].exchange(value, std::memory_order_relaxed);
 }
 
+extern "C" int pnc_linear_smallm_split(const float* a, int lda, const void* W, const void* W_lo, const float* bias,
+                                       float* out, int ldo, int M, int N, int K, int silu_in, int silu_out,
+                                       void* stream) {
+    if (!a || !W || !out || M < 1 || M > SM_MAXM || N < 1 || K < 8) return PNC_EINVAL;
+    if (K % 8 || lda % 4) return PNC_EINVAL;
+    if (((uintptr_t)a | (uintptr_t)W | (uintptr_t)W_lo) & 15) return PNC_EALIGN;
+    hipLaunchKernelGGL(linear_smallm_kernel, dim3((N + 3) / 4), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), a, lda, reinterpret_cast<const half_t*>(W),
+                       reinterpret_cast<const half_t*>(W_lo), bias, out, ldo, M, N, K, silu_in, silu_out);
+    return pnc_launch_status();
+}
+
 extern "C" int pnc_linear_smallm(const float* a, int lda, const void* W, const float* bias,
                                  float* out, int ldo, int M, int N, int K, int silu_in, int silu_out,
                                  void* stream) {
-    if (!a || !W || !out || M < 1 || M > SM_MAXM || N < 1 || K < 8) return PNC_EINVAL;
-    if (K % 8 || lda % 4) return PNC_EINVAL;
-    if (((uintptr_t)a | (uintptr_t)W) & 15) return PNC_EALIGN;
-    hipLaunchKernelGGL(linear_smallm_kernel, dim3((N + 3) / 4), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), a, lda, reinterpret_cast<const half_t*>(W), bias,
-                       out, ldo, M, N, K, silu_in, silu_out);
-    return pnc_launch_status();
+    return pnc_linear_smallm_split(a, lda, W, nullptr, bias, out, ldo, M, N, K, silu_in, silu_out, stream);
 }
 
 extern "C" int pnc_linear_smallm_segments(const float* a, int lda, const void* W, const float* bias, float* out, int M,
                                           int m0, int Mtot, int N, int K, const int32_t* seg_start, int nseg, int silu_in,
                                           int silu_out, void* stream) {
+    return pnc_linear_smallm_segments_split(a, lda, W, nullptr, bias, out, M, m0, Mtot, N, K, seg_start, nseg, silu_in, silu_out, stream);
+}
+
+extern "C" int pnc_linear_smallm_segments_split(const float* a, int lda, const void* W, const void* W_lo, const float* bias,
+                                                float* out, int M, int m0, int Mtot, int N, int K, const int32_t* seg_start,
+                                                int nseg, int silu_in, int silu_out, void* stream) {
     if (!a || !W || !out || !seg_start || M < 1 || M > SM_MAXM || m0 < 0 || m0 + M > Mtot || N < 1 || K < 8) return PNC_EINVAL;
     if (K % 8 || lda % 4 || nseg < 1 || nseg > PNC_SMALLM_MAX_SEGS) return PNC_EINVAL;
-    if (((uintptr_t)a | (uintptr_t)W) & 15) return PNC_EALIGN;
+    if (((uintptr_t)a | (uintptr_t)W | (uintptr_t)W_lo) & 15) return PNC_EALIGN;
     SmallmSegs segs;
     segs.nseg = nseg;
     if (seg_start[0] != 0 || seg_start[nseg] != N) return PNC_EINVAL;
@@ -486,7 +510,8 @@ extern "C" int pnc_linear_smallm_segments(const float* a, int lda, const void* W
     }
     const int waves = N / SEG_NC;
     hipLaunchKernelGGL(linear_smallm_seg_kernel, dim3((waves + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, lda,
-                       reinterpret_cast<const half_t*>(W), bias, out, M, m0, Mtot, N, K, silu_in, silu_out, segs);
+                       reinterpret_cast<const half_t*>(W), reinterpret_cast<const half_t*>(W_lo), bias, out, M, m0, Mtot, N, K, silu_in,
+                       silu_out, segs);
     return pnc_launch_status();
 }
 

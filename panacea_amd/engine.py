@@ -16,6 +16,7 @@ code never calls it and there is no automatic fallback.
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 import os
 from dataclasses import dataclass
@@ -86,6 +87,15 @@ class Precision:
     ctx: bool = False
     ff_hidden: bool = False
     attn_o: bool = False
+    # `weights`: the packed WEIGHTS are split too, W = fp16(W) + 2^-11 * fp16((W - fp16(W)) * 2^11) (PncGemmParams.W_lo).  Every GEMM
+    # adds the A_hi * W_lo products to its lo pass, so an fp32 checkpoint is multiplied at ~22 bits instead of being rounded to fp16
+    # first (that rounding alone is 1.3e-3 .. 2.1e-3 of eps on the tiny network).  The plane joins the fp16 lo
+    # pass of a split activation: the flag needs every class split and fp16 lo planes.
+    # It is a plain class attribute here and a field of the subclass SplitWeights only.  The fields of THIS class are the operand
+    # classes and `lo8`; code that enumerates dataclasses.fields(Precision) as "the classes" (tests/test_precise_wide.py does) keeps
+    # seeing exactly those, and `weights` splits no activation.  So `precise-full` is a SplitWeights and never equal to a Precision:
+    # where both should answer alike, ask is_wide().
+    weights = False
 
     def __post_init__(self):
         att = (self.qkv, self.q_text, self.kv_text, self.attn_o, self.ctx)
@@ -93,16 +103,30 @@ class Precision:
             raise ValueError("the attention operand classes qkv, q_text, kv_text, ctx and attn_o are split together or not at all")
         if any(att) and self.lo8:
             raise ValueError("the split attention kernels read fp16 lo planes: a policy that splits q / k / v cannot set lo8")
+        if self.weights and self.lo8:
+            raise ValueError("split weights ride on the fp16 lo pass: a policy with `weights` cannot set lo8 (the e4m3 form of a weight "
+                             "lo pass would need an e4m3 copy of every activation's hi plane)")
+        if self.weights and not all(getattr(self, c) for c in OPERAND_CLASSES):
+            raise ValueError("split weights need every operand class split: each GEMM that receives W_lo must also receive an fp16 A_lo")
 
     @property
     def name(self) -> str:
-        on = [k for k, v in self.__dict__.items() if v and k != "lo8"]
-        return "fp16" if not on else "split(" + ",".join(on) + (")+e4m3-lo" if self.lo8 else ")")
+        on = [k for k, v in self.__dict__.items() if v and k not in ("lo8", "weights")]
+        return "fp16" if not on else "split(" + ",".join(on) + (")+e4m3-lo" if self.lo8 else ")") + ("+weights" if self.weights else "")
 
     def lo_dtype(self, cls: str) -> torch.dtype:
         """dtype of the lo plane of operand class `cls` (= its PNC_LO_* format, panacea_amd.hip.lo_fmt)"""
         return torch.uint8 if (self.lo8 and cls in LO8_CLASSES) else torch.float16
 
+
+@dataclass(frozen=True)
+class SplitWeights(Precision):
+    """A policy whose weights are split as well (`weights`, see Precision): every operand class split, fp16 lo planes"""
+    weights: bool = True
+
+
+OPERAND_CLASSES = ("stream", "gn_stt", "ff_out", "stem", "gn_head", "gn_res", "gnt", "conv_mid",
+                   "ln", "qkv", "q_text", "kv_text", "ctx", "ff_hidden", "attn_o")
 
 # classes whose consumers all run the e4m3 lo pass: plain-A GEMMs with K % 16 == 0 and the conv gathers with Cin % 64 == 0.
 # Not: `stem` (Cin = 8: a 16-byte chunk of e4m3 would span two taps), `conv_mid` (narrow hint-stem layers), `gn_res` (its
@@ -124,8 +148,18 @@ PRECISE_F16LO = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_h
 # heavy-tail weight set, where `precise` leaves 2.0e-3.  The target of on_range_exceeded = "escalate".
 PRECISE_WIDE = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_head=True, gn_res=True, gnt=True, conv_mid=True,
                          ln=True, qkv=True, q_text=True, kv_text=True, ctx=True, ff_hidden=True, attn_o=True)
+# `precise-wide` plus split weights: the policy for fp32 checkpoints, whose weights are not fp16-representable.  Three fp16 passes
+# per GEMM instead of two, and an fp16 lo twin of every packed weight (about +4.5 GB at full size).
+PRECISE_FULL = SplitWeights(**dataclasses.asdict(PRECISE_WIDE))
 PRECISIONS = {"fast": FAST, "precise": PRECISE, "precise-all": PRECISE_ALL, "precise-lite": PRECISE_LITE,
-              "precise-f16lo": PRECISE_F16LO, "precise-wide": PRECISE_WIDE}
+              "precise-f16lo": PRECISE_F16LO, "precise-wide": PRECISE_WIDE, "precise-full": PRECISE_FULL}
+
+
+def is_wide(p) -> bool:
+    """every operand class split with fp16 lo planes, hence the split attention kernels: `precise-wide`, `precise-full` and any policy
+    built like them, whatever its class or `weights` flag.  Single-device policies (no frame / view shards)."""
+    p = precision(p)
+    return not p.lo8 and all(getattr(p, c) for c in OPERAND_CLASSES)
 
 
 def precision(p) -> Precision:
@@ -721,17 +755,44 @@ class Runtime:
 # ----------------------------------------------------------------------------------------------
 # weight packing (fp32 checkpoint tensors -> fp16 operand layouts of the kernels)
 # ----------------------------------------------------------------------------------------------
-def pk_f16(w: torch.Tensor) -> torch.Tensor:
-    return w.detach().to(torch.float16).contiguous()
+def split_lo(w: torch.Tensor, hi16: torch.Tensor) -> torch.Tensor:
+    """lo plane of a split weight whose hi plane is `hi16`: fp16((w - hi16) * 2^11), from the fp32 (unrounded) values `w`"""
+    return ((w.detach().to(torch.float32) - hi16.to(torch.float32)) * 2048.0).to(torch.float16)
+
+
+def _cast16(w: torch.Tensor, lo: bool = False) -> torch.Tensor:
+    """the fp16 plane of a weight the packers store: fp16(w), or — `lo`, building a lo twin — fp16((w - fp16(w)) * 2^11).
+    Elementwise, so every permutation and zero padding the packers apply around it gives the lo plane the layout of its hi plane."""
+    w = w.detach()
+    hi = w.to(torch.float16)
+    return split_lo(w, hi) if lo else hi
+
+
+def lo_planes(packed):
+    """what a lo twin keeps of the result of a `_pack(lo=True)` / `pack(lo=True)`: the fp16 planes, in their places; every other
+    tensor (fp32 biases, norm parameters, tables — the hi copies hold them) becomes None; numbers stay"""
+    if isinstance(packed, torch.Tensor):
+        return packed if packed.dtype == torch.float16 else None
+    if isinstance(packed, dict):
+        return {k: lo_planes(v) for k, v in packed.items()}
+    if isinstance(packed, (list, tuple)):
+        return type(packed)(lo_planes(v) for v in packed)
+    return packed
+
+
+# Every fp16 packer takes `lo`: False = the hi plane fp16(w) (the packed weight), True = the lo plane of the same weight in the same
+# layout.  The modules' `_pack(lo)` hand it on, so one body describes both planes.
+def pk_f16(w: torch.Tensor, lo: bool = False) -> torch.Tensor:
+    return _cast16(w, lo).contiguous()
 
 
 def pk_f32(w: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return None if w is None else w.detach().to(torch.float32).contiguous()
 
 
-def pk_linear(w: torch.Tensor) -> torch.Tensor:
+def pk_linear(w: torch.Tensor, lo: bool = False) -> torch.Tensor:
     """nn.Linear weight [N, K] is already the W[N][K] operand."""
-    return pk_f16(w.reshape(w.shape[0], -1))
+    return pk_f16(w.reshape(w.shape[0], -1), lo)
 
 
 def pk_lo8(w16: torch.Tensor):
@@ -745,40 +806,49 @@ def pk_lo8(w16: torch.Tensor):
     return q.view(torch.uint8).contiguous(), 127 - sh
 
 
-def wlo(pk: dict, key, a_lo: Optional[torch.Tensor], w16: Optional[torch.Tensor] = None):
+def wlo(pk: dict, key, a_lo: Optional[torch.Tensor], w16: Optional[torch.Tensor] = None, rt: Optional["Runtime"] = None):
     """w_lo argument of a GEMM whose A operand has the lo plane `a_lo`: the e4m3 copy of the packed weight pk[key] (or `w16`)
-    when the plane is e4m3 — packed on first use and kept in `pk` next to the fp16 weights — else None"""
-    if a_lo is None or a_lo.dtype != torch.uint8:
+    when the plane is e4m3 — packed on first use and kept in `pk` next to the fp16 weights —; the fp16 lo twin of pk[key] when the
+    plane is fp16 and the policy of `rt` splits the weights (Packable.packed_lo: built on first use; `key` may be a path, and an
+    entry that is a (weight, bias) pair gives its weight); else None"""
+    if a_lo is None:
         return None
+    if a_lo.dtype != torch.uint8:
+        if rt is None or not rt.prec.weights:
+            return None
+        t = pk.lo()
+        for k in (key if isinstance(key, tuple) else (key,)):
+            t = t[k]
+        return t[0] if isinstance(t, tuple) else t
     k8 = (key, "lo8")
     if k8 not in pk:
         pk[k8] = pk_lo8(pk[key] if w16 is None else w16)
     return pk[k8]
 
 
-def pk_conv3x3(w: torch.Tensor, cin_pad: Optional[int] = None) -> torch.Tensor:
+def pk_conv3x3(w: torch.Tensor, cin_pad: Optional[int] = None, lo: bool = False) -> torch.Tensor:
     """[Cout, Cin, 3, 3] -> [Cout, 9*Cin_pad].  K order (ky, kx, ci) for narrow inputs; (ci/64, ky, kx, ci%64) when
     Cin_pad % 64 == 0 (see include/panacea_hip.h: the nine taps of a 64-channel slice become adjacent K tiles)."""
     co, ci = w.shape[0], w.shape[1]
     cp = cin_pad or ((ci + 7) // 8 * 8)
     p = torch.zeros((co, 3, 3, cp), device=w.device, dtype=torch.float16)
-    p[..., :ci] = w.detach().permute(0, 2, 3, 1).to(torch.float16)
+    p[..., :ci] = _cast16(w.detach().permute(0, 2, 3, 1), lo)
     if cp % 64 == 0:
         p = p.view(co, 9, cp // 64, 64).permute(0, 2, 1, 3)
     return p.reshape(co, 9 * cp).contiguous()
 
 
-def pk_conv1d(w: torch.Tensor) -> torch.Tensor:
+def pk_conv1d(w: torch.Tensor, lo: bool = False) -> torch.Tensor:
     """[Cout, Cin, 3] -> [Cout, 3*Cin] with K ordered (dt, ci); (ci/64, dt, ci%64) when Cin % 64 == 0 (include/panacea_hip.h:
     the three taps of a 64-channel slice become adjacent K tiles)."""
     co, ci = w.shape[0], w.shape[1]
     p = w.detach().permute(0, 2, 1)
     if ci % 64 == 0:
         p = p.reshape(co, 3, ci // 64, 64).permute(0, 2, 1, 3)
-    return pk_f16(p.reshape(co, -1))
+    return pk_f16(p.reshape(co, -1), lo)
 
 
-def pk_geglu(w: torch.Tensor, b: torch.Tensor):
+def pk_geglu(w: torch.Tensor, b: torch.Tensor, lo: bool = False):
     """GEGLU projection [8C, C]: rows [0,4C) are values, [4C,8C) gates (attention.py:97).  Interleave
     32-row blocks (value block j, gate block j) so that the two MFMA column blocks of one wave hold a
     value and its gate at the same accumulator position."""
@@ -788,7 +858,7 @@ def pk_geglu(w: torch.Tensor, b: torch.Tensor):
     wv, wg = w[:n2].view(n2 // 32, 32, -1), w[n2:].view(n2 // 32, 32, -1)
     wi = torch.stack([wv, wg], dim=1).reshape(2 * n2, -1)
     bi = torch.stack([b[:n2].view(-1, 32), b[n2:].view(-1, 32)], dim=1).reshape(-1)
-    return pk_f16(wi), pk_f32(bi)
+    return pk_f16(wi, lo), pk_f32(bi)
 
 
 # K order inside every aligned group of 16 on the weight side of the fused chains (include/panacea_hip.h, section 1b): position
@@ -804,16 +874,28 @@ def mfma_a_fragments(w16: torch.Tensor) -> torch.Tensor:
     return wp.reshape(R, 32, S, 2, 8).permute(0, 2, 3, 1, 4).reshape(R, S, 64, 8).contiguous()
 
 
+class Packed(dict):
+    """what Packable.packed() returns: the packed copies, and the way to their lo twins (`lo()`, engine.wlo)"""
+    owner = None
+
+    def lo(self) -> dict:
+        return self.owner.packed_lo()
+
+
 class Packable:
-    """Mixin for modules that keep kernel-layout copies of their parameters in `self._pk`."""
+    """Mixin for modules that keep kernel-layout copies of their parameters in `self._pk` — and, under a policy that splits the
+    weights, the fp16 lo twins of the fp16 ones in `self._pk_lo` (built on first use, dropped together with `_pk`)."""
     _pk: Optional[dict] = None
+    _pk_lo: Optional[dict] = None
 
     def _init_packable(self):
         self._pk = None
+        self._pk_lo = None
         self.register_load_state_dict_post_hook(lambda m, _k: m.invalidate_packed())
 
     def invalidate_packed(self):
         self._pk = None
+        self._pk_lo = None
 
     def _apply(self, fn, *a, **k):          # .to() / .cuda() / .half() move the parameters
         self.invalidate_packed()
@@ -822,10 +904,20 @@ class Packable:
     def packed(self) -> dict:
         if self._pk is None:
             with torch.no_grad():
-                self._pk = self._pack()
+                self._pk = Packed(self._pack())
+                self._pk.owner = self
         return self._pk
 
-    def _pack(self) -> dict:                # pragma: no cover
+    def packed_lo(self) -> dict:
+        """`_pack(lo=True)`: the LO plane of every fp16 weight, fp16((w - fp16(w)) * 2^11) of the fp32 parameter, under the keys and
+        with the permutations and padding of `packed()`; entries that are not fp16 planes are None (engine.lo_planes).  Only a
+        policy with `weights` asks for it (engine.wlo)."""
+        if self._pk_lo is None:
+            with torch.no_grad():
+                self._pk_lo = lo_planes(self._pack(lo=True))
+        return self._pk_lo
+
+    def _pack(self, lo: bool = False) -> dict:                # pragma: no cover
         raise NotImplementedError
 
 
@@ -947,13 +1039,20 @@ def layer_norm_split(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta
 
 
 def small_linear(rt: Runtime, a32: torch.Tensor, w16: torch.Tensor, bias, M: int, N: int, K: int,
-                 silu_in=False, silu_out=False) -> torch.Tensor:
-    """fp32-activation linear for the (frames x 1280) time-embedding path; rows in chunks of 16."""
+                 silu_in=False, silu_out=False, w_lo: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32-activation linear for the (frames x 1280) time-embedding path; rows in chunks of 16.  `w_lo`: the lo twin of w16
+    under a policy that splits the weights (the kernel joins the pair in fp32)."""
     out = rt.empty((M, N), torch.float32)
+    kw = {} if w_lo is None else dict(w_lo=w_lo)
     for m0 in range(0, M, 16):
         mm = min(16, M - m0)
-        rt.be.linear_smallm(a32[m0:], K, w16, bias, out[m0:], N, mm, N, K, silu_in, silu_out)
+        rt.be.linear_smallm(a32[m0:], K, w16, bias, out[m0:], N, mm, N, K, silu_in, silu_out, **kw)
     return out
+
+
+def wlo32(pk: dict, key, rt: Runtime) -> Optional[torch.Tensor]:
+    """lo twin of the packed weight pk[key] of an fp32-activation linear (small_linear), or None unless the policy splits the weights"""
+    return pk.lo()[key] if rt.prec.weights else None
 
 
 _FREQS: Dict[tuple, torch.Tensor] = {}

@@ -131,6 +131,8 @@ _SIGNATURES = {
     "pnc_layernorm": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _P]),
     "pnc_linear_smallm": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "pnc_linear_smallm_segments": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "pnc_linear_smallm_split": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "pnc_linear_smallm_segments_split": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "pnc_timestep_embedding": (_I, [_P, _I, _I, _P, _P, _P]),
     "pnc_timestep_embedding_f32": (_I, [_P, _I, _I, _P, _P, _P]),
     "pnc_nchw_to_tokens_f16": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -333,7 +335,8 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
     """`gn_part` (temporal conv only): receives the GroupNorm(32) records of the fp32 output, ceil(Npix / 64) per frame
     (PncGemmParams.gn_part).  `a16_lo` / `out16_lo`: lo planes of precise (split) operands, see PncGemmParams.A_lo in the header; their dtype names the
     format (fp16, or uint8 = e4m3 bytes).  `w_lo` = (W_lo e4m3 bytes [N, K], w_lo_exp E8M0 byte of the tensor) — engine.pk_lo8 —
-    is the weight side of an e4m3 lo pass."""
+    is the weight side of an e4m3 lo pass; `w_lo` = an fp16 tensor in w16's layout is the lo plane of split weights (engine.wlo under
+    the `precise-full` policy, PncGemmParams.W_lo): it goes with an fp16 `a16_lo`."""
     p = GemmParams()
     p.struct_bytes = C.sizeof(GemmParams)
     f16, f32 = torch.float16, torch.float32
@@ -345,6 +348,8 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
             raise PncError("an e4m3 lo plane needs the e4m3 copy of the weights (w_lo = engine.pk_lo8(w16))")
         p.W_lo, p.w_lo_exp = _ptr(w_lo[0], torch.uint8, "w_lo"), int(w_lo[1])
         p.ldw_lo = w_lo[0].shape[-1]
+    elif w_lo is not None:         # split weights; the library refuses the plane without an fp16 a16_lo
+        p.W_lo, p.ldw_lo = _ptr(w_lo, f16, "w_lo"), w_ld
     p.M, p.N, p.K, p.lda, p.a_mode, p.ldw = M, N, K, lda, a_mode, w_ld
     if ln_out16 is not None:       # LayerNorm of the fp32 output rows, fused into the GEMM where a workgroup owns whole rows
         p.ln_gamma, p.ln_beta, p.ln_out16 = _ptr(ln_gamma, torch.float32, "ln_gamma"), _ptr(ln_beta, torch.float32, "ln_beta"), \
@@ -492,15 +497,28 @@ def layernorm(x32, ldx, M, Cch, gamma, beta, eps, y16, ldy, y16_lo=None):
                   _ptr(beta), eps, _ptr(y16), ldy, _ptr(y16_lo), _stream()), "pnc_layernorm")
 
 
-def linear_smallm(a32, lda, w16, bias, out32, ldo, M, N, K, silu_in=False, silu_out=False):
+def linear_smallm(a32, lda, w16, bias, out32, ldo, M, N, K, silu_in=False, silu_out=False, w_lo=None):
+    """`w_lo`: the fp16 lo plane of split weights (pnc_linear_smallm_split)"""
+    if w_lo is not None:
+        _check(_timed("linear_smallm", 2.0 * M * N * K, 4.0 * N * K, load().pnc_linear_smallm_split, _ptr(a32), lda, _ptr(w16),
+                      _ptr(w_lo, torch.float16, "w_lo"), _ptr(bias), _ptr(out32), ldo, M, N, K, int(silu_in), int(silu_out),
+                      _stream()), "pnc_linear_smallm_split")
+        return
     _check(_timed("linear_smallm", 2.0 * M * N * K, 2.0 * N * K, load().pnc_linear_smallm, _ptr(a32), lda, _ptr(w16),
                   _ptr(bias), _ptr(out32), ldo, M, N, K, int(silu_in), int(silu_out), _stream()), "pnc_linear_smallm")
 
 
-def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_start, silu_in=False, silu_out=False):
+def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_start, silu_in=False, silu_out=False, w_lo=None):
     """the same linear for len(seg_start) - 1 sites in one launch: out32 = one contiguous [Mtot, width] block per site, blocks back
-    to back (include/panacea_hip.h); `seg_start` = the sites' first columns + [N], a host sequence"""
+    to back (include/panacea_hip.h); `seg_start` = the sites' first columns + [N], a host sequence; `w_lo`: the fp16 lo plane of
+    split weights (pnc_linear_smallm_segments_split)"""
     segs = (C.c_int32 * len(seg_start))(*seg_start)
+    if w_lo is not None:
+        _check(_timed("linear_smallm", 2.0 * M * N * K, 4.0 * N * K, load().pnc_linear_smallm_segments_split, _ptr(a32), lda,
+                      _ptr(w16), _ptr(w_lo, torch.float16, "w_lo"), _ptr(bias), _ptr(out32), M, m0, Mtot, N, K,
+                      C.cast(segs, C.c_void_p), len(seg_start) - 1, int(silu_in), int(silu_out), _stream()),
+               "pnc_linear_smallm_segments_split")
+        return
     _check(_timed("linear_smallm", 2.0 * M * N * K, 2.0 * N * K, load().pnc_linear_smallm_segments, _ptr(a32), lda, _ptr(w16),
                   _ptr(bias), _ptr(out32), M, m0, Mtot, N, K, C.cast(segs, C.c_void_p), len(seg_start) - 1, int(silu_in),
                   int(silu_out), _stream()), "pnc_linear_smallm_segments")

@@ -78,9 +78,9 @@ class FeedForward(nn.Module, Packable):
         self.net = nn.Sequential(GEGLU(dim, inner_dim), nn.Dropout(dropout), nn.Linear(inner_dim, dim_out))
         self._init_packable()
 
-    def _pack(self):
-        w1, b1 = E.pk_geglu(self.net[0].proj.weight, self.net[0].proj.bias)
-        return dict(w1=w1, b1=b1, w2=E.pk_linear(self.net[2].weight), b2=E.pk_f32(self.net[2].bias))
+    def _pack(self, lo=False):
+        w1, b1 = E.pk_geglu(self.net[0].proj.weight, self.net[0].proj.bias, lo)
+        return dict(w1=w1, b1=b1, w2=E.pk_linear(self.net[2].weight, lo), b2=E.pk_f32(self.net[2].bias))
 
     def _run(self, rt: Runtime, x16, M, res32, out32=None, out16=None, out16_lo=None, x16_lo=None):
         """out = FF(x16) + res32 -> out32 (may alias res32) and/or out16 (+ lo plane of a precise operand).  `x16_lo`: lo plane
@@ -88,10 +88,10 @@ class FeedForward(nn.Module, Packable):
         pk = self.packed()
         hid = rt.empty((M, self.inner_dim), torch.float16)
         hid_lo = rt.lo_plane((M, self.inner_dim), "ff_hidden")
-        wide = {} if x16_lo is None else dict(a16_lo=x16_lo)
+        wide = {} if x16_lo is None else dict(a16_lo=x16_lo, w_lo=E.wlo(pk, "w1", x16_lo, rt=rt))
         rt.be.gemm(x16, pk["w1"], M=M, N=2 * self.inner_dim, K=self.dim, lda=self.dim, bias=pk["b1"],
                    geglu=True, out16=hid, ldc16=self.inner_dim, **wide, **({} if hid_lo is None else dict(out16_lo=hid_lo)))
-        wide = {} if hid_lo is None else dict(a16_lo=hid_lo)
+        wide = {} if hid_lo is None else dict(a16_lo=hid_lo, w_lo=E.wlo(pk, "w2", hid_lo, rt=rt))
         rt.be.gemm(hid, pk["w2"], M=M, N=self.dim_out, K=self.inner_dim, lda=self.inner_dim, bias=pk["b2"],
                    res1=res32, ldr1=self.dim_out, out32=out32, ldc32=self.dim_out, out16=out16,
                    ldc16=self.dim_out, out16_lo=out16_lo, **wide)
@@ -137,13 +137,13 @@ class _AttentionBase(nn.Module, Packable):
         self.backend = backend
         self._init_packable()
 
-    def _pack(self):
-        pk = dict(wo=E.pk_linear(self.to_out[0].weight), bo=E.pk_f32(self.to_out[0].bias))
+    def _pack(self, lo=False):
+        pk = dict(wo=E.pk_linear(self.to_out[0].weight, lo), bo=E.pk_f32(self.to_out[0].bias))
         if self.is_self:
-            pk["wqkv"] = E.pk_f16(torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], dim=0))
+            pk["wqkv"] = E.pk_f16(torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], dim=0), lo)
         else:
-            pk["wq"], pk["wk"], pk["wv"] = (E.pk_linear(self.to_q.weight), E.pk_linear(self.to_k.weight),
-                                            E.pk_linear(self.to_v.weight))
+            pk["wq"], pk["wk"], pk["wv"] = (E.pk_linear(self.to_q.weight, lo), E.pk_linear(self.to_k.weight, lo),
+                                            E.pk_linear(self.to_v.weight, lo))
         return pk
 
     # ---- text cross-attention: x16 [M, C] queries of F frames vs the 77 context tokens of each sample
@@ -161,7 +161,10 @@ class _AttentionBase(nn.Module, Packable):
             kv, kv_lo = rt.empty((rows, 2 * C), torch.float16), rt.lo_plane((rows, 2 * C), "kv_text")
             if "wkv" not in pk:                       # [W_k; W_v], packed once next to them
                 pk["wkv"] = torch.cat([pk["wk"], pk["wv"]]).contiguous()
-            rt.be.gemm(rt.ctx16, pk["wkv"], M=rows, N=2 * C, K=D, lda=D, out16=kv, ldc16=2 * C, out16_lo=kv_lo, a16_lo=rt.ctx16_lo)
+            if rt.prec.weights and "wkv" not in pk.lo():
+                pk.lo()["wkv"] = torch.cat([pk.lo()["wk"], pk.lo()["wv"]]).contiguous()
+            rt.be.gemm(rt.ctx16, pk["wkv"], M=rows, N=2 * C, K=D, lda=D, out16=kv, ldc16=2 * C, out16_lo=kv_lo, a16_lo=rt.ctx16_lo,
+                       w_lo=E.wlo(pk, "wkv", rt.ctx16_lo, rt=rt))
             f, fl = kv.view(-1), kv_lo.view(-1)
             return f, fl, f[C:], fl[C:], 2 * C
         k = rt.empty((rows, C), torch.float16)
@@ -177,7 +180,8 @@ class _AttentionBase(nn.Module, Packable):
         C, M = self.inner_dim, F * H * W
         if rt.prec.q_text:
             q, q_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "q_text")
-            rt.be.gemm(x16, pk["wq"], M=M, N=C, K=self.query_dim, lda=self.query_dim, out16=q, ldc16=C, out16_lo=q_lo, a16_lo=x16_lo)
+            rt.be.gemm(x16, pk["wq"], M=M, N=C, K=self.query_dim, lda=self.query_dim, out16=q, ldc16=C, out16_lo=q_lo, a16_lo=x16_lo,
+                       w_lo=E.wlo(pk, "wq", x16_lo, rt=rt))
             k, k_lo, v, v_lo, ld = self._text_kv(rt)
             o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
             rt.be.attn_views_split(q, q_lo, C, k, k_lo, ld, v, v_lo, ld, o, o_lo, C, groups=F, heads=self.heads, H=H, W=W,
@@ -200,7 +204,7 @@ class _AttentionBase(nn.Module, Packable):
         """split policy: to_out(o) + res on the split attention output, then the LayerNorm that follows -> (y16, y16_lo)"""
         pk = self.packed()
         rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32, ldr1=self.query_dim, out32=out32,
-                   ldc32=self.query_dim, a16_lo=o_lo)
+                   ldc32=self.query_dim, a16_lo=o_lo, w_lo=E.wlo(pk, "wo", o_lo, rt=rt))
         return _ln_after(rt, ln, out32, M, self.query_dim, None)
 
     def _qkv_split(self, rt: Runtime, x16, x16_lo, M):
@@ -210,7 +214,7 @@ class _AttentionBase(nn.Module, Packable):
         C = self.inner_dim
         qkv, qkv_lo = rt.empty((M, 3 * C), torch.float16), rt.lo_plane((M, 3 * C), "qkv")
         rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qkv, ldc16=3 * C, out16_lo=qkv_lo,
-                   a16_lo=x16_lo)
+                   a16_lo=x16_lo, w_lo=E.wlo(pk, "wqkv", x16_lo, rt=rt))
         return qkv.view(-1), qkv_lo.view(-1)
 
     # ---- spatial self-attention over width-sliced views (views = 1: plain attention)
@@ -334,7 +338,7 @@ class BasicTransformerBlock(nn.Module, Packable):
         self.dim = dim
         self._init_packable()
 
-    def _pack(self):
+    def _pack(self, lo=False):
         return {f"{n}{s}": E.pk_f32(getattr(getattr(self, n), "weight" if s == "w" else "bias"))
                 for n in ("norm1", "norm2", "norm3") for s in ("w", "b")}
 
@@ -433,14 +437,14 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         self.identity_layer = nn.Identity()
         self._init_packable()
 
-    def _pack(self):
+    def _pack(self, lo=False):
         pk = {}
         sfx = ["", "_temporal"] + (["_crossview"] if self.insert_crossview else [])
         for s in sfx:
             n, pi, po = getattr(self, "norm" + s), getattr(self, "proj_in" + s), getattr(self, "proj_out" + s)
             pk["g" + s], pk["b" + s] = E.pk_f32(n.weight), E.pk_f32(n.bias)
-            pk["wi" + s], pk["bi" + s] = E.pk_linear(pi.weight), E.pk_f32(pi.bias)
-            pk["wo" + s], pk["bo" + s] = E.pk_linear(po.weight), E.pk_f32(po.bias)
+            pk["wi" + s], pk["bi" + s] = E.pk_linear(pi.weight, lo), E.pk_f32(pi.bias)
+            pk["wo" + s], pk["bo" + s] = E.pk_linear(po.weight, lo), E.pk_f32(po.bias)
         pk["pos"] = E.temporal_pos_table(self.num_frames, self.inner_dim).to(self.proj_in.weight.device)
         return pk
 
@@ -466,10 +470,10 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         if branch == "temporal":
             # + position table indexed by t = frame % T (attention.py:1117-1118)
             rt.be.gemm(n16, pk["wi" + sfx], M=Mb, N=C, K=C, lda=C, bias=pk["bi" + sfx], rowbias=pk["pos"],
-                       rb_rows=Hb * Wb, rb_mod=rt.T, out32=t32, ldc32=C, a16_lo=n16lo, w_lo=E.wlo(pk, "wi" + sfx, n16lo), **lnkw)
+                       rb_rows=Hb * Wb, rb_mod=rt.T, out32=t32, ldc32=C, a16_lo=n16lo, w_lo=E.wlo(pk, "wi" + sfx, n16lo, rt=rt), **lnkw)
         else:
             rt.be.gemm(n16, pk["wi" + sfx], M=Mb, N=C, K=C, lda=C, bias=pk["bi" + sfx], out32=t32, ldc32=C,
-                       a16_lo=n16lo, w_lo=E.wlo(pk, "wi" + sfx, n16lo), **lnkw)
+                       a16_lo=n16lo, w_lo=E.wlo(pk, "wi" + sfx, n16lo, rt=rt), **lnkw)
         p16 = p16lo = None
         for i, blk in enumerate(blocks):
             r = blk._run(rt, t32, Fb, Hb, Wb, branch, last=(i == len(blocks) - 1), x16=x16 if i == 0 else None)
@@ -480,7 +484,7 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         # x = proj_out(t) + x_in, in place on the stream
         rt.be.gemm(p16, pk["wo" + sfx], M=M, N=C, K=C, lda=C, bias=pk["bo" + sfx], res1=x.f32, ldr1=C,
                    out32=x.f32, ldc32=C, out16=out16, ldc16=C, a16_lo=p16lo, out16_lo=out16_lo,
-                   w_lo=E.wlo(pk, "wo" + sfx, p16lo))
+                   w_lo=E.wlo(pk, "wo" + sfx, p16lo, rt=rt))
 
     def _run(self, rt: Runtime, x: Act, want_f16: bool = False) -> Act:
         if rt.T != self.num_frames:
@@ -527,7 +531,7 @@ class TextKVProjector:
         else:
             self.parts = None
 
-    def pack(self):
+    def pack(self, lo=False):
         dims = {a.context_dim for a in self.sites}
         if len(dims) != 1:
             raise ValueError(f"cross-attention sites with different context widths {sorted(dims)}")
@@ -540,7 +544,7 @@ class TextKVProjector:
         for a in self.sites:
             offs.append(o)
             o += a.inner_dim
-        return E.pk_f16(w), nt, nkp, offs, dims.pop()
+        return E.pk_f16(w, lo), nt, nkp, offs, dims.pop()
 
     def run(self, rt: Runtime):
         if not self.sites:
@@ -561,7 +565,13 @@ class TextKVProjector:
             # split policy: every output column row-major with its lo plane (the split attention kernels read V row-major)
             ld = NKp + NT
             kv, kv_lo = rt.empty((rows, ld), torch.float16), rt.lo_plane((rows, ld), "kv_text")
-            rt.be.gemm(rt.ctx16, w, M=rows, N=ld, K=D, lda=D, out16=kv, ldc16=ld, out16_lo=kv_lo, a16_lo=rt.ctx16_lo)
+            w_lo = None
+            if rt.prec.weights:                       # the lo twin of the stacked weights: same rows, same zero padding (n_split)
+                if getattr(self, "_pk_lo", None) is None or getattr(self, "_sig_lo", None) != sig:
+                    with torch.no_grad():
+                        self._pk_lo, self._sig_lo = self.pack(lo=True)[0], sig
+                w_lo = self._pk_lo
+            rt.be.gemm(rt.ctx16, w, M=rows, N=ld, K=D, lda=D, out16=kv, ldc16=ld, out16_lo=kv_lo, a16_lo=rt.ctx16_lo, w_lo=w_lo)
             f, fl = kv.view(-1), kv_lo.view(-1)
             for a, o in zip(self.sites, offs):
                 rt.text_kv[id(a)] = (f[o:], fl[o:], f[NKp + o:], fl[NKp + o:], ld)

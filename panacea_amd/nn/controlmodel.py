@@ -67,13 +67,20 @@ class ControlNet3D(UNetModel3D):
     def make_zero_conv(self, channels, dims=2):
         return TimestepEmbedSequential(zero_module(conv_nd(dims, channels, channels, 1, padding=0)))
 
-    def _pack(self):
-        pk = super()._pack()
-        pk["hint"] = [conv_params(m) for m in self.input_hint_block if isinstance(m, nn.Conv2d)]
+    def _pack(self, lo=False):
+        pk = super()._pack(lo)
+        pk["hint"] = [conv_params(m, lo) for m in self.input_hint_block if isinstance(m, nn.Conv2d)]
         s = float(self.control_scales)
         zc = []
         for z in list(self.zero_convs) + [self.middle_block_out]:
-            w, b = conv_params(z[0])
+            w, b = conv_params(z[0], lo)
+            if s != 1.0 and lo:
+                # lo twin: the scale is folded BEFORE the split — the residual of the fp32 product w * s against
+                # the hi plane the branch below stores
+                w32 = z[0].weight.detach().float().reshape(w.shape)
+                w = E.split_lo(w32 * s, (w32.half().float() * s).half()).contiguous()
+                zc.append((w, b * s))
+                continue
             zc.append(((w.float() * s).half().contiguous(), b * s) if s != 1.0 else (w, b))
         pk["zero"] = zc
         return pk
@@ -90,7 +97,8 @@ class ControlNet3D(UNetModel3D):
         for i, ((w, b), s) in enumerate(zip(pk["hint"], HINT_STRIDES)):
             last = i == len(HINT_STRIDES) - 1
             a = run_conv3x3(rt, a.f16, a.F, a.H, a.W, a.C, w, b, w.shape[0], stride=s, act_silu=not last,
-                            out32=last, out16=not last, x16_lo=a.f16_lo, split_out="conv_mid")
+                            out32=last, out16=not last, x16_lo=a.f16_lo, split_out="conv_mid",
+                            w_lo=E.wlo(pk, ("hint", i), a.f16_lo, rt=rt))
         return a
 
     def _run_control(self, rt: Runtime, x16: Act, hint: torch.Tensor, emb32: torch.Tensor) -> List[Act]:
@@ -130,7 +138,7 @@ class ControlNet3D(UNetModel3D):
         o = rt.empty((h.M, h.C), torch.float32)
         x16 = h.need_f16(rt)
         rt.be.gemm(x16, w16, M=h.M, N=h.C, K=h.C, lda=h.C, bias=b, out32=o, ldc32=h.C, a16_lo=h.f16_lo,
-                   w_lo=E.wlo(pk, ("zero", idx), h.f16_lo, w16))
+                   w_lo=E.wlo(pk, ("zero", idx), h.f16_lo, w16, rt=rt))
         return Act(h.F, h.H, h.W, h.C, f32=o)
 
     def forward(self, x, hint, timesteps=None, context=None, y=None, **kwargs):

@@ -35,12 +35,13 @@ class TimestepBlock(nn.Module):
     """openaimodel.py:66-76 — marker for children that take the timestep embedding."""
 
 
-def conv_params(conv: nn.Conv2d):
+def conv_params(conv: nn.Conv2d, lo=False):
+    """(packed weight, fp32 bias) of a 3x3 or 1x1 conv; `lo`: the weight's lo plane (engine.pk_f16)"""
     k = conv.kernel_size[0]
     if k == 3:
-        return E.pk_conv3x3(conv.weight), E.pk_f32(conv.bias)
+        return E.pk_conv3x3(conv.weight, lo=lo), E.pk_f32(conv.bias)
     if k == 1:
-        return E.pk_linear(conv.weight), E.pk_f32(conv.bias)
+        return E.pk_linear(conv.weight, lo), E.pk_f32(conv.bias)
     raise NotImplementedError(f"conv kernel size {k}")
 
 
@@ -100,8 +101,8 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock, Packable):
         super().__init__(*args)
         self._init_packable()
 
-    def _pack(self):
-        return {i: conv_params(m) for i, m in enumerate(self) if isinstance(m, nn.Conv2d)}
+    def _pack(self, lo=False):
+        return {i: conv_params(m, lo) for i, m in enumerate(self) if isinstance(m, nn.Conv2d)}
 
     def _run(self, rt: Runtime, x: Act, emb32, want_f16: bool = False) -> Act:
         layers = list(self)
@@ -119,7 +120,7 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock, Packable):
                 pk = self.packed()
                 w16, b = pk[i]
                 x16 = x.need_f16(rt)
-                w_lo = E.wlo(pk, i, x.f16_lo, w16)
+                w_lo = E.wlo(pk, i, x.f16_lo, w16, rt=rt)
                 if layer.kernel_size[0] == 3:
                     x = run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, w16, b, layer.out_channels,
                                     stride=layer.stride[0], out16=wf, x16_lo=x.f16_lo, split_out="stream", w_lo=w_lo)
@@ -147,8 +148,8 @@ class Upsample(nn.Module, Packable):
         self.conv = conv_nd(dims, self.channels, self.out_channels, 3, padding=padding)
         self._init_packable()
 
-    def _pack(self):
-        w, b = conv_params(self.conv)
+    def _pack(self, lo=False):
+        w, b = conv_params(self.conv, lo)
         return dict(w=w, b=b)
 
     # the conv's operand as a precise pair (class `stream`).  False (bench.py --upsample-plain-operand, an A/B of the error budget):
@@ -160,7 +161,7 @@ class Upsample(nn.Module, Packable):
         x16 = x.need_f16(rt)
         lo = x.f16_lo if self.precise_operand else None
         return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk["w"], pk["b"], self.out_channels,
-                           upsample=True, out16=want_f16, x16_lo=lo, split_out="stream", w_lo=E.wlo(pk, "w", lo))
+                           upsample=True, out16=want_f16, x16_lo=lo, split_out="stream", w_lo=E.wlo(pk, "w", lo, rt=rt))
 
 
 class Downsample(nn.Module, Packable):
@@ -174,15 +175,15 @@ class Downsample(nn.Module, Packable):
         self.op = conv_nd(dims, self.channels, self.out_channels, 3, stride=2, padding=padding)
         self._init_packable()
 
-    def _pack(self):
-        w, b = conv_params(self.op)
+    def _pack(self, lo=False):
+        w, b = conv_params(self.op, lo)
         return dict(w=w, b=b)
 
     def _run(self, rt: Runtime, x: Act, want_f16=False) -> Act:
         pk = self.packed()
         x16 = x.need_f16(rt)
         return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk["w"], pk["b"], self.out_channels,
-                           stride=2, out16=want_f16, x16_lo=x.f16_lo, split_out="stream", w_lo=E.wlo(pk, "w", x.f16_lo))
+                           stride=2, out16=want_f16, x16_lo=x.f16_lo, split_out="stream", w_lo=E.wlo(pk, "w", x.f16_lo, rt=rt))
 
 
 class ResBlock3D(TimestepBlock, Packable):
@@ -221,16 +222,16 @@ class ResBlock3D(TimestepBlock, Packable):
         self.skip_connection = nn.Identity() if oc == channels else conv_nd(dims, channels, oc, 1)
         self._init_packable()
 
-    def _pack(self):
+    def _pack(self, lo=False):
         f32, il, it, ol, ot = E.pk_f32, self.in_layers, self.in_layers_temporal, self.out_layers, self.out_layers_temporal
         pk = dict(
-            g1=f32(il[0].weight), b1=f32(il[0].bias), w1=E.pk_conv3x3(il[2].weight), c1=f32(il[2].bias),
-            gt1=f32(it[0].weight), bt1=f32(it[0].bias), wt1=E.pk_conv1d(it[2].weight), ct1=f32(it[2].bias),
-            we=E.pk_linear(self.emb_layers[1].weight), be=f32(self.emb_layers[1].bias),
-            g2=f32(ol[0].weight), b2=f32(ol[0].bias), w2=E.pk_conv3x3(ol[3].weight), c2=f32(ol[3].bias),
-            gt2=f32(ot[0].weight), bt2=f32(ot[0].bias), wt2=E.pk_conv1d(ot[3].weight), ct2=f32(ot[3].bias))
+            g1=f32(il[0].weight), b1=f32(il[0].bias), w1=E.pk_conv3x3(il[2].weight, lo=lo), c1=f32(il[2].bias),
+            gt1=f32(it[0].weight), bt1=f32(it[0].bias), wt1=E.pk_conv1d(it[2].weight, lo), ct1=f32(it[2].bias),
+            we=E.pk_linear(self.emb_layers[1].weight, lo), be=f32(self.emb_layers[1].bias),
+            g2=f32(ol[0].weight), b2=f32(ol[0].bias), w2=E.pk_conv3x3(ol[3].weight, lo=lo), c2=f32(ol[3].bias),
+            gt2=f32(ot[0].weight), bt2=f32(ot[0].bias), wt2=E.pk_conv1d(ot[3].weight, lo), ct2=f32(ot[3].bias))
         if isinstance(self.skip_connection, nn.Conv2d):
-            pk["ws"], pk["bs"] = E.pk_linear(self.skip_connection.weight), f32(self.skip_connection.bias)
+            pk["ws"], pk["bs"] = E.pk_linear(self.skip_connection.weight, lo), f32(self.skip_connection.bias)
         return pk
 
     def _emb_out(self, rt: Runtime, emb32: torch.Tensor, pk, F: int, Co: int) -> torch.Tensor:
@@ -239,7 +240,7 @@ class ResBlock3D(TimestepBlock, Packable):
         out = rt.emb_proj.get(id(self))
         if out is not None and out.shape == (F, Co):
             return out
-        return E.small_linear(rt, emb32, pk["we"], pk["be"], F, Co, self.emb_channels)
+        return E.small_linear(rt, emb32, pk["we"], pk["be"], F, Co, self.emb_channels, w_lo=E.wlo32(pk, "we", rt))
 
     def _run(self, rt: Runtime, x: Act, emb32: torch.Tensor, want_f16: bool = False, want_stats: bool = False) -> Act:
         if rt.T != self.num_frames:
@@ -257,7 +258,7 @@ class ResBlock3D(TimestepBlock, Packable):
         # in_layers: GN + SiLU + conv3x3
         tail = 2 * F * x.H if rt.vshard is not None else 0      # room for a view band's neighbour columns (_conv3x3_view_band)
         a16, a16lo = E.gn_spatial(rt, x.f32, F, N, Cin, pk["g1"], pk["b1"], 1e-5, True, split="gn_res", tail_rows=tail, part=x.gn_part)
-        h = run_conv3x3(rt, a16, F, H, W, Cin, pk["w1"], pk["c1"], Co, x16_lo=a16lo).f32
+        h = run_conv3x3(rt, a16, F, H, W, Cin, pk["w1"], pk["c1"], Co, x16_lo=a16lo, w_lo=E.wlo(pk, "w1", a16lo, rt=rt)).f32
         # h = h + conv1d_t(SiLU(GN_t(h))) + emb_layers(emb)[frame]      (:505-531)
         # emb32 arrives as SiLU(emb): the activation of `emb_layers` is applied ONCE per network evaluation by
         # _time_embedding (32 ResBlocks x 16 x 1280 identical SiLUs otherwise), the Linear runs here
@@ -273,13 +274,13 @@ class ResBlock3D(TimestepBlock, Packable):
             part1 = E.gn_records(rt, F, N)
             rt.be.gemm(t16, pk["wt1"], M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tch, bias=pk["ct1"],
                        rowbias=emb_out, rb_rows=N, rb_mod=F, res1=h, ldr1=Co, out32=h, ldc32=Co, a16_lo=t16lo,
-                       w_lo=E.wlo(pk, "wt1", t16lo), gn_part=part1)
+                       w_lo=E.wlo(pk, "wt1", t16lo, rt=rt), gn_part=part1)
         elif sh is not None:
             # (round 2's form, FrameShard(resblock="transpose"): the fp32 stream to the pixel sharding and back)
             # the exchange runs on the communicator's stream; what this site computes independently of it — the timestep
             # embedding's linear and the skip path — is enqueued under the transfer
             pend = sh.to_pixels_start(h, rt.B, N)
-            emb_out = E.small_linear(rt, rt.emb_all, pk["we"], pk["be"], rt.B * rt.T, Co, self.emb_channels)
+            emb_out = E.small_linear(rt, rt.emb_all, pk["we"], pk["be"], rt.B * rt.T, Co, self.emb_channels, w_lo=E.wlo32(pk, "we", rt))
             s = self._skip(rt, x, pk)
             h = pend.result()
         else:
@@ -290,12 +291,12 @@ class ResBlock3D(TimestepBlock, Packable):
             part1 = E.gn_records(rt, F, N) if sh is None else None
             rt.be.gemm(t16, pk["wt1"], M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct1"],
                        rowbias=emb_out, rb_rows=Nt, rb_mod=rt.B * rt.T, res1=h, ldr1=Co, out32=h, ldc32=Co, a16_lo=t16lo,
-                       w_lo=E.wlo(pk, "wt1", t16lo), gn_part=part1)
+                       w_lo=E.wlo(pk, "wt1", t16lo, rt=rt), gn_part=part1)
             if sh is not None:
                 h = sh.to_frames(h, rt.B, N)
         # out_layers: GN + SiLU + conv3x3
         a16, a16lo = E.gn_spatial(rt, h, F, N, Co, pk["g2"], pk["b2"], 1e-5, True, split="gn_res", tail_rows=tail, part=part1)
-        g = run_conv3x3(rt, a16, F, H, W, Co, pk["w2"], pk["c2"], Co, x16_lo=a16lo).f32
+        g = run_conv3x3(rt, a16, F, H, W, Co, pk["w2"], pk["c2"], Co, x16_lo=a16lo, w_lo=E.wlo(pk, "w2", a16lo, rt=rt)).f32
         # skip path
         if s is None:
             s = self._skip(rt, x, pk)
@@ -314,13 +315,13 @@ class ResBlock3D(TimestepBlock, Packable):
             part2 = E.gn_records(rt, F, N) if want_stats else None
             rt.be.gemm(t16, pk["wt2"], M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tc2, bias=pk["ct2"],
                        res1=g, ldr1=Co, res2=s, ldr2=Co, out32=g, ldc32=Co, out16=o16, ldc16=Co, a16_lo=t16lo,
-                       out16_lo=o16lo, w_lo=E.wlo(pk, "wt2", t16lo), gn_part=part2)
+                       out16_lo=o16lo, w_lo=E.wlo(pk, "wt2", t16lo, rt=rt), gn_part=part2)
         else:
             # the skip path stays in the frame layout: g + conv1d in the pixel layout, exchange back, then + skip
             gp = sh.to_pixels(g, rt.B, N)
             t16, t16lo = E.gn_temporal(rt, gp, Nt, Co, pk["gt2"], pk["bt2"], 1e-5)
             rt.be.gemm(t16, pk["wt2"], M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct2"],
-                       res1=gp, ldr1=Co, out32=gp, ldc32=Co, a16_lo=t16lo, w_lo=E.wlo(pk, "wt2", t16lo))
+                       res1=gp, ldr1=Co, out32=gp, ldc32=Co, a16_lo=t16lo, w_lo=E.wlo(pk, "wt2", t16lo, rt=rt))
             g = sh.to_frames(gp, rt.B, N)
             rt.be.add_f32(g, s, M * Co, g, o16, o16lo)
         return Act(F, H, W, Co, f32=g, f16=o16, f16_lo=o16lo, gn_part=part2)
@@ -332,7 +333,7 @@ class ResBlock3D(TimestepBlock, Packable):
         s = rt.empty((x.M, self.out_channels), torch.float32)
         x16 = x.need_f16(rt)
         rt.be.gemm(x16, pk["ws"], M=x.M, N=self.out_channels, K=self.channels, lda=self.channels, bias=pk["bs"], out32=s,
-                   ldc32=self.out_channels, a16_lo=x.f16_lo, w_lo=E.wlo(pk, "ws", x.f16_lo))
+                   ldc32=self.out_channels, a16_lo=x.f16_lo, w_lo=E.wlo(pk, "ws", x.f16_lo, rt=rt))
         return s
 
     precision = "precise"      # operand policy of the reference-compatible entry below (the network sets rt.prec itself)
@@ -354,15 +355,15 @@ class EmbProjector:
 
     def __init__(self, root):
         self.blocks = [m for m in root.modules() if isinstance(m, ResBlock3D)]
-        self._pk = self._sig = None
+        self._pk = self._sig = self._pk_lo = self._sig_lo = None
 
-    def pack(self):
+    def pack(self, lo=False):
         w = torch.cat([b.emb_layers[1].weight for b in self.blocks], dim=0)
         bias = torch.cat([b.emb_layers[1].bias for b in self.blocks], dim=0)
         seg = [0]
         for b in self.blocks:
             seg.append(seg[-1] + b.out_channels)
-        return E.pk_linear(w), E.pk_f32(bias), seg
+        return E.pk_linear(w, lo), E.pk_f32(bias), seg
 
     def run(self, rt: Runtime, emb32: torch.Tensor):
         if not self.blocks or len(self.blocks) > 64 or any(b.out_channels % 4 for b in self.blocks):
@@ -376,8 +377,14 @@ class EmbProjector:
         w, bias, seg = self._pk
         F, K = emb32.shape[0], self.blocks[0].emb_channels
         out = rt.empty((seg[-1] * F,), torch.float32)
+        kw = {}
+        if rt.prec.weights:                           # the lo twin of the stacked weights follows the same sources
+            if self._pk_lo is None or self._sig_lo != sig:
+                with torch.no_grad():
+                    self._pk_lo, self._sig_lo = self.pack(lo=True)[0], sig
+            kw = dict(w_lo=self._pk_lo)
         for m0 in range(0, F, 16):
-            rt.be.linear_smallm_segments(emb32[m0:], K, w, bias, out, min(16, F - m0), m0, F, seg[-1], K, seg)
+            rt.be.linear_smallm_segments(emb32[m0:], K, w, bias, out, min(16, F - m0), m0, F, seg[-1], K, seg, **kw)
         for b, s0, s1 in zip(self.blocks, seg[:-1], seg[1:]):
             rt.emb_proj[id(b)] = out[s0 * F:s1 * F].view(F, s1 - s0)
 
@@ -540,11 +547,18 @@ class UNetModel3D(nn.Module, Packable):
         gmin = min(((m.out_channels // 32) * m.num_frames for m in self.modules() if isinstance(m, ResBlock3D)), default=4)
         prec = self.precision
         esc = self.__dict__.get("_escalated")
-        if E.precision(prec) == E.PRECISE_WIDE:
+        if E.is_wide(prec):
             # every operand class split with fp16 lo planes: the range of the bound is fp16's own (measured 8.5e-6 eps in the CPU
             # error budget of the heavy-tail weight set)
             out = {"policy": prec, "eps_max_abs": 1e-3 if gmin >= 4 else 2.5e-3, "values_per_temporal_group": gmin,
                    "valid_for": "|operand| < 65504"}
+            if E.precision(prec).weights:
+                # `precise-full`: the weights of this network are split as well, so the bound holds for fp32 checkpoints — it no longer
+                # asks for fp16-representable weights (|w| < 65504 like every operand).  The first-stage VAE and the text tower are
+                # outside this network and keep single fp16 weights.
+                out["weights"] = "split (fp16 hi + lo planes): fp32 checkpoints, |w| < 65504"
+            else:
+                out["weights"] = "single fp16: the bound is stated on fp16-representable weights"
             if esc is not None:
                 out["escalated_from"], out["trigger_count"] = esc["from"], esc["trigger_count"]
             return out
@@ -612,7 +626,7 @@ class UNetModel3D(nn.Module, Packable):
         evaluations are not re-run"""
         if self.frame_shard is None and self.view_shard is None:
             return
-        if self.on_range_exceeded == "escalate" or E.precision(self.precision) == E.PRECISE_WIDE:
+        if self.on_range_exceeded == "escalate" or E.is_wide(self.precision):
             raise ValueError("the 'precise-wide' operand policy and on_range_exceeded='escalate' do not run frame- or view-sharded")
 
     def _evaluate(self, once, device):
@@ -735,13 +749,13 @@ class UNetModel3D(nn.Module, Packable):
         ep.run(rt, emb32)
 
     # ---- packed parameters owned by the network itself (time embedding MLP, output head)
-    def _pack(self):
+    def _pack(self, lo=False):
         te = self.time_embed
-        pk = dict(tw0=E.pk_linear(te[0].weight), tb0=E.pk_f32(te[0].bias),
-                  tw2=E.pk_linear(te[2].weight), tb2=E.pk_f32(te[2].bias))
+        pk = dict(tw0=E.pk_linear(te[0].weight, lo), tb0=E.pk_f32(te[0].bias),
+                  tw2=E.pk_linear(te[2].weight, lo), tb2=E.pk_f32(te[2].bias))
         if hasattr(self, "out"):
             pk["og"], pk["ob"] = E.pk_f32(self.out[0].weight), E.pk_f32(self.out[0].bias)
-            pk["ow"], pk["oc"] = E.pk_conv3x3(self.out[2].weight), E.pk_f32(self.out[2].bias)
+            pk["ow"], pk["oc"] = E.pk_conv3x3(self.out[2].weight, lo=lo), E.pk_f32(self.out[2].bias)
         return pk
 
     def _time_embedding(self, rt: Runtime, timesteps: torch.Tensor) -> torch.Tensor:
@@ -751,9 +765,9 @@ class UNetModel3D(nn.Module, Packable):
         if mc % 8:
             raise NotImplementedError("model_channels must be a multiple of 8")
         t_emb = timestep_embedding(timesteps.to(rt.device), mc)
-        h = E.small_linear(rt, t_emb, pk["tw0"], pk["tb0"], rt.F, td, mc, silu_out=True)
+        h = E.small_linear(rt, t_emb, pk["tw0"], pk["tb0"], rt.F, td, mc, silu_out=True, w_lo=E.wlo32(pk, "tw0", rt))
         # returns SiLU(emb): every consumer of emb (ResBlock3D.emb_layers, :468-476) starts with nn.SiLU
-        emb = E.small_linear(rt, h, pk["tw2"], pk["tb2"], rt.F, td, td, silu_out=True)
+        emb = E.small_linear(rt, h, pk["tw2"], pk["tb2"], rt.F, td, td, silu_out=True, w_lo=E.wlo32(pk, "tw2", rt))
         if rt.shard is not None:
             # the temporal sites run on all T frames of a pixel: they index the embedding rows of ALL frames (40 KB)
             rt.emb_all = rt.shard.gather_rows(emb, rt.B)
@@ -766,7 +780,7 @@ class UNetModel3D(nn.Module, Packable):
         a16, a16lo = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, pk["og"], pk["ob"], 1e-5, True, split="gn_head",
                                   tail_rows=2 * h.F * h.H if rt.vshard is not None else 0)
         o = run_conv3x3(rt, a16, h.F, h.H, h.W, h.C, pk["ow"], pk["oc"], self.out_channels, x16_lo=a16lo,
-                        w_lo=E.wlo(pk, "ow", a16lo))
+                        w_lo=E.wlo(pk, "ow", a16lo, rt=rt))
         if tokens:
             return o
         out = rt.empty((h.F, self.out_channels, h.H, h.W), torch.float32)

@@ -32,14 +32,17 @@ def _fp16_round(a: np.ndarray) -> np.ndarray:
 TAIL_PERIOD, TAIL_PHASE = 64, 5       # heavy-tail weight sets: output channels c with c % 64 == 5 of every residual-out tensor
 
 
-def synth_tensor(name: str, shape: Tuple[int, ...], salt: int = 0, tail: float = 0.0) -> torch.Tensor:
+def synth_tensor(name: str, shape: Tuple[int, ...], salt: int = 0, tail: float = 0.0, round_fp16: bool = True) -> torch.Tensor:
     """One parameter, from its NAME and SHAPE only.
 
     `tail` > 0 (a power of two, so the values stay fp16-representable) multiplies the output rows c % 64 == 5 of every tensor that
     writes into the residual stream: a few "massive activation" channels, as trained diffusion / transformer checkpoints have
     them, carry the stream to |v| = 10^2 .. 10^3 — the regime where the e4m3 lo plane of an fp16-rounded operand clamps
     (include/panacea_hip.h: |v| >= 512) and a GroupNorm group is dominated by one channel.  Default 0: the weight sets of every
-    earlier pin are unchanged."""
+    earlier pin are unchanged.
+
+    `round_fp16` = False skips the final rounding: the same stream as plain fp32 values, as an fp32 checkpoint holds them — weights
+    that are NOT fp16-representable (the `precise-full` operand policy, tests/golden/tiny_w32.npz)."""
     g = _rng(name, salt)
     shape = tuple(int(s) for s in shape)
     leaf = name.rsplit(".", 1)[-1]
@@ -56,18 +59,19 @@ def synth_tensor(name: str, shape: Tuple[int, ...], salt: int = 0, tail: float =
         a = g.standard_normal(shape, dtype=np.float32) * (gain / np.sqrt(max(fan_in, 1)))
         if tail > 0.0 and gain != 1.0 and len(shape) > 1:
             a[TAIL_PHASE::TAIL_PERIOD] *= np.float32(tail)
-    return torch.from_numpy(_fp16_round(a))
+    return torch.from_numpy(_fp16_round(a) if round_fp16 else np.ascontiguousarray(a, dtype=np.float32))
 
 
-def synth_state_dict(manifest: Dict[str, Iterable[int]], salt: int = 0, threads: int = 8, tail: float = 0.0) -> Dict[str, torch.Tensor]:
+def synth_state_dict(manifest: Dict[str, Iterable[int]], salt: int = 0, threads: int = 8, tail: float = 0.0,
+                     round_fp16: bool = True) -> Dict[str, torch.Tensor]:
     """Every tensor is generated from its own (name, shape) stream, so the result does not depend on the
     thread count; numpy's Generator releases the GIL while sampling."""
     items = list(manifest.items())
     if threads <= 1 or len(items) < 64:
-        return {k: synth_tensor(k, tuple(v), salt, tail) for k, v in items}
+        return {k: synth_tensor(k, tuple(v), salt, tail, round_fp16) for k, v in items}
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(threads) as ex:
-        vals = list(ex.map(lambda kv: synth_tensor(kv[0], tuple(kv[1]), salt, tail), items))
+        vals = list(ex.map(lambda kv: synth_tensor(kv[0], tuple(kv[1]), salt, tail, round_fp16), items))
     return {k: v for (k, _), v in zip(items, vals)}
 
 

@@ -3,7 +3,8 @@
     python tools/exp/wide_timing.py [--reps 5]
 
 One MI355X, the full network on synthetic weights: ms per evaluation (mean of --reps after two warm-ups) under `precise` with "warn",
-`precise` with "escalate" (ordinary weights: never triggers, adds one synchronous counter read per evaluation) and `precise-wide`,
+`precise` with "escalate" (ordinary weights: never triggers, adds one synchronous counter read per evaluation), `precise-wide` and
+`precise-full` (split weights on top: profiles/precise_full.md),
 then the per-launch time of the split attention kernels from one profiled `precise-wide` evaluation (hip.Profiler, HIP events)."""
 import argparse
 import sys
@@ -46,6 +47,9 @@ def main():
         m.on_range_exceeded = "warn"
         m.precision = "precise-wide"
         print(f"precise-wide: {ms():.1f} ms per evaluation")
+        m.precision = "precise-full"
+        print(f"precise-full: {ms():.1f} ms per evaluation")
+        m.precision = "precise-wide"
         p = hip.Profiler()
         hip.set_profiler(p)
         w(inp["x"], inp["t"], cond(inp))

@@ -15,7 +15,7 @@ from pathlib import Path
 import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from panacea_amd import build_network, checkpoint, configs, pipeline, sampling, synth   # noqa: E402
+from panacea_amd import build_network, checkpoint, configs, engine, pipeline, sampling, synth   # noqa: E402
 from panacea_amd.nn import model                                               # noqa: E402
 
 VAE = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4, 4],
@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--prediction", choices=["eps", "v", "edm"], default="eps", help="denoiser parameterisation")
     ap.add_argument("--discretization", choices=sorted(DISCRETIZATIONS), default="ddpm", help="the sampler's sigma schedule")
     ap.add_argument("--frames", type=int, default=8, choices=range(1, 17), metavar="1..16", help="frames per clip (num_frames)")
+    ap.add_argument("--precision", choices=sorted(engine.PRECISIONS), default=None,
+                    help="operand policy of the denoiser (default: the network's own, `precise`); `precise-full` splits the weights too — "
+                         "the policy for fp32 checkpoints")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
@@ -62,6 +65,8 @@ def main():
         net.diffusion_model.load_state_dict(synth.synth_state_dict(man), strict=True)
         fs.load_state_dict(synth.synth_state_dict({k: list(v.shape) for k, v in fs.state_dict().items()}), strict=True)
     net, fs = net.to(dev), fs.to(dev)
+    if a.precision:
+        net.diffusion_model.precision = a.precision
     _, _, h, w = configs.SHAPES["full"]
     T = a.frames
     g = {k: v.to(dev) for k, v in synth.synth_inputs(2, T, h, w, context_dim=kw["context_dim"]).items()}
