@@ -40,7 +40,9 @@ const char* pnc_version(void);
  *  8: + pnc_cfg_sampler_step / PncSamplerStepParams;
  *  still 8 (additive, no struct / prototype / option changes): PncGemmParams.W_lo next to an fp16 A_lo is the fp16 lo plane of the
  *  weights, + pnc_linear_smallm_split / pnc_linear_smallm_segments_split.  One check is stricter for existing callers: a non-NULL
- *  PncGemmParams.W_lo with A_lo = NULL, which pnc_gemm_f16 used to ignore, is now PNC_EINVAL — clear the field with A_lo) */
+ *  PncGemmParams.W_lo with A_lo = NULL, which pnc_gemm_f16 used to ignore, is now PNC_EINVAL — clear the field with A_lo;
+ *  still 8 (additive): + pnc_attn_uses_text_kernel.  One dispatch is narrower: the few-key kernel takes key buffers whose row count
+ *  kvH * kvW is a multiple of 8 only, a ragged buffer (77 rows) runs on the general kernel — same attention, see PncAttnParams.kv_valid) */
 #define PNC_ABI_VERSION 8
 int pnc_abi_version(void);
 /* hex SHA-256 of the sources + compile flags the library was built from (panacea_amd/build.py computes the same digest over
@@ -281,7 +283,11 @@ typedef struct PncAttnParams {
     int32_t kvH, kvW, kv_views;     /* kv grid per kv group */
     int32_t kv_rows_per_group;      /* rows of K per kv group */
     int32_t q_per_kv;               /* kv group = g / q_per_kv */
-    int32_t kv_valid;               /* valid keys per kv view (<= kvH*kvW/kv_views) */
+    int32_t kv_valid;               /* valid keys per kv view (<= kvH*kvW/kv_views).  PADDING CONTRACT, Nkv = kvH*kvW/kv_views keys per view:
+                                       the K rows and V^T entries of keys kv_valid .. Nkv - 1 of a view ARE read and must be finite (a
+                                       probability of exactly 0 does not silence a NaN or Inf); their values do not influence the output,
+                                       not by one bit.  Nothing at or beyond key Nkv of a view, and no row at or beyond row kvH*kvW of a
+                                       group's K, is read: a V^T row may end at its last key, whatever ldvt says */
     int32_t nseg[8];                /* per q view */
     int32_t seg[8][2];              /* kv view ids */
     float scale;                    /* softmax scale (d^-0.5) */
@@ -297,6 +303,11 @@ typedef struct PncAttnParams {
 } PncAttnParams;
 
 int pnc_attn_views_f16(const PncAttnParams* p, void* stream);
+/* 1 when pnc_attn_views_f16 would launch its single-pass few-key kernel (PNC_OPT_ATTN_VARIANT: 43) for these parameters under the
+ * current options, 0 when the general kernel runs or the parameters are refused — answered by the dispatch's own predicate.  The
+ * few-key kernel needs: one view, one segment, not causal, kvH * kvW <= 96 and a multiple of 8, 64 < kv_valid <= 96, ldvt /
+ * vt_gstride / ldk multiples of 8; unforced, also 16 or more workgroups per group (query tiles of 128 x groups of 5 heads) */
+int pnc_attn_uses_text_kernel(const PncAttnParams* p);
 
 /* Temporal self-attention over the T frames of one pixel (head dim 64), 1 <= T <= 16:
  *   row m = (b*T+t)*Npix + p; q/k/v fp16 with leading dims; out fp16.

@@ -434,6 +434,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && QB == 2 && DMA) ? 2 : 1) void 
 //     lane instead of 64);
 //   * K / V^T of head h + 1 arrive by LDS-DMA under head h's arithmetic (two stages of 28 KB).
 // Same S^T = K Q^T / O^T = V^T P^T register layout as attn_views_kernel (a lane owns a query; K rows permuted by kperm()).
+// ACCEPTED BUFFERS (attn_text_dispatch is the one place that decides): one view, one segment, not causal, a key buffer of
+// Nkv = kvH * kvW <= 96 rows with Nkv % 8 == 0 and 64 < kv_valid <= Nkv, ldvt / vt_gstride / ldk multiples of 8.  K is read row by
+// row (key < Nkv), V^T in 16-byte chunks of 8 keys guarded per chunk (kc < Nkv) — hence Nkv % 8 == 0: with 77 rows the chunk at key
+// 72 would bring in keys 77 .. 79 from behind the row, and P = 0 times a NaN found there is NaN.  Keys kv_valid .. Nkv - 1 ARE read
+// and must be finite (PncAttnParams.kv_valid); their probabilities are exact zeros, so their values do not matter.
 template <int HG>
 __global__ __launch_bounds__(256, 2) void attn_text_kernel(const PncAttnParams p, const int nhg) {
     constexpr int KROWS = 96, STAGE = KROWS * 128 + 2 * 64 * 128;      // K tile (96 keys) + two V^T tiles (keys 0-63, 64-127)
@@ -490,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void attn_text_kernel(const PncAttnParams p
     if (nh > 1) dma_head(1, 1);
     const float sc = p.scale * 1.44269504088896340736f;
     const int krow_lds = kperm(frow);
-    // Padding keys (kv_valid .. 95; their K rows are zeros) are masked through the ACCUMULATOR'S INITIAL VALUE: block 2's first MFMA
+    // Padding keys (kv_valid .. 95; their K rows are finite — zeros in the product — so -1e30 + K.q stays -1e30) are masked through the ACCUMULATOR'S INITIAL VALUE: block 2's first MFMA
     // starts from -1e30 at this lane's padding positions (key 64 + grp * 16 + r >= kv_valid) and from 0 elsewhere — sixteen registers
     // set once per workgroup, no compare / select chain per head (the host dispatches this kernel for 64 < kv_valid <= 96 only)
     f32x16 init2;
@@ -771,16 +776,16 @@ __global__ __launch_bounds__(256) void attn_temporal_wide_kernel(
     }
 }
 
-}  // namespace
+constexpr int TEXT_HG = 5;          // heads per workgroup of attn_text_kernel
 
-extern "C" int pnc_attn_views_f16(const PncAttnParams* pp, void* stream) {
+// argument checks of pnc_attn_views_f16: PNC_OK, or the code it returns without launching
+int attn_views_check(const PncAttnParams* pp) {
     if (!pp) return PNC_EINVAL;
     const PncAttnParams& p = *pp;
     if (!p.q || !p.k || !p.vt || !p.o) return PNC_EINVAL;
     if (p.views < 1 || p.views > 8 || p.kv_views < 1 || p.kv_views > 8) return PNC_EINVAL;
     if (p.W % p.views || p.kvW % p.kv_views) return PNC_EINVAL;
-    const int kvWv = p.kvW / p.kv_views;
-    (void)kvWv;   // any view width: V^T chunks fall back to a per-key gather when a view row is not 8-aligned
+    const int kvWv = p.kvW / p.kv_views;   // any view width: V^T chunks fall back to a per-key gather when a view row is not 8-aligned
     if (p.ldq % 8 || p.ldk % 8 || p.ldo % 4) return PNC_EALIGN;
     if (((uintptr_t)p.q | (uintptr_t)p.k) & 15) return PNC_EALIGN;
     if ((uintptr_t)p.vt & 15) return PNC_EALIGN;
@@ -801,6 +806,42 @@ extern "C" int pnc_attn_views_f16(const PncAttnParams* pp, void* stream) {
             }
         }
     }
+    return PNC_OK;
+}
+
+// THE dispatch predicate (p has passed attn_views_check): true when pnc_attn_views_f16 launches attn_text_kernel for p under the
+// current options.  pnc_attn_views_f16 and pnc_attn_uses_text_kernel both ask here, nowhere else.
+// Few keys shared by all queries of a sample (the text tokens): the dedicated single-pass kernel (round 6).  PNC_OPT_ATTN_VARIANT = 43
+// forces it wherever it applies (tests), any other non-zero value keeps attn_views_kernel (A/B).
+bool attn_text_dispatch(const PncAttnParams& p) {
+    // attn_text_kernel stages V^T in 16-byte chunks of 8 keys guarded per CHUNK (kc < kvH * kvW): the key buffer must have a multiple of
+    // 8 rows (the product's 80), or the last chunk of a ragged buffer — 77 rows: keys 77 .. 79 — brings in whatever follows the V^T row,
+    // and a P of 0 does not silence a NaN or Inf read there.  Ragged buffers stay on attn_views_kernel, which tests each key.
+    const bool text_ok = p.views == 1 && p.kv_views == 1 && p.nseg[0] == 1 && p.seg[0][0] == 0 && !p.causal && p.kvH * p.kvW <= 96 &&
+                         ((p.kvH * p.kvW) & 7) == 0 && p.kv_valid > 64 && p.kv_valid <= 96 && (p.ldvt & 7) == 0 &&
+                         (p.vt_gstride & 7) == 0 && (p.ldk & 7) == 0;
+    const int force = pnc_get_option(PNC_OPT_ATTN_VARIANT);
+    const int Nq = p.H * (p.W / p.views);
+    const int nhg = (p.heads + TEXT_HG - 1) / TEXT_HG;
+    // Small per-frame grids — the 4 x 48 level: 2 query tiles x 4 head groups — stay on the smaller workgroups of attn_views_kernel.
+    // The test looks at ONE group (frame), never at the batch: a sample's eps must not depend on the batch it is evaluated in
+    // (tests/test_model_gpu.py: the CFG half alone reproduces its bits), and the two kernels round P differently.
+    const bool big_enough = (long)((Nq + 127) / 128) * nhg >= 16;
+    const int dopt = pnc_get_option(PNC_OPT_ATTN_DMA);          // bit 2: keep attn_views_kernel for these launches (whole-step A/B)
+    return text_ok && (force == 43 || (force == 0 && big_enough)) && (dopt & 3) != 0 && !(dopt & 4);
+}
+
+}  // namespace
+
+extern "C" int pnc_attn_uses_text_kernel(const PncAttnParams* pp) {
+    return attn_views_check(pp) == PNC_OK && attn_text_dispatch(*pp) ? 1 : 0;
+}
+
+extern "C" int pnc_attn_views_f16(const PncAttnParams* pp, void* stream) {
+    const int rc = attn_views_check(pp);
+    if (rc != PNC_OK) return rc;
+    const PncAttnParams& p = *pp;
+    const int kvWv = p.kvW / p.kv_views;
     const int Nq = p.H * (p.W / p.views);
     // variants: (waves, query blocks per wave) -> queries per workgroup.  Two blocks per wave: every K / V^T fragment read feeds
     // two MFMAs (600-670 TFLOP/s at level 0 vs 470-500 for 4 x 1); mid-size views: 8 x 1 (256 queries); small views: 4 x 1
@@ -816,24 +857,11 @@ extern "C" int pnc_attn_views_f16(const PncAttnParams* pp, void* stream) {
     // and MFMA phases coincide and add up; two independent workgroups drift apart and overlap them: level 0 intra 685 -> 638 us,
     // cross 1221 -> 1164, level 1 intra 111 -> 100 (same box, interleaved: profiles/round4/attn_ab_r4a.log).  force = 1: the size
     // heuristic with 82 in the place of 42 (whole-step A/B of the old choice).
-    // Few keys shared by all queries of a sample (the text tokens): the dedicated single-pass kernel (round 6).  PNC_OPT_ATTN_VARIANT = 43
-    // forces it wherever it applies (tests), any other non-zero value keeps attn_views_kernel (A/B).
-    {
-        const bool text_ok = p.views == 1 && p.kv_views == 1 && p.nseg[0] == 1 && p.seg[0][0] == 0 && !p.causal && p.kvH * p.kvW <= 96 &&
-                             p.kv_valid > 64 && p.kv_valid <= 96 && (p.ldvt & 7) == 0 && (p.vt_gstride & 7) == 0 && (p.ldk & 7) == 0;
-        constexpr int HG = 5;
-        const int nhg = (p.heads + HG - 1) / HG;
-        const long nwg = (long)((Nq + 127) / 128) * nhg * p.groups;
-        // Small per-frame grids — the 4 x 48 level: 2 query tiles x 4 head groups — stay on the smaller workgroups of attn_views_kernel.
-        // The test looks at ONE group (frame), never at the batch: a sample's eps must not depend on the batch it is evaluated in
-        // (tests/test_model_gpu.py: the CFG half alone reproduces its bits), and the two kernels round P differently.
-        const bool big_enough = (long)((Nq + 127) / 128) * nhg >= 16;
-        const int dopt = pnc_get_option(PNC_OPT_ATTN_DMA);          // bit 2: keep attn_views_kernel for these launches (whole-step A/B)
-        if (text_ok && (force == 43 || (force == 0 && big_enough)) && (dopt & 3) != 0 && !(dopt & 4)) {
-            const dim3 grid((unsigned)nwg);
-            hipLaunchKernelGGL((attn_text_kernel<HG>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, nhg);
-            return pnc_launch_status();
-        }
+    if (attn_text_dispatch(p)) {
+        const int nhg = (p.heads + TEXT_HG - 1) / TEXT_HG;
+        const dim3 grid((unsigned)((long)((Nq + 127) / 128) * nhg * p.groups));
+        hipLaunchKernelGGL((attn_text_kernel<TEXT_HG>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, nhg);
+        return pnc_launch_status();
     }
     const int big = force == 1 ? 82 : 42;
     const int variant = force >= 41 ? force : (kv_keys <= 256 ? (Nq >= 256 ? 42 : 41) : (Nq >= 512 ? big : (Nq >= 256 ? 81 : 41)));

@@ -119,6 +119,7 @@ _SIGNATURES = {
     "pnc_gemm_workspace_floats": (_L, [C.POINTER(GemmParams)]),
     "pnc_gemm_fuses_layernorm": (_I, [C.POINTER(GemmParams)]),
     "pnc_attn_views_f16": (_I, [C.POINTER(AttnParams), _P]),
+    "pnc_attn_uses_text_kernel": (_I, [C.POINTER(AttnParams)]),
     "pnc_attn_views_split_f16": (_I, [C.POINTER(AttnSplitParams), _P]),
     "pnc_attn_temporal_split_f16": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "pnc_softmax_rows_f16": (_I, [_P, _L, _I, _I, _F, _I, _I, _P, _L, _P]),
@@ -416,6 +417,19 @@ def attn_views(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H
     nkeys = sum(len(sv) for sv in segs) * kv_valid
     _check(_timed("attn_views", 4.0 * groups * heads * nq * nkeys * 64, 0.0, load().pnc_attn_views_f16,
                   C.byref(p), _stream()), "pnc_attn_views_f16")
+
+
+def attn_uses_text_kernel(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H, W, views,
+                          kvH, kvW, kv_views, kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal=False, k_halo=None, vt_halo=None) -> bool:
+    """pnc_attn_uses_text_kernel: would `attn_views` with these arguments, under the current options, launch the single-pass few-key
+    kernel?  Answered by the library's own dispatch predicate; nothing is launched."""
+    p = AttnParams()
+    if k_halo is not None:
+        for i in range(2):
+            p.k_halo[i], p.vt_halo[i] = _ptr(k_halo[i]), _ptr(vt_halo[i])
+    _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
+                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal)
+    return bool(load().pnc_attn_uses_text_kernel(C.byref(p)))
 
 
 def attn_views_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, groups, heads, H, W, views, kvH, kvW, kv_views,

@@ -70,9 +70,12 @@ def test_view_attention_chain_vs_oracle(inter, b, H, C):
     close(f"view attention inter={inter} C={C}", out.view(b, N, C), ref)
 
 
-def test_text_cross_attention_chain_vs_oracle():
-    """attention.py:229-291 with the 77 context tokens (keys padded to 80 rows, masked in the kernel)"""
-    b, T, N, C, D = 2, 2, 192, 128, 64
+@pytest.mark.parametrize("b,T,N,C,text_kernel", [(2, 2, 192, 128, False), (1, 2, 768, 768, True)])
+def test_text_cross_attention_chain_vs_oracle(b, T, N, C, text_kernel):
+    """attention.py:229-291 with the 77 context tokens (keys padded to 80 rows, masked in the kernel) — on a grid the dispatcher leaves to
+    attn_views_kernel (192 queries x 2 heads) and on one it sends to attn_text_kernel (768 queries x 12 heads: 6 query tiles x 3 head
+    groups); which of the two runs is asserted, not assumed"""
+    D = 64
     heads = C // 64
     sd = _attn_sd(C, ctx_dim=D, seed=30)
     x = r16(b * T, N, C, seed=5)
@@ -91,12 +94,14 @@ def test_text_cross_attention_chain_vs_oracle():
     hip.gemm(c16, E.pk_linear(sd["a.to_v.weight"]).to(DEV), M=b * 80, N=C, K=D, lda=D, out16=v, ldc16=C)
     vt = v.view(b, 80, C).permute(0, 2, 1).contiguous()
     o = torch.empty(M, C, device=DEV, dtype=torch.float16)
-    hip.attn_views(q, C, k, C, vt, 80, C * 80, o, C, groups=b * T, heads=heads, H=1, W=N, views=1, kvH=1, kvW=80, kv_views=1,
-                   kv_rows_per_group=80, q_per_kv=T, kv_valid=77, segs=[[0]], scale=64 ** -0.5)
+    geo = dict(groups=b * T, heads=heads, H=1, W=N, views=1, kvH=1, kvW=80, kv_views=1, kv_rows_per_group=80, q_per_kv=T, kv_valid=77,
+               segs=[[0]], scale=64 ** -0.5)
+    assert hip.attn_uses_text_kernel(q, C, k, C, vt, 80, C * 80, o, C, **geo) == text_kernel
+    hip.attn_views(q, C, k, C, vt, 80, C * 80, o, C, **geo)
     out = torch.empty(M, C, device=DEV)
     hip.gemm(o, E.pk_linear(sd["a.to_out.0.weight"]).to(DEV), M=M, N=C, K=C, lda=C, bias=dev(sd["a.to_out.0.bias"]), out32=out, ldc32=C)
     torch.cuda.synchronize()
-    close("text cross-attention", out.view(b * T, N, C), ref)
+    close(f"text cross-attention C={C}", out.view(b * T, N, C), ref)
 
 
 def test_temporal_self_attention_chain_vs_oracle():
