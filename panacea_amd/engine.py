@@ -20,7 +20,7 @@ import dataclasses
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -170,6 +170,32 @@ def precision(p) -> Precision:
     return PRECISIONS[p]
 
 
+class Operand(NamedTuple):
+    """One contraction operand as it travels from its producer to `gemm` (or an attention kernel): the fp16 plane and — when the
+    policy splits the operand's class — its lo plane, fp16 or uint8 = e4m3 bytes (Precision.lo_dtype)."""
+    hi: torch.Tensor
+    lo: Optional[torch.Tensor] = None
+
+    def map(self, fn) -> "Operand":
+        """the same view / slice / exchange of both planes"""
+        return Operand(fn(self.hi), None if self.lo is None else fn(self.lo))
+
+    def planes(self) -> list:
+        return [self.hi] if self.lo is None else [self.hi, self.lo]
+
+
+class TextKV(NamedTuple):
+    """Text keys / values of one cross-attention site (Runtime.text_kv), as flat views whose element 0 is the site's first one.
+    Keys are row-major: token r of sample b starts at element (b * TEXT_PAD + r) * ldk.  Values, fp16 policies: channel-major V^T,
+    channel c of sample b starts at b * v_gstride + c * ldv (the layout pnc_attn_views_f16 reads); a policy that splits `kv_text`:
+    row-major like the keys, ldv = ldk, v_gstride = 0 (the split attention kernels; a transposed store has no lo plane)."""
+    k: Operand
+    ldk: int
+    v: Operand
+    ldv: int
+    v_gstride: int = 0
+
+
 @dataclass
 class Act:
     """A feature map in the resident layout: [F*H*W, C] tokens, fp32 stream and/or fp16 operand."""
@@ -178,8 +204,7 @@ class Act:
     W: int
     C: int
     f32: Optional[torch.Tensor] = None
-    f16: Optional[torch.Tensor] = None
-    f16_lo: Optional[torch.Tensor] = None      # lo plane when f16 is a precise (split) operand
+    f16: Optional[Operand] = None
     gn_part: Optional[torch.Tensor] = None     # GroupNorm(32) records of f32 when its producer wrote them (engine.gn_records)
 
     @property
@@ -190,16 +215,15 @@ class Act:
     def M(self) -> int:
         return self.F * self.H * self.W
 
-    def need_f16(self, rt: "Runtime") -> torch.Tensor:
-        """fp16 operand copy of the stream (operand class `stream`: the lo plane lands in `f16_lo`)"""
+    def need_f16(self, rt: "Runtime") -> Operand:
+        """fp16 operand copy of the stream (operand class `stream`)"""
         if self.f16 is None:
-            self.f16 = rt.empty((self.M, self.C), torch.float16)
-            self.f16_lo = rt.lo_plane((self.M, self.C), "stream")
-            rt.be.cast_f16(self.f32, self.M * self.C, self.f16, self.f16_lo)
+            self.f16 = rt.operand((self.M, self.C), "stream")
+            rt.be.cast_f16(self.f32, self.M * self.C, *self.f16)
         return self.f16
 
     def to_nchw(self) -> torch.Tensor:
-        t = self.f32 if self.f32 is not None else self.f16.float()
+        t = self.f32 if self.f32 is not None else self.f16.hi.float()
         return t.view(self.F, self.H, self.W, self.C).permute(0, 3, 1, 2).contiguous()
 
 
@@ -700,11 +724,10 @@ class Runtime:
         self.F = B * self.T_local
         self.emb_all: Optional[torch.Tensor] = None    # frame-sharded runs: SiLU(emb) rows of ALL B*T frames
         self.prec: Precision = FAST                    # operand precision policy of this evaluation
-        self.ctx16: Optional[torch.Tensor] = None      # [B*TEXT_PAD, context_dim] fp16, zero padded
-        self.ctx16_lo: Optional[torch.Tensor] = None   # its lo plane when the policy splits `ctx`
+        self.ctx16: Optional[Operand] = None           # [B*TEXT_PAD, context_dim] fp16, zero padded (+ lo plane: operand class `ctx`)
         self.n_text = 77
         self.trace: Optional[Dict[str, torch.Tensor]] = None
-        self.text_kv: Dict[int, tuple] = {}            # per cross-attention site: (k, ldk, vt, ldvt, vt_gstride)
+        self.text_kv: Dict[int, TextKV] = {}           # per cross-attention site (id of its attn2)
         self.emb_proj: Dict[int, torch.Tensor] = {}    # per ResBlock3D: emb_layers(emb), [F, C] fp32 (nn.openaimodel.EmbProjector)
         self.text_frozen = False                       # text_kv / guided come from StepInvariants (sampler hoisting)
         self.guided: Optional["Act"] = None            # precomputed ControlNet hint-stem output
@@ -729,6 +752,10 @@ class Runtime:
             return None
         return self.empty(shape, self.prec.lo_dtype(cls), tail_rows)
 
+    def operand(self, shape, cls: Optional[str] = None, tail_rows: int = 0) -> Operand:
+        """an uninitialised fp16 operand of class `cls` (None: never split), with its lo plane when the policy splits that class"""
+        return Operand(self.empty(shape, torch.float16, tail_rows), self.lo_plane(shape, cls, tail_rows=tail_rows) if cls else None)
+
     def set_context(self, context: torch.Tensor):
         """context: (B, n_text, D) — tiled over T inside the reference (controlmodel.py:121-122,183-184);
         here every frame of sample b simply reads sample b's keys."""
@@ -743,13 +770,12 @@ class Runtime:
         if self.prec.ctx:
             c32 = torch.zeros((B, TEXT_PAD, D), device=self.device, dtype=torch.float32)
             c32[:, :n] = context.to(device=self.device, dtype=torch.float32)
-            self.ctx16 = self.empty((B * TEXT_PAD, D), torch.float16)
-            self.ctx16_lo = self.lo_plane((B * TEXT_PAD, D), "ctx")
-            self.be.cast_f16(c32, c32.numel(), self.ctx16, self.ctx16_lo)
+            self.ctx16 = self.operand((B * TEXT_PAD, D), "ctx")
+            self.be.cast_f16(c32, c32.numel(), *self.ctx16)
             return
         c = torch.zeros((B, TEXT_PAD, D), device=self.device, dtype=torch.float16)
         c[:, :n] = context.to(device=self.device, dtype=torch.float16)
-        self.ctx16 = c.view(B * TEXT_PAD, D)
+        self.ctx16 = Operand(c.view(B * TEXT_PAD, D))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -806,26 +832,6 @@ def pk_lo8(w16: torch.Tensor):
     return q.view(torch.uint8).contiguous(), 127 - sh
 
 
-def wlo(pk: dict, key, a_lo: Optional[torch.Tensor], w16: Optional[torch.Tensor] = None, rt: Optional["Runtime"] = None):
-    """w_lo argument of a GEMM whose A operand has the lo plane `a_lo`: the e4m3 copy of the packed weight pk[key] (or `w16`)
-    when the plane is e4m3 — packed on first use and kept in `pk` next to the fp16 weights —; the fp16 lo twin of pk[key] when the
-    plane is fp16 and the policy of `rt` splits the weights (Packable.packed_lo: built on first use; `key` may be a path, and an
-    entry that is a (weight, bias) pair gives its weight); else None"""
-    if a_lo is None:
-        return None
-    if a_lo.dtype != torch.uint8:
-        if rt is None or not rt.prec.weights:
-            return None
-        t = pk.lo()
-        for k in (key if isinstance(key, tuple) else (key,)):
-            t = t[k]
-        return t[0] if isinstance(t, tuple) else t
-    k8 = (key, "lo8")
-    if k8 not in pk:
-        pk[k8] = pk_lo8(pk[key] if w16 is None else w16)
-    return pk[k8]
-
-
 def pk_conv3x3(w: torch.Tensor, cin_pad: Optional[int] = None, lo: bool = False) -> torch.Tensor:
     """[Cout, Cin, 3, 3] -> [Cout, 9*Cin_pad].  K order (ky, kx, ci) for narrow inputs; (ci/64, ky, kx, ci%64) when
     Cin_pad % 64 == 0 (see include/panacea_hip.h: the nine taps of a 64-channel slice become adjacent K tiles)."""
@@ -875,7 +881,7 @@ def mfma_a_fragments(w16: torch.Tensor) -> torch.Tensor:
 
 
 class Packed(dict):
-    """what Packable.packed() returns: the packed copies, and the way to their lo twins (`lo()`, engine.wlo)"""
+    """what Packable.packed() returns: the packed copies, and the way to their lo twins (`lo()`, engine.gemm)"""
     owner = None
 
     def lo(self) -> dict:
@@ -911,7 +917,7 @@ class Packable:
     def packed_lo(self) -> dict:
         """`_pack(lo=True)`: the LO plane of every fp16 weight, fp16((w - fp16(w)) * 2^11) of the fp32 parameter, under the keys and
         with the permutations and padding of `packed()`; entries that are not fp16 planes are None (engine.lo_planes).  Only a
-        policy with `weights` asks for it (engine.wlo)."""
+        policy with `weights` asks for it (engine.gemm, engine.small_linear)."""
         if self._pk_lo is None:
             with torch.no_grad():
                 self._pk_lo = lo_planes(self._pack(lo=True))
@@ -952,14 +958,13 @@ def gn_records(rt: Runtime, F: int, N: int) -> Optional[torch.Tensor]:
 
 def gn_spatial(rt: Runtime, x32: torch.Tensor, F: int, N: int, C: int, gamma, beta, eps: float, silu: bool,
                split: Optional[str] = None, tail_rows: int = 0, part: Optional[torch.Tensor] = None):
-    """-> (y16, y16_lo).  `split`: the operand class of the output ("gn_stt" | "gn_res" | "gn_head"); y16_lo is None unless the
+    """-> Operand.  `split`: the operand class of the output ("gn_stt" | "gn_res" | "gn_head"); its lo plane is None unless the
     policy splits that class (precise operand for the consumer GEMM).  `tail_rows`: Runtime.empty's, for an output that feeds a
     3x3 conv of a view band.  `part`: the statistics records of x32 when its producer wrote them (`gn_records`): no statistics launch."""
     if C % 64:
         raise ValueError(f"GroupNorm(32) kernels need C % 64 == 0, got {C}")
     ppc = _ppc(N)
-    y = rt.empty((F * N, C), torch.float16, tail_rows)
-    ylo = rt.lo_plane((F * N, C), split, tail_rows=tail_rows) if split else None
+    y, ylo = out = rt.operand((F * N, C), split, tail_rows)
     if part is None:
         nrec = (N + ppc - 1) // ppc
         part = rt.empty((F * nrec * 32 * 3,), torch.float32)
@@ -991,68 +996,95 @@ def gn_spatial(rt: Runtime, x32: torch.Tensor, F: int, N: int, C: int, gamma, be
                 lt = None if ylo is None else ylo._pnc_tail[F * N + side * F * H: F * N + (side + 1) * F * H]
                 rt.be.groupnorm_apply(raw.reshape(F * H, C).contiguous(), C, F, H, C, ppc, comb, gamma, beta, eps, silu, yt, C, lt,
                                       n_records=nrec)
-        y._pnc_halo_ready = True
-        if ylo is not None:
-            ylo._pnc_halo_ready = True
-        return y, ylo
+        for pl in out.planes():
+            pl._pnc_halo_ready = True
+        return out
     if vs is not None:           # statistics of the whole panorama, not of this rank's band of views
         part = vs.combine_stats(part, F, nrec, rt.be)
     rt.be.groupnorm_apply(x32, C, F, N, C, ppc, part, gamma, beta, eps, silu, y, C, ylo, n_records=nrec)
-    return y, ylo
+    return out
 
 
-def gn_temporal(rt: Runtime, x32: torch.Tensor, N: int, C: int, gamma, beta, eps: float):
-    """-> (y16, y16_lo) (operand class `gnt`).  x32 holds ALL T frames of N pixels per sample (the resident layout, or
-    the pixel-sharded layout of a FrameShard with N = pixels per rank)."""
-    y = rt.empty((rt.B * rt.T * N, C), torch.float16)
-    ylo = rt.lo_plane((rt.B * rt.T * N, C), "gnt")
-    rt.be.groupnorm_temporal_silu(x32, rt.B, rt.T, N, C, gamma, beta, eps, y, ylo)
-    return y, ylo
+def gn_temporal(rt: Runtime, x32: torch.Tensor, N: int, C: int, gamma, beta, eps: float) -> Operand:
+    """Operand class `gnt`.  x32 holds ALL T frames of N pixels per sample (the resident layout, or the pixel-sharded layout of a
+    FrameShard with N = pixels per rank)."""
+    y = rt.operand((rt.B * rt.T * N, C), "gnt")
+    rt.be.groupnorm_temporal_silu(x32, rt.B, rt.T, N, C, gamma, beta, eps, *y)
+    return y
 
 
-def gn_temporal_sharded(rt: Runtime, sh: "FrameShard", x32: torch.Tensor, N: int, C: int, gamma, beta, eps: float):
+def gn_temporal_sharded(rt: Runtime, sh: "FrameShard", x32: torch.Tensor, N: int, C: int, gamma, beta, eps: float) -> Operand:
     """The temporal GroupNorm + SiLU of a frame-sharded run in the FRAME layout: x32 holds this rank's T_local frames of N pixels per
-    sample.  -> (y16, y16_lo) in the (T_local + 2)-frame layout of the temporal conv (PncGemmParams.t_halo), halo frames filled."""
+    sample.  -> the operand in the (T_local + 2)-frame layout of the temporal conv (PncGemmParams.t_halo), halo frames filled."""
     B, Tl = rt.B, rt.T_local
     stats = rt.empty((B * N * 64,), torch.float32)
     rt.be.groupnorm_temporal_part(x32, B, Tl, N, C, gamma, beta, eps, stats, 1, rt.T)
     sh.allreduce_sum(stats)
-    y = rt.empty((B * (Tl + 2) * N, C), torch.float16)
-    ylo = rt.lo_plane((B * (Tl + 2) * N, C), "gnt")
-    rt.be.groupnorm_temporal_part(x32, B, Tl, N, C, gamma, beta, eps, stats, 2, rt.T, y, ylo, 1)
-    sh.halo_frames([y] + ([ylo] if ylo is not None else []), B, Tl)
-    return y, ylo
-
-
-def layer_norm(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta) -> torch.Tensor:
-    y = rt.empty((M, C), torch.float16)
-    rt.be.layernorm(x32, C, M, C, gamma, beta, 1e-5, y, C)
+    y = rt.operand((B * (Tl + 2) * N, C), "gnt")
+    rt.be.groupnorm_temporal_part(x32, B, Tl, N, C, gamma, beta, eps, stats, 2, rt.T, y.hi, y.lo, 1)
+    sh.halo_frames(y.planes(), B, Tl)
     return y
 
 
-def layer_norm_split(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta):
-    """-> (y16, y16_lo): LayerNorm with the lo plane of operand class `ln` (None unless the policy splits it)"""
-    y = rt.empty((M, C), torch.float16)
-    ylo = rt.lo_plane((M, C), "ln")
-    rt.be.layernorm(x32, C, M, C, gamma, beta, 1e-5, y, C, ylo)
-    return y, ylo
+def layer_norm(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta) -> Operand:
+    """operand class `ln`"""
+    y = rt.operand((M, C), "ln")
+    rt.be.layernorm(x32, C, M, C, gamma, beta, 1e-5, y.hi, C, y.lo)
+    return y
 
 
-def small_linear(rt: Runtime, a32: torch.Tensor, w16: torch.Tensor, bias, M: int, N: int, K: int,
-                 silu_in=False, silu_out=False, w_lo: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp32-activation linear for the (frames x 1280) time-embedding path; rows in chunks of 16.  `w_lo`: the lo twin of w16
-    under a policy that splits the weights (the kernel joins the pair in fp32)."""
+def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_lo=None, **kw):
+    """THE launch of a GEMM on an operand: a @ W^T with the epilogue `kw` (the keywords of the backend's `gemm`), fp16 output into
+    `out`.  W = pk[key]; `key` may be a path into `pk` (a tuple), and an entry that is a (weight, bias) pair gives both.  What goes
+    with the planes of `a` and `out` is decided here and nowhere else:
+      a.lo is e4m3   the e4m3 copy of W for the lo pass (pk_lo8), packed on first use and kept in `pk` next to the fp16 weights;
+      a.lo is fp16   the fp16 lo twin of W when the policy splits the weights (Packable.packed_lo, built on first use), else nothing;
+      no a.lo        nothing.
+    `key=None`: `pk` is W itself, a stacked matrix that is no Packable's (TextKVProjector, EmbProjector), and `w_lo` its lo twin — used
+    under the same conditions as a module's."""
+    w = pk
+    if key is not None:
+        for k in key if isinstance(key, tuple) else (key,):
+            w = w[k]
+        if isinstance(w, tuple):
+            w, b = w
+            if kw.get("bias") is None:
+                kw["bias"] = b
+    if a.lo is None:
+        w_lo = None
+    elif a.lo.dtype == torch.uint8:
+        k8 = (key, "lo8")
+        if k8 not in pk:
+            pk[k8] = pk_lo8(w)
+        w_lo = pk[k8]
+    elif not rt.prec.weights:
+        w_lo = None
+    elif key is not None:
+        w_lo = _lo_twin(pk, key)
+    if out is not None:
+        kw["out16"] = out.hi
+        if out.lo is not None:
+            kw["out16_lo"] = out.lo
+    rt.be.gemm(a.hi, w, a16_lo=a.lo, w_lo=w_lo, **kw)
+
+
+def _lo_twin(pk: "Packed", key) -> torch.Tensor:
+    t = pk.lo()
+    for k in key if isinstance(key, tuple) else (key,):
+        t = t[k]
+    return t[0] if isinstance(t, tuple) else t
+
+
+def small_linear(rt: Runtime, a32: torch.Tensor, pk: "Packed", wkey, bkey, M: int, N: int, K: int,
+                 silu_in=False, silu_out=False) -> torch.Tensor:
+    """fp32-activation linear pk[wkey], pk[bkey] for the (frames x 1280) time-embedding path; rows in chunks of 16.  Under a policy
+    that splits the weights the kernel joins pk[wkey] with its lo twin in fp32."""
     out = rt.empty((M, N), torch.float32)
-    kw = {} if w_lo is None else dict(w_lo=w_lo)
+    kw = dict(w_lo=_lo_twin(pk, wkey)) if rt.prec.weights else {}
     for m0 in range(0, M, 16):
         mm = min(16, M - m0)
-        rt.be.linear_smallm(a32[m0:], K, w16, bias, out[m0:], N, mm, N, K, silu_in, silu_out, **kw)
+        rt.be.linear_smallm(a32[m0:], K, pk[wkey], pk[bkey], out[m0:], N, mm, N, K, silu_in, silu_out, **kw)
     return out
-
-
-def wlo32(pk: dict, key, rt: Runtime) -> Optional[torch.Tensor]:
-    """lo twin of the packed weight pk[key] of an fp32-activation linear (small_linear), or None unless the policy splits the weights"""
-    return pk.lo()[key] if rt.prec.weights else None
 
 
 _FREQS: Dict[tuple, torch.Tensor] = {}

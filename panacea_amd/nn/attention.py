@@ -82,38 +82,28 @@ class FeedForward(nn.Module, Packable):
         w1, b1 = E.pk_geglu(self.net[0].proj.weight, self.net[0].proj.bias, lo)
         return dict(w1=w1, b1=b1, w2=E.pk_linear(self.net[2].weight, lo), b2=E.pk_f32(self.net[2].bias))
 
-    def _run(self, rt: Runtime, x16, M, res32, out32=None, out16=None, out16_lo=None, x16_lo=None):
-        """out = FF(x16) + res32 -> out32 (may alias res32) and/or out16 (+ lo plane of a precise operand).  `x16_lo`: lo plane
-        of the input (operand class `ln`); the GEGLU hidden state is split when the policy splits `ff_hidden`."""
+    def _run(self, rt: Runtime, x: E.Operand, M, res32, out32=None, out: Optional[E.Operand] = None):
+        """FF(x) + res32 -> out32 (may alias res32) and/or the fp16 operand `out`.  The GEGLU hidden state is an operand of class
+        `ff_hidden`."""
         pk = self.packed()
-        hid = rt.empty((M, self.inner_dim), torch.float16)
-        hid_lo = rt.lo_plane((M, self.inner_dim), "ff_hidden")
-        wide = {} if x16_lo is None else dict(a16_lo=x16_lo, w_lo=E.wlo(pk, "w1", x16_lo, rt=rt))
-        rt.be.gemm(x16, pk["w1"], M=M, N=2 * self.inner_dim, K=self.dim, lda=self.dim, bias=pk["b1"],
-                   geglu=True, out16=hid, ldc16=self.inner_dim, **wide, **({} if hid_lo is None else dict(out16_lo=hid_lo)))
-        wide = {} if hid_lo is None else dict(a16_lo=hid_lo, w_lo=E.wlo(pk, "w2", hid_lo, rt=rt))
-        rt.be.gemm(hid, pk["w2"], M=M, N=self.dim_out, K=self.inner_dim, lda=self.inner_dim, bias=pk["b2"],
-                   res1=res32, ldr1=self.dim_out, out32=out32, ldc32=self.dim_out, out16=out16,
-                   ldc16=self.dim_out, out16_lo=out16_lo, **wide)
+        hid = rt.operand((M, self.inner_dim), "ff_hidden")
+        E.gemm(rt, x, pk, "w1", hid, M=M, N=2 * self.inner_dim, K=self.dim, lda=self.dim, bias=pk["b1"], geglu=True,
+               ldc16=self.inner_dim)
+        E.gemm(rt, hid, pk, "w2", out, M=M, N=self.dim_out, K=self.inner_dim, lda=self.inner_dim, bias=pk["b2"],
+               res1=res32, ldr1=self.dim_out, out32=out32, ldc32=self.dim_out, ldc16=self.dim_out)
 
 
-def _ln_kwargs(rt: Runtime, ln, M: int, C: int):
-    """kwargs that make a GEMM also write LayerNorm(out32 rows) as fp16 (PncGemmParams.ln_*): fused into the epilogue where
-    a workgroup owns whole rows (level 0), the library's LayerNorm kernel right after the GEMM otherwise.  -> (kwargs, x16)"""
-    if ln is None or rt.prec.ln:         # (a split LayerNorm output: the standalone kernel writes its lo plane, `_ln_after`)
-        return {}, None
-    x16 = rt.empty((M, C), torch.float16)
-    return dict(ln_gamma=ln[0], ln_beta=ln[1], ln_out16=x16, ldln=C, ln_eps=1e-5), x16
-
-
-def _ln_after(rt: Runtime, ln, t32, M: int, C: int, y16):
-    """-> (y16, y16_lo) of the LayerNorm that follows a residual GEMM: what the GEMM wrote (`_ln_kwargs`), or — the policy splits
-    `ln`: the fused-LayerNorm epilogue has no lo plane — the standalone LayerNorm kernel with its lo plane"""
-    if ln is None:
-        return None, None
-    if rt.prec.ln:
-        return E.layer_norm_split(rt, t32, M, C, ln[0], ln[1])
-    return y16, None
+def _gemm_ln(rt: Runtime, a: E.Operand, pk, key, ln, M: int, C: int, out32, **kw) -> Optional[E.Operand]:
+    """GEMM into the fp32 rows out32 [M, C], then y = LayerNorm(out32 rows) with `ln` = (gamma, beta) -> y (None: no LayerNorm
+    follows).  The GEMM writes y itself (PncGemmParams.ln_*: fused into the epilogue where a workgroup owns whole rows, the library's
+    LayerNorm kernel right after the GEMM otherwise) unless the policy splits `ln`: that epilogue has no lo plane, the standalone
+    kernel writes one."""
+    if ln is None or rt.prec.ln:
+        E.gemm(rt, a, pk, key, M=M, N=C, out32=out32, ldc32=C, **kw)
+        return None if ln is None else E.layer_norm(rt, out32, M, C, *ln)
+    y = rt.operand((M, C))
+    E.gemm(rt, a, pk, key, M=M, N=C, out32=out32, ldc32=C, ln_gamma=ln[0], ln_beta=ln[1], ln_out16=y.hi, ldln=C, ln_eps=1e-5, **kw)
+    return y
 
 
 class _AttentionBase(nn.Module, Packable):
@@ -144,81 +134,54 @@ class _AttentionBase(nn.Module, Packable):
         else:
             pk["wq"], pk["wk"], pk["wv"] = (E.pk_linear(self.to_q.weight, lo), E.pk_linear(self.to_k.weight, lo),
                                             E.pk_linear(self.to_v.weight, lo))
+            pk["wkv"] = torch.cat([pk["wk"], pk["wv"]])         # [W_k; W_v]: one GEMM under a policy that splits `kv_text`
         return pk
 
     # ---- text cross-attention: x16 [M, C] queries of F frames vs the 77 context tokens of each sample
-    def _text_kv(self, rt: Runtime):
-        """(k, ldk, vt, ldvt, vt_gstride) of this site.  The network projects the text keys/values of ALL its
-        cross-attention sites of one width in two GEMMs up front (`project_text_kv`); a module used on its own
-        projects its own."""
+    def _text_kv(self, rt: Runtime) -> E.TextKV:
+        """The network projects the text keys/values of ALL its cross-attention sites in one GEMM up front (TextKVProjector); a
+        module used on its own projects its own."""
         hit = rt.text_kv.get(id(self))
         if hit is not None:
             return hit
         pk = self.packed()
-        C, D, rows = self.inner_dim, rt.ctx16.shape[1], rt.B * E.TEXT_PAD
+        C, D, rows = self.inner_dim, rt.ctx16.hi.shape[1], rt.B * E.TEXT_PAD
         if rt.prec.kv_text:
-            # split policy: K and V row-major with their lo planes, one [rows, 2C] block -> (k, k_lo, v, v_lo, ld)
-            kv, kv_lo = rt.empty((rows, 2 * C), torch.float16), rt.lo_plane((rows, 2 * C), "kv_text")
-            if "wkv" not in pk:                       # [W_k; W_v], packed once next to them
-                pk["wkv"] = torch.cat([pk["wk"], pk["wv"]]).contiguous()
-            if rt.prec.weights and "wkv" not in pk.lo():
-                pk.lo()["wkv"] = torch.cat([pk.lo()["wk"], pk.lo()["wv"]]).contiguous()
-            rt.be.gemm(rt.ctx16, pk["wkv"], M=rows, N=2 * C, K=D, lda=D, out16=kv, ldc16=2 * C, out16_lo=kv_lo, a16_lo=rt.ctx16_lo,
-                       w_lo=E.wlo(pk, "wkv", rt.ctx16_lo, rt=rt))
-            f, fl = kv.view(-1), kv_lo.view(-1)
-            return f, fl, f[C:], fl[C:], 2 * C
-        k = rt.empty((rows, C), torch.float16)
+            # split policy: K and V row-major with their lo planes, one [rows, 2C] block
+            kv = rt.operand((rows, 2 * C), "kv_text")
+            E.gemm(rt, rt.ctx16, pk, "wkv", kv, M=rows, N=2 * C, K=D, lda=D, ldc16=2 * C)
+            kv = kv.map(lambda t: t.view(-1))
+            return E.TextKV(kv, 2 * C, kv.map(lambda t: t[C:]), 2 * C)
+        k = rt.operand((rows, C))
         vt = rt.empty((rt.B, C, E.TEXT_PAD), torch.float16)
-        rt.be.gemm(rt.ctx16, pk["wk"], M=rows, N=C, K=D, lda=D, out16=k, ldc16=C)
-        rt.be.gemm(rt.ctx16, pk["wv"], M=rows, N=C, K=D, lda=D, out16t=vt, ldt=E.TEXT_PAD, t_rows=E.TEXT_PAD,
-                   t_gstride=C * E.TEXT_PAD, n_split=0)
-        return k, C, vt, E.TEXT_PAD, C * E.TEXT_PAD
+        E.gemm(rt, rt.ctx16, pk, "wk", k, M=rows, N=C, K=D, lda=D, ldc16=C)
+        E.gemm(rt, rt.ctx16, pk, "wv", M=rows, N=C, K=D, lda=D, out16t=vt, ldt=E.TEXT_PAD, t_rows=E.TEXT_PAD,
+               t_gstride=C * E.TEXT_PAD, n_split=0)
+        return E.TextKV(k, C, E.Operand(vt), E.TEXT_PAD, C * E.TEXT_PAD)
 
-    def _run_text(self, rt: Runtime, x16, F, H, W, res32, out32, ln=None, x16_lo=None):
-        """`ln` = (gamma, beta) of the LayerNorm that follows the residual add: its fp16 output (hi, lo) is returned"""
-        pk = self.packed()
+    def _run_text(self, rt: Runtime, x: E.Operand, F, H, W, res32, out32, ln=None) -> Optional[E.Operand]:
+        """`ln` = (gamma, beta) of the LayerNorm that follows the residual add: its fp16 output is returned"""
         C, M = self.inner_dim, F * H * W
+        q = rt.operand((M, C), "q_text")
+        E.gemm(rt, x, self.packed(), "wq", q, M=M, N=C, K=self.query_dim, lda=self.query_dim, ldc16=C)
+        kv = self._text_kv(rt)
+        o = rt.operand((M, C), "attn_o")
+        geo = dict(groups=F, heads=self.heads, H=H, W=W, views=1, kvH=1, kvW=E.TEXT_PAD, kv_views=1, kv_rows_per_group=E.TEXT_PAD,
+                   q_per_kv=F // rt.B, kv_valid=rt.n_text, segs=[[0]], scale=self.scale)
         if rt.prec.q_text:
-            q, q_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "q_text")
-            rt.be.gemm(x16, pk["wq"], M=M, N=C, K=self.query_dim, lda=self.query_dim, out16=q, ldc16=C, out16_lo=q_lo, a16_lo=x16_lo,
-                       w_lo=E.wlo(pk, "wq", x16_lo, rt=rt))
-            k, k_lo, v, v_lo, ld = self._text_kv(rt)
-            o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
-            rt.be.attn_views_split(q, q_lo, C, k, k_lo, ld, v, v_lo, ld, o, o_lo, C, groups=F, heads=self.heads, H=H, W=W,
-                                   views=1, kvH=1, kvW=E.TEXT_PAD, kv_views=1, kv_rows_per_group=E.TEXT_PAD, q_per_kv=F // rt.B,
-                                   kv_valid=rt.n_text, segs=[[0]], scale=self.scale)
-            return self._out_proj(rt, o, o_lo, M, C, res32, out32, ln)
-        q = rt.empty((M, C), torch.float16)
-        rt.be.gemm(x16, pk["wq"], M=M, N=C, K=self.query_dim, lda=self.query_dim, out16=q, ldc16=C)
-        k, ldk, vt, ldvt, vt_gs = self._text_kv(rt)
-        o = rt.empty((M, C), torch.float16)
-        rt.be.attn_views(q, C, k, ldk, vt, ldvt, vt_gs, o, C, groups=F, heads=self.heads, H=H, W=W,
-                         views=1, kvH=1, kvW=E.TEXT_PAD, kv_views=1, kv_rows_per_group=E.TEXT_PAD,
-                         q_per_kv=F // rt.B, kv_valid=rt.n_text, segs=[[0]], scale=self.scale)
-        lnkw, y16 = _ln_kwargs(rt, ln, M, self.query_dim)
-        rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32,
-                   ldr1=self.query_dim, out32=out32, ldc32=self.query_dim, **lnkw)
-        return y16, None
+            rt.be.attn_views_split(q.hi, q.lo, C, kv.k.hi, kv.k.lo, kv.ldk, kv.v.hi, kv.v.lo, kv.ldv, o.hi, o.lo, C, **geo)
+        else:
+            rt.be.attn_views(q.hi, C, kv.k.hi, kv.ldk, kv.v.hi, kv.ldv, kv.v_gstride, o.hi, C, **geo)
+        return self._out_proj(rt, o, M, res32, out32, ln)
 
-    def _out_proj(self, rt: Runtime, o, o_lo, M, C, res32, out32, ln):
-        """split policy: to_out(o) + res on the split attention output, then the LayerNorm that follows -> (y16, y16_lo)"""
+    def _out_proj(self, rt: Runtime, o: E.Operand, M, res32, out32, ln) -> Optional[E.Operand]:
+        """to_out(o) + res32 -> out32, then the LayerNorm `ln` that follows -> its fp16 output (`_gemm_ln`)"""
         pk = self.packed()
-        rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32, ldr1=self.query_dim, out32=out32,
-                   ldc32=self.query_dim, a16_lo=o_lo, w_lo=E.wlo(pk, "wo", o_lo, rt=rt))
-        return _ln_after(rt, ln, out32, M, self.query_dim, None)
-
-    def _qkv_split(self, rt: Runtime, x16, x16_lo, M):
-        """split policy: the fused QKV GEMM into ONE row-major [M, 3C] block + lo plane (the split attention kernels read V
-        row-major: the transposed V^T store of the fp16 path has no lo plane) -> (qkv, qkv_lo)"""
-        pk = self.packed()
-        C = self.inner_dim
-        qkv, qkv_lo = rt.empty((M, 3 * C), torch.float16), rt.lo_plane((M, 3 * C), "qkv")
-        rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qkv, ldc16=3 * C, out16_lo=qkv_lo,
-                   a16_lo=x16_lo, w_lo=E.wlo(pk, "wqkv", x16_lo, rt=rt))
-        return qkv.view(-1), qkv_lo.view(-1)
+        return _gemm_ln(rt, o, pk, "wo", ln, M, self.query_dim, out32, K=self.inner_dim, lda=self.inner_dim, bias=pk["bo"],
+                        res1=res32, ldr1=self.query_dim)
 
     # ---- spatial self-attention over width-sliced views (views = 1: plain attention)
-    def _run_views(self, rt: Runtime, x16, F, H, W, segs, res32, out32, ln=None, x16_lo=None):
+    def _run_views(self, rt: Runtime, x: E.Operand, F, H, W, segs, res32, out32, ln=None) -> Optional[E.Operand]:
         pk = self.packed()
         C, N = self.inner_dim, H * W
         M = F * N
@@ -226,62 +189,49 @@ class _AttentionBase(nn.Module, Packable):
         views = vs.n_local if vs is not None else len(segs)
         if W % views:
             raise ValueError(f"grid width {W} is not divisible into {views} views")
+        geo = dict(groups=F, heads=self.heads, H=H, W=W, views=views, kvH=H, kvW=W, kv_views=views, kv_rows_per_group=N, q_per_kv=1,
+                   kv_valid=H * (W // views), scale=self.scale)
+        qkv = dict(M=M, N=3 * C, K=self.query_dim, lda=self.query_dim)
+        o = rt.operand((M, C), "attn_o")
         if rt.prec.qkv:
             if rt.vshard is not None:
                 raise ValueError("the precise-wide operand policy does not run view-sharded")
-            f, fl = self._qkv_split(rt, x16, x16_lo, M)
-            o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
-            rt.be.attn_views_split(f, fl, 3 * C, f[C:], fl[C:], 3 * C, f[2 * C:], fl[2 * C:], 3 * C, o, o_lo, C, groups=F,
-                                   heads=self.heads, H=H, W=W, views=views, kvH=H, kvW=W, kv_views=views, kv_rows_per_group=N,
-                                   q_per_kv=1, kv_valid=H * (W // views), segs=segs, scale=self.scale)
-            return self._out_proj(rt, o, o_lo, M, C, res32, out32, ln)
-        qk = rt.empty((M, 2 * C), torch.float16)
-        vt = rt.empty((F, C, N), torch.float16)
-        rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qk, ldc16=2 * C,
-                   out16t=vt, ldt=N, t_rows=N, t_gstride=C * N, n_split=2 * C)
-        o = rt.empty((M, C), torch.float16)
-        Wv = W // views
-        if vs is not None and any(u != v for v, row in enumerate(segs) for u in row):
-            # this rank's band of views attends its neighbours' edge views too.  Round 5: the band's keys / values stay where the
-            # QKV GEMM wrote them; the two neighbour views arrive in halo buffers of the band's geometry (PncAttnParams.k_halo) —
-            # rounds 3-4 concatenated keys and values of n_local + 2 views (4.5 ms per evaluation at G = 1)
-            k_halo, vt_halo = vs.halo_views(rt, qk.view(F, H, W, 2 * C)[..., C:], vt.view(F, C, H, W), M, 2 * C, C)
-            rt.be.attn_views(qk, 2 * C, qk.view(-1)[C:], 2 * C, vt, N, C * N, o, C, groups=F, heads=self.heads,
-                             H=H, W=W, views=views, kvH=H, kvW=W, kv_views=views, kv_rows_per_group=N, q_per_kv=1,
-                             kv_valid=H * Wv, segs=vs.local_segments(segs, halo_ids=True), scale=self.scale,
-                             k_halo=k_halo, vt_halo=vt_halo)
+            # ONE row-major [M, 3C] block + lo plane: the split attention kernels read V row-major (the transposed V^T store of the
+            # fp16 path has no lo plane)
+            t = rt.operand((M, 3 * C), "qkv")
+            E.gemm(rt, x, pk, "wqkv", t, ldc16=3 * C, **qkv)
+            f, fl = t.map(lambda p: p.view(-1))
+            rt.be.attn_views_split(f, fl, 3 * C, f[C:], fl[C:], 3 * C, f[2 * C:], fl[2 * C:], 3 * C, o.hi, o.lo, C, segs=segs, **geo)
         else:
-            if vs is not None:
+            qk = rt.empty((M, 2 * C), torch.float16)
+            vt = rt.empty((F, C, N), torch.float16)
+            E.gemm(rt, x, pk, "wqkv", E.Operand(qk), ldc16=2 * C, out16t=vt, ldt=N, t_rows=N, t_gstride=C * N, n_split=2 * C, **qkv)
+            halo = {}
+            if vs is not None and any(u != v for v, row in enumerate(segs) for u in row):
+                # this rank's band of views attends its neighbours' edge views too.  Round 5: the band's keys / values stay where the
+                # QKV GEMM wrote them; the two neighbour views arrive in halo buffers of the band's geometry (PncAttnParams.k_halo) —
+                # rounds 3-4 concatenated keys and values of n_local + 2 views (4.5 ms per evaluation at G = 1)
+                k_halo, vt_halo = vs.halo_views(rt, qk.view(F, H, W, 2 * C)[..., C:], vt.view(F, C, H, W), M, 2 * C, C)
+                segs, halo = vs.local_segments(segs, halo_ids=True), dict(k_halo=k_halo, vt_halo=vt_halo)
+            elif vs is not None:
                 segs = [[i] for i in range(views)]
-            rt.be.attn_views(qk, 2 * C, qk.view(-1)[C:], 2 * C, vt, N, C * N, o, C, groups=F, heads=self.heads,
-                             H=H, W=W, views=views, kvH=H, kvW=W, kv_views=views, kv_rows_per_group=N, q_per_kv=1,
-                             kv_valid=H * Wv, segs=segs, scale=self.scale)
-        lnkw, y16 = _ln_kwargs(rt, ln, M, self.query_dim)
-        rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32,
-                   ldr1=self.query_dim, out32=out32, ldc32=self.query_dim, **lnkw)
-        return y16, None
+            rt.be.attn_views(qk, 2 * C, qk.view(-1)[C:], 2 * C, vt, N, C * N, o.hi, C, segs=segs, **geo, **halo)
+        return self._out_proj(rt, o, M, res32, out32, ln)
 
     # ---- temporal self-attention over the T frames of each pixel
-    def _run_temporal(self, rt: Runtime, x16, N, res32, out32, ln=None, x16_lo=None):
-        pk = self.packed()
+    def _run_temporal(self, rt: Runtime, x: E.Operand, N, res32, out32, ln=None) -> Optional[E.Operand]:
         C = self.inner_dim
         M = rt.B * rt.T * N              # all T frames of N pixels per sample (N = pixels per rank when frame-sharded)
+        qkv = rt.operand((M, 3 * C), "qkv")
+        E.gemm(rt, x, self.packed(), "wqkv", qkv, M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, ldc16=3 * C)
+        o = rt.operand((M, C), "attn_o")
+        f, fl = qkv.map(lambda p: p.view(-1))
+        geo = dict(B=rt.B, T=rt.T, Npix=N, heads=self.heads, scale=self.scale)
         if rt.prec.qkv:
-            f, fl = self._qkv_split(rt, x16, x16_lo, M)
-            o, o_lo = rt.empty((M, C), torch.float16), rt.lo_plane((M, C), "attn_o")
-            rt.be.attn_temporal_split(f, fl, 3 * C, f[C:], fl[C:], 3 * C, f[2 * C:], fl[2 * C:], 3 * C, o, o_lo, C, B=rt.B, T=rt.T,
-                                      Npix=N, heads=self.heads, scale=self.scale)
-            return self._out_proj(rt, o, o_lo, M, C, res32, out32, ln)
-        qkv = rt.empty((M, 3 * C), torch.float16)
-        rt.be.gemm(x16, pk["wqkv"], M=M, N=3 * C, K=self.query_dim, lda=self.query_dim, out16=qkv, ldc16=3 * C)
-        o = rt.empty((M, C), torch.float16)
-        flat = qkv.view(-1)
-        rt.be.attn_temporal(flat, 3 * C, flat[C:], 3 * C, flat[2 * C:], 3 * C, o, C, B=rt.B, T=rt.T, Npix=N,
-                            heads=self.heads, scale=self.scale)
-        lnkw, y16 = _ln_kwargs(rt, ln, M, self.query_dim)
-        rt.be.gemm(o, pk["wo"], M=M, N=self.query_dim, K=C, lda=C, bias=pk["bo"], res1=res32,
-                   ldr1=self.query_dim, out32=out32, ldc32=self.query_dim, **lnkw)
-        return y16, None
+            rt.be.attn_temporal_split(f, fl, 3 * C, f[C:], fl[C:], 3 * C, f[2 * C:], fl[2 * C:], 3 * C, o.hi, o.lo, C, **geo)
+        else:
+            rt.be.attn_temporal(f, 3 * C, f[C:], 3 * C, f[2 * C:], 3 * C, o.hi, C, **geo)
+        return self._out_proj(rt, o, M, res32, out32, ln)
 
 
 class CrossAttention(_AttentionBase):
@@ -346,40 +296,31 @@ class BasicTransformerBlock(nn.Module, Packable):
         pk = self.packed()
         return pk["norm1w"], pk["norm1b"]
 
-    def _run(self, rt: Runtime, t32, F, H, W, branch: str, last: bool, x16=None, x16_lo=None):
-        """t32 [M, dim] fp32 stream, updated in place; returns the fp16 copy (hi, lo) of the final x when `last`
-        (operand class `ff_out`).  `x16`: norm1(t32) when the GEMM that produced t32 has already written it.  norm2 / norm3
-        are written by the residual GEMMs that precede them (PncGemmParams.ln_*), not by LayerNorm launches of their own."""
+    def _run(self, rt: Runtime, t32, F, H, W, branch: str, last: bool, x: Optional[E.Operand] = None) -> Optional[E.Operand]:
+        """t32 [M, dim] fp32 stream, updated in place; returns the fp16 copy of the final x when `last` (operand class `ff_out`).
+        `x`: norm1(t32) when the GEMM that produced t32 has already written it.  norm2 / norm3 come with the residual GEMMs that
+        precede them (`_gemm_ln`)."""
         pk = self.packed()
         C, N = self.dim, H * W
         M = F * N
-        if x16 is None:
-            if rt.prec.ln:
-                x16, x16_lo = E.layer_norm_split(rt, t32, M, C, pk["norm1w"], pk["norm1b"])
-            else:
-                x16 = E.layer_norm(rt, t32, M, C, pk["norm1w"], pk["norm1b"])
+        if x is None:
+            x = E.layer_norm(rt, t32, M, C, pk["norm1w"], pk["norm1b"])
         ln2, ln3 = (pk["norm2w"], pk["norm2b"]), (pk["norm3w"], pk["norm3b"])
         nviews = rt.vshard.n_local if rt.vshard is not None else 6
         if branch == "temporal":
-            x16, x16_lo = self.attn1._run_temporal(rt, x16, N, t32, t32, ln=ln2, x16_lo=x16_lo)
-        elif self.attn1.kind == "intra-view":
+            x = self.attn1._run_temporal(rt, x, N, t32, t32, ln=ln2)
+        elif self.attn1.kind in ("intra-view", "inter-view"):
             ph, pw = panorama_grid(N, nviews)
-            x16, x16_lo = self.attn1._run_views(rt, x16, F, ph, pw, INTRA_SEGS, t32, t32, ln=ln2, x16_lo=x16_lo)
-        elif self.attn1.kind == "inter-view":
-            ph, pw = panorama_grid(N, nviews)
-            x16, x16_lo = self.attn1._run_views(rt, x16, F, ph, pw, INTER_SEGS, t32, t32, ln=ln2, x16_lo=x16_lo)
+            x = self.attn1._run_views(rt, x, F, ph, pw, INTRA_SEGS if self.attn1.kind == "intra-view" else INTER_SEGS, t32, t32, ln=ln2)
         else:
             if rt.vshard is not None:
                 raise NotImplementedError("plain spatial self-attention spans the whole panorama; a view shard serves the "
                                           "intra-view / inter-view kinds")
-            x16, x16_lo = self.attn1._run_views(rt, x16, F, H, W, [[0]], t32, t32, ln=ln2, x16_lo=x16_lo)
-        x16, x16_lo = self.attn2._run_text(rt, x16, F, H, W, t32, t32, ln=ln3, x16_lo=x16_lo)
-        out16 = out16lo = None
-        if last:
-            out16 = rt.empty((M, C), torch.float16)
-            out16lo = rt.lo_plane((M, C), "ff_out")
-        self.ff._run(rt, x16, M, t32, out32=None if last else t32, out16=out16, out16_lo=out16lo, x16_lo=x16_lo)
-        return (out16, out16lo) if last else None
+            x = self.attn1._run_views(rt, x, F, H, W, [[0]], t32, t32, ln=ln2)
+        x = self.attn2._run_text(rt, x, F, H, W, t32, t32, ln=ln3)
+        out = rt.operand((M, C), "ff_out") if last else None
+        self.ff._run(rt, x, M, t32, out32=None if last else t32, out=out)
+        return out
 
 
 class SpatialTemporalTransformer(nn.Module, Packable):
@@ -448,43 +389,33 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         pk["pos"] = E.temporal_pos_table(self.num_frames, self.inner_dim).to(self.proj_in.weight.device)
         return pk
 
-    def _branch(self, rt: Runtime, x: Act, sfx: str, blocks, branch: str, out16=None, out16_lo=None):
+    def _branch(self, rt: Runtime, x: Act, sfx: str, blocks, branch: str, out: Optional[E.Operand] = None):
         pk = self.packed()
         C, M = x.C, x.M
-        n16, n16lo = E.gn_spatial(rt, x.f32, x.F, x.N, C, pk["g" + sfx], pk["b" + sfx], 1e-6, False,
-                                  split="gn_stt", part=x.gn_part)
+        n = E.gn_spatial(rt, x.f32, x.F, x.N, C, pk["g" + sfx], pk["b" + sfx], 1e-6, False, split="gn_stt", part=x.gn_part)
         x.gn_part = None             # (the branches update x.f32 in place: the producer's records describe the first branch's input only)
         sh = rt.shard if branch == "temporal" else None
         if sh is not None:
             # Frame-sharded run: the temporal branch is pointwise per pixel (LN, projections, text cross-attention, FF) or
             # couples the T frames of ONE pixel (temporal self-attention), so it runs on all T frames of N/G pixels.
             # Exchanged: the GroupNorm output going in, the last block's fp16 output coming back (fp16 planes only).
-            n16, n16lo = sh.to_pixels_planes([n16, n16lo], rt.B, x.N)       # (hi + lo plane in ONE exchange: round 6)
+            n = E.Operand(*sh.to_pixels_planes(list(n), rt.B, x.N))       # (hi + lo plane in ONE exchange: round 6)
             Fb, Hb, Wb = rt.B * rt.T, 1, x.N // sh.G
         else:
             Fb, Hb, Wb = x.F, x.H, x.W
         Mb = Fb * Hb * Wb
         t32 = rt.empty((Mb, C), torch.float32)
-        lnkw, x16 = _ln_kwargs(rt, blocks[0].norm1_params(), Mb, C)          # norm1 of the first block rides on proj_in
-        # (split `ln`: no fused LayerNorm; the first block runs its own with the lo plane)
-        if branch == "temporal":
-            # + position table indexed by t = frame % T (attention.py:1117-1118)
-            rt.be.gemm(n16, pk["wi" + sfx], M=Mb, N=C, K=C, lda=C, bias=pk["bi" + sfx], rowbias=pk["pos"],
-                       rb_rows=Hb * Wb, rb_mod=rt.T, out32=t32, ldc32=C, a16_lo=n16lo, w_lo=E.wlo(pk, "wi" + sfx, n16lo, rt=rt), **lnkw)
-        else:
-            rt.be.gemm(n16, pk["wi" + sfx], M=Mb, N=C, K=C, lda=C, bias=pk["bi" + sfx], out32=t32, ldc32=C,
-                       a16_lo=n16lo, w_lo=E.wlo(pk, "wi" + sfx, n16lo, rt=rt), **lnkw)
-        p16 = p16lo = None
+        # + position table indexed by t = frame % T (attention.py:1117-1118)
+        pos = dict(rowbias=pk["pos"], rb_rows=Hb * Wb, rb_mod=rt.T) if branch == "temporal" else {}
+        # norm1 of the first block rides on proj_in
+        p = _gemm_ln(rt, n, pk, "wi" + sfx, blocks[0].norm1_params(), Mb, C, t32, K=C, lda=C, bias=pk["bi" + sfx], **pos)
         for i, blk in enumerate(blocks):
-            r = blk._run(rt, t32, Fb, Hb, Wb, branch, last=(i == len(blocks) - 1), x16=x16 if i == 0 else None)
-            if r is not None:
-                p16, p16lo = r
+            p = blk._run(rt, t32, Fb, Hb, Wb, branch, last=(i == len(blocks) - 1), x=p)
         if sh is not None:
-            p16, p16lo = sh.to_frames_planes([p16, p16lo], rt.B, x.N)
+            p = E.Operand(*sh.to_frames_planes(list(p), rt.B, x.N))
         # x = proj_out(t) + x_in, in place on the stream
-        rt.be.gemm(p16, pk["wo" + sfx], M=M, N=C, K=C, lda=C, bias=pk["bo" + sfx], res1=x.f32, ldr1=C,
-                   out32=x.f32, ldc32=C, out16=out16, ldc16=C, a16_lo=p16lo, out16_lo=out16_lo,
-                   w_lo=E.wlo(pk, "wo" + sfx, p16lo, rt=rt))
+        E.gemm(rt, p, pk, "wo" + sfx, out, M=M, N=C, K=C, lda=C, bias=pk["bo" + sfx], res1=x.f32, ldr1=C, out32=x.f32, ldc32=C,
+               ldc16=C)
 
     def _run(self, rt: Runtime, x: Act, want_f16: bool = False) -> Act:
         if rt.T != self.num_frames:
@@ -492,10 +423,9 @@ class SpatialTemporalTransformer(nn.Module, Packable):
         self._branch(rt, x, "", self.transformer_blocks, "spatial")
         if self.insert_crossview:
             self._branch(rt, x, "_crossview", self.transformer_blocks_crossview, "crossview")
-        out16 = rt.empty((x.M, x.C), torch.float16) if want_f16 else None
-        out16lo = rt.lo_plane((x.M, x.C), "stream", on=want_f16)
-        self._branch(rt, x, "_temporal", self.transformer_blocks_temporal, "temporal", out16=out16, out16_lo=out16lo)
-        return Act(x.F, x.H, x.W, x.C, f32=x.f32, f16=out16, f16_lo=out16lo)
+        out = rt.operand((x.M, x.C), "stream") if want_f16 else None
+        self._branch(rt, x, "_temporal", self.transformer_blocks_temporal, "temporal", out=out)
+        return Act(x.F, x.H, x.W, x.C, f32=x.f32, f16=out)
 
     precision = "precise"      # operand policy of the reference-compatible entry below (the network sets rt.prec itself)
 
@@ -558,31 +488,31 @@ class TextKVProjector:
             with torch.no_grad():
                 self._pk, self._sig = self.pack(), sig
         w, NT, NKp, offs, Dm = self._pk
-        rows, D = rt.B * E.TEXT_PAD, rt.ctx16.shape[1]
+        rows, D = rt.B * E.TEXT_PAD, rt.ctx16.hi.shape[1]
         if Dm != D:
             raise ValueError(f"context width {D} does not match the cross-attention context_dim {Dm}")
         if rt.prec.kv_text:
             # split policy: every output column row-major with its lo plane (the split attention kernels read V row-major)
             ld = NKp + NT
-            kv, kv_lo = rt.empty((rows, ld), torch.float16), rt.lo_plane((rows, ld), "kv_text")
+            kv = rt.operand((rows, ld), "kv_text")
             w_lo = None
             if rt.prec.weights:                       # the lo twin of the stacked weights: same rows, same zero padding (n_split)
                 if getattr(self, "_pk_lo", None) is None or getattr(self, "_sig_lo", None) != sig:
                     with torch.no_grad():
                         self._pk_lo, self._sig_lo = self.pack(lo=True)[0], sig
                 w_lo = self._pk_lo
-            rt.be.gemm(rt.ctx16, w, M=rows, N=ld, K=D, lda=D, out16=kv, ldc16=ld, out16_lo=kv_lo, a16_lo=rt.ctx16_lo, w_lo=w_lo)
-            f, fl = kv.view(-1), kv_lo.view(-1)
+            E.gemm(rt, rt.ctx16, w, None, kv, w_lo=w_lo, M=rows, N=ld, K=D, lda=D, ldc16=ld)
+            kv = kv.map(lambda t: t.view(-1))
             for a, o in zip(self.sites, offs):
-                rt.text_kv[id(a)] = (f[o:], fl[o:], f[NKp + o:], fl[NKp + o:], ld)
+                rt.text_kv[id(a)] = E.TextKV(kv.map(lambda t: t[o:]), ld, kv.map(lambda t: t[NKp + o:]), ld)
             return
         k = rt.empty((rows, NKp), torch.float16)
         vt = rt.empty((rt.B, NT, E.TEXT_PAD), torch.float16)
-        rt.be.gemm(rt.ctx16, w, M=rows, N=NKp + NT, K=D, lda=D, out16=k, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,
-                   t_rows=E.TEXT_PAD, t_gstride=NT * E.TEXT_PAD, n_split=NKp)
+        E.gemm(rt, rt.ctx16, w, None, E.Operand(k), M=rows, N=NKp + NT, K=D, lda=D, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,
+               t_rows=E.TEXT_PAD, t_gstride=NT * E.TEXT_PAD, n_split=NKp)
         kf, vf = k.view(-1), vt.view(-1)
         for a, o in zip(self.sites, offs):
-            rt.text_kv[id(a)] = (kf[o:], NKp, vf[o * E.TEXT_PAD:], E.TEXT_PAD, NT * E.TEXT_PAD)
+            rt.text_kv[id(a)] = E.TextKV(E.Operand(kf[o:]), NKp, E.Operand(vf[o * E.TEXT_PAD:]), E.TEXT_PAD, NT * E.TEXT_PAD)
 
 
 def _is_listconfig(v) -> bool:

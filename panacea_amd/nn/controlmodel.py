@@ -90,15 +90,13 @@ class ControlNet3D(UNetModel3D):
         pk = self.packed()
         F, C, H, W = hint.shape
         cp = (C + 7) // 8 * 8
-        t16 = rt.empty((F * H * W, cp), torch.float16)
-        t16lo = rt.lo_plane((F * H * W, cp), "conv_mid")
-        rt.be.nchw_to_tokens_f16(hint.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, cp, t16, t16lo)
-        a = Act(F, H, W, cp, f16=t16, f16_lo=t16lo)
-        for i, ((w, b), s) in enumerate(zip(pk["hint"], HINT_STRIDES)):
+        t16 = rt.operand((F * H * W, cp), "conv_mid")
+        rt.be.nchw_to_tokens_f16(hint.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, cp, *t16)
+        a = Act(F, H, W, cp, f16=t16)
+        for i, ((w, _), s) in enumerate(zip(pk["hint"], HINT_STRIDES)):
             last = i == len(HINT_STRIDES) - 1
-            a = run_conv3x3(rt, a.f16, a.F, a.H, a.W, a.C, w, b, w.shape[0], stride=s, act_silu=not last,
-                            out32=last, out16=not last, x16_lo=a.f16_lo, split_out="conv_mid",
-                            w_lo=E.wlo(pk, ("hint", i), a.f16_lo, rt=rt))
+            a = run_conv3x3(rt, a.f16, a.F, a.H, a.W, a.C, pk, ("hint", i), w.shape[0], stride=s, act_silu=not last,
+                            out32=last, out16=not last, split_out="conv_mid")
         return a
 
     def _run_control(self, rt: Runtime, x16: Act, hint: torch.Tensor, emb32: torch.Tensor) -> List[Act]:
@@ -117,14 +115,13 @@ class ControlNet3D(UNetModel3D):
                                      f"{h.H}x{h.W}x{h.C} (the hint must be 8x the latent resolution)")
                 if guided.F < 1 or h.F % guided.F:
                     raise ValueError(f"{guided.F} hint frames do not tile the batch of {h.F} frames")
-                h.f16 = rt.empty((h.M, h.C), torch.float16)
-                h.f16_lo = rt.lo_plane((h.M, h.C), "stream")
+                h.f16 = rt.operand((h.M, h.C), "stream")
                 # h += guided_hint.  A hint of F / k frames is shared by the k groups of the batch (the two CFG halves carry
                 # the SAME BEV layout: the fused sampler step hands it over once and the stem runs on T frames, not 2 T)
                 mg = guided.M * h.C
                 for r in range(h.F // guided.F):
                     sl = slice(r * guided.M, (r + 1) * guided.M)
-                    rt.be.add_f32(h.f32[sl], guided.f32, mg, h.f32[sl], h.f16[sl], None if h.f16_lo is None else h.f16_lo[sl])
+                    rt.be.add_f32(h.f32[sl], guided.f32, mg, h.f32[sl], *h.f16.map(lambda t: t[sl]))
             outs.append(self._zero_conv(rt, h, pk, i))
         h = self.middle_block._run(rt, h, emb32, want_f16=True)
         if rt.trace is not None:
@@ -134,11 +131,8 @@ class ControlNet3D(UNetModel3D):
 
     @staticmethod
     def _zero_conv(rt: Runtime, h: Act, pk: dict, idx: int) -> Act:
-        w16, b = pk["zero"][idx]
         o = rt.empty((h.M, h.C), torch.float32)
-        x16 = h.need_f16(rt)
-        rt.be.gemm(x16, w16, M=h.M, N=h.C, K=h.C, lda=h.C, bias=b, out32=o, ldc32=h.C, a16_lo=h.f16_lo,
-                   w_lo=E.wlo(pk, ("zero", idx), h.f16_lo, w16, rt=rt))
+        E.gemm(rt, h.need_f16(rt), pk, ("zero", idx), M=h.M, N=h.C, K=h.C, lda=h.C, out32=o, ldc32=h.C)      # a (weight, bias) entry
         return Act(h.F, h.H, h.W, h.C, f32=o)
 
     def forward(self, x, hint, timesteps=None, context=None, y=None, **kwargs):
@@ -204,7 +198,7 @@ class ControlledUNetModel3D(UNetModel3D):
             guided = self.controlnet._hint_stem(rt, hint.detach().to(torch.float32).contiguous())
         # the sources are kept (for StepInvariants.rebuild) only where the policy can still change: an un-escalated "escalate" network
         keep = self.on_range_exceeded == "escalate" and not self.escalated
-        return StepInvariants(rt.ctx16, rt.n_text, dict(rt.text_kv), guided, (context, hint), rt.prec, rt.ctx16_lo, keep_sources=keep)
+        return StepInvariants(rt.ctx16, rt.n_text, dict(rt.text_kv), guided, (context, hint), rt.prec, keep_sources=keep)
 
     two_stream = True      # run the ControlNet branch on a second HIP stream, concurrently with the UNet encoder
     split_samples = False  # additionally run every sample of the batch (CFG half) as its own stream pair
@@ -263,7 +257,6 @@ class ControlledUNetModel3D(UNetModel3D):
                     inv.rebuild(self)              # prepared under the policy this network escalated from: text K/V, lo planes
                 inv.check(rt, context, hint)
                 rt.ctx16, rt.n_text, rt.text_kv, rt.text_frozen = inv.ctx16, inv.n_text, dict(inv.text_kv), True
-                rt.ctx16_lo = inv.ctx16_lo
                 rt.guided = inv.guided
             else:
                 rt.set_context(context)
@@ -294,7 +287,7 @@ class ControlledUNetModel3D(UNetModel3D):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     control = cn._run_control(rt_cn, x16, hint32, cn._time_embedding(rt_cn, timesteps))
-                for t in (x16.f16, rt.ctx16, hint32, timesteps):
+                for t in (x16.f16.hi, rt.ctx16.hi, hint32, timesteps):
                     t.record_stream(side)
 
                 def join():
@@ -317,9 +310,9 @@ class ControlledUNetModel3D(UNetModel3D):
 class StepInvariants:
     """Result of ControlledUNetModel3D.prepare(): tensors that are constant over the sampler steps of one sample."""
 
-    def __init__(self, ctx16, n_text, text_kv, guided, sources, prec=E.FAST, ctx16_lo=None, keep_sources=False):
+    def __init__(self, ctx16: E.Operand, n_text, text_kv, guided, sources, prec=E.FAST, keep_sources=False):
+        """ctx16: Runtime.ctx16; text_kv: Runtime.text_kv (an engine.TextKV per cross-attention site of both networks)"""
         self.ctx16, self.n_text, self.text_kv, self.guided, self.prec = ctx16, n_text, text_kv, guided, prec
-        self.ctx16_lo = ctx16_lo
         self._src = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in sources)
         self._sources = tuple(sources) if keep_sources else None
 

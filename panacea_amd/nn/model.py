@@ -50,11 +50,11 @@ def _conv3x3(rt: Runtime, x16, F, Hin, Win, Cin, w16, b, Cout, *, upsample=False
     Hout, Wout = (2 * Hin, 2 * Win) if upsample else ((Hin // 2, Win // 2) if down_br else (Hin, Win))
     M = F * Hout * Wout
     o32 = rt.empty((M, Cout), torch.float32)
-    o16 = rt.empty((M, Cout), torch.float16) if out16 else None
+    o16 = rt.operand((M, Cout)) if out16 else None      # (the first stage runs plain fp16 operands: no lo planes)
     rt.be.gemm(x16, w16, M=M, N=Cout, K=9 * Cin, a_mode=E._hip.A_CONV3X3,
                conv=dict(Cin=Cin, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=2 if down_br else 1,
                          upsample=int(upsample), pad_br=int(down_br)),
-               bias=b, res1=res32, ldr1=Cout, out32=o32, ldc32=Cout, out16=o16, ldc16=Cout)
+               bias=b, res1=res32, ldr1=Cout, out32=o32, ldc32=Cout, out16=o16 and o16.hi, ldc16=Cout)
     return Act(F, Hout, Wout, Cout, f32=o32, f16=o16)
 
 
@@ -74,7 +74,7 @@ class Upsample(nn.Module, Packable):
 
     def _run(self, rt: Runtime, x: Act) -> Act:
         w, b = self.packed()["c"]
-        return _conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, x.C, w, b, x.C, upsample=True)
+        return _conv3x3(rt, x.need_f16(rt).hi, x.F, x.H, x.W, x.C, w, b, x.C, upsample=True)
 
     def forward(self, x):
         rt = Runtime(x.device, x.shape[0], 1)
@@ -97,7 +97,7 @@ class Downsample(nn.Module, Packable):
 
     def _run(self, rt: Runtime, x: Act) -> Act:
         w, b = self.packed()["c"]
-        return _conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, x.C, w, b, x.C, down_br=True)
+        return _conv3x3(rt, x.need_f16(rt).hi, x.F, x.H, x.W, x.C, w, b, x.C, down_br=True)
 
     def forward(self, x):
         rt = Runtime(x.device, x.shape[0], 1)
@@ -135,17 +135,17 @@ class ResnetBlock(nn.Module, Packable):
     def _run(self, rt: Runtime, x: Act) -> Act:
         pk = self.packed()
         Ci, Co = self.in_channels, self.out_channels
-        h16, _ = E.gn_spatial(rt, x.f32, x.F, x.N, Ci, *pk["n1"], 1e-6, True)
+        h16 = E.gn_spatial(rt, x.f32, x.F, x.N, Ci, *pk["n1"], 1e-6, True).hi
         h = _conv3x3(rt, h16, x.F, x.H, x.W, Ci, *pk["c1"], Co)
-        h16, _ = E.gn_spatial(rt, h.f32, x.F, x.N, Co, *pk["n2"], 1e-6, True)
+        h16 = E.gn_spatial(rt, h.f32, x.F, x.N, Co, *pk["n2"], 1e-6, True).hi
         skip = x.f32
         if Ci != Co:
             w, b = pk["sc"]
             if self.use_conv_shortcut:
-                skip = _conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, Ci, w, b, Co).f32
+                skip = _conv3x3(rt, x.need_f16(rt).hi, x.F, x.H, x.W, Ci, w, b, Co).f32
             else:
                 skip = rt.empty((x.M, Co), torch.float32)
-                rt.be.gemm(x.need_f16(rt), w, M=x.M, N=Co, K=Ci, lda=Ci, bias=b, out32=skip, ldc32=Co)
+                rt.be.gemm(x.need_f16(rt).hi, w, M=x.M, N=Co, K=Ci, lda=Ci, bias=b, out32=skip, ldc32=Co)
         return _conv3x3(rt, h16, x.F, x.H, x.W, Co, *pk["c2"], Co, res32=skip)      # x (or shortcut(x)) + h
 
     def forward(self, x, temb=None):
@@ -178,7 +178,7 @@ class AttnBlock(nn.Module, Packable):
         C, N, M, F = self.in_channels, x.N, x.M, x.F
         if N > 16384 or N % 8:
             raise NotImplementedError(f"AttnBlock over {N} tokens per frame (supported: multiples of 8 up to 16384)")
-        h16, _ = E.gn_spatial(rt, x.f32, F, N, C, *pk["n"], 1e-6, False)
+        h16 = E.gn_spatial(rt, x.f32, F, N, C, *pk["n"], 1e-6, False).hi
         q16, k16 = rt.empty((M, C), torch.float16), rt.empty((M, C), torch.float16)
         vt16 = rt.empty((F, C, N), torch.float16)                       # channel-major V^T per frame
         rt.be.gemm(h16, pk["q"][0], M=M, N=C, K=C, lda=C, bias=pk["q"][1], out16=q16, ldc16=C)
@@ -302,7 +302,7 @@ class Decoder(nn.Module, Packable):
                 h = up.upsample._run(rt, h)
         if self.give_pre_end:
             return h
-        h16, _ = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True)
+        h16 = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True).hi
         w, b = pk["cout"]
         return _conv3x3(rt, h16, h.F, h.H, h.W, h.C, w, b, self.out_ch)
 
@@ -366,7 +366,7 @@ class Encoder(nn.Module, Packable):
         if isinstance(self.mid.attn_1, AttnBlock):
             h = self.mid.attn_1._run(rt, h)
         h = self.mid.block_2._run(rt, h)
-        h16, _ = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True)
+        h16 = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True).hi
         w, b = pk["cout"]
         return _conv3x3(rt, h16, h.F, h.H, h.W, h.C, w, b, self.out_channels)
 
@@ -413,7 +413,7 @@ class FirstStageEncoder(nn.Module, Packable):
             w, b = self.packed()["q"]
             n = self.quant_conv.out_channels
             m32 = rt.empty((h.M, n), torch.float32)
-            rt.be.gemm(h.need_f16(rt), w, M=h.M, N=n, K=h.C, lda=h.C, bias=b, out32=m32, ldc32=n)
+            rt.be.gemm(h.need_f16(rt).hi, w, M=h.M, N=n, K=h.C, lda=h.C, bias=b, out32=m32, ldc32=n)
             return Act(h.F, h.H, h.W, n, f32=m32).to_nchw().to(x.dtype)
 
     def encode(self, x: torch.Tensor, generator=None, sample: bool = True) -> torch.Tensor:

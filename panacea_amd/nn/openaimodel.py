@@ -45,53 +45,29 @@ def conv_params(conv: nn.Conv2d, lo=False):
     raise NotImplementedError(f"conv kernel size {k}")
 
 
-def run_conv3x3(rt: Runtime, x16: torch.Tensor, F: int, Hin: int, Win: int, Cin_pad: int, w16, bias, Cout: int,
+def run_conv3x3(rt: Runtime, x: E.Operand, F: int, Hin: int, Win: int, Cin_pad: int, pk, key, Cout: int, bias=None,
                 stride: int = 1, upsample: bool = False, act_silu: bool = False, out32: bool = True,
-                out16: bool = False, x16_lo: Optional[torch.Tensor] = None, split_out: Optional[str] = None, w_lo=None):
-    """3x3 conv (pad 1) as implicit GEMM over the channels-last fp16 image x16 [F*Hin*Win, Cin_pad] (+ lo plane of a
-    precise operand, + `w_lo` = engine.wlo(...) when that plane is e4m3); `split_out`: operand class of the fp16 output, which
-    is written as a precise pair when the policy splits that class."""
-    if rt.vshard is not None:
-        return _conv3x3_view_band(rt, x16, F, Hin, Win, Cin_pad, w16, bias, Cout, stride, upsample, act_silu, out32, out16,
-                                  x16_lo, split_out, w_lo)
-    if upsample:
-        Hout, Wout = 2 * Hin, 2 * Win
-    else:
-        Hout, Wout = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
-    M = F * Hout * Wout
-    o32 = rt.empty((M, Cout), torch.float32) if out32 else None
-    o16 = rt.empty((M, Cout), torch.float16) if out16 else None
-    o16lo = rt.lo_plane((M, Cout), split_out, on=out16) if split_out else None
-    rt.be.gemm(x16, w16, M=M, N=Cout, K=9 * Cin_pad, a_mode=E._hip.A_CONV3X3, w_lo=w_lo,
-               conv=dict(Cin=Cin_pad, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=stride, upsample=int(upsample)),
-               bias=bias, act=E._hip.ACT_SILU if act_silu else E._hip.ACT_NONE,
-               out32=o32, ldc32=Cout, out16=o16, ldc16=Cout, a16_lo=x16_lo, out16_lo=o16lo)
-    return Act(F, Hout, Wout, Cout, f32=o32, f16=o16, f16_lo=o16lo)
-
-
-def _conv3x3_view_band(rt: Runtime, x16, F, Hin, Win, Cin_pad, w16, bias, Cout, stride, upsample, act_silu, out32, out16,
-                       x16_lo, split_out, w_lo):
-    """run_conv3x3 on this rank's band of views (engine.ViewShard).  The band's columns -1 and Win — the neighbour ranks' edge
-    columns — sit in a tail of the operand's own allocation (ViewShard.band_operand) and the gather reads them where the
-    unsharded conv reads the neighbouring views (PncGemmParams.x_halo_off): the conv runs over the band as it lies and writes
-    the band's outputs, no widened copy of the operand and no window copy of the result."""
-    vs = rt.vshard
-    if stride == 2 and Win % 2:
-        raise ValueError(f"a stride-2 conv over a view band needs an even band width, got {Win}")
-    planes, xoff = vs.band_operand(rt, [x16] + ([x16_lo] if x16_lo is not None else []), F, Hin, Win, Cin_pad)
+                out16: bool = False, split_out: Optional[str] = None) -> Act:
+    """3x3 conv (pad 1) as implicit GEMM over the channels-last fp16 image x [F*Hin*Win, Cin_pad] with the weights pk[key]
+    (engine.gemm); `split_out`: operand class of the fp16 output.
+    On a rank's band of views (engine.ViewShard) the band's columns -1 and Win — the neighbour ranks' edge columns — sit in a tail
+    of the operand's own allocation (ViewShard.band_operand) and the gather reads them where the unsharded conv reads the
+    neighbouring views (PncGemmParams.x_halo_off): the conv runs over the band as it lies and writes the band's outputs, no widened
+    copy of the operand and no window copy of the result."""
     Hout = 2 * Hin if upsample else (Hin - 1) // stride + 1
     Wout = 2 * Win if upsample else (Win - 1) // stride + 1
+    conv = dict(Cin=Cin_pad, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=stride, upsample=int(upsample))
+    if rt.vshard is not None:
+        if stride == 2 and Win % 2:
+            raise ValueError(f"a stride-2 conv over a view band needs an even band width, got {Win}")
+        planes, conv["x_halo_off"] = rt.vshard.band_operand(rt, x.planes(), F, Hin, Win, Cin_pad)
+        x = E.Operand(*planes)
     M = F * Hout * Wout
     o32 = rt.empty((M, Cout), torch.float32) if out32 else None
-    o16 = rt.empty((M, Cout), torch.float16) if out16 else None
-    o16lo = rt.lo_plane((M, Cout), split_out, on=out16) if split_out else None
-    rt.be.gemm(planes[0], w16, M=M, N=Cout, K=9 * Cin_pad, a_mode=E._hip.A_CONV3X3, w_lo=w_lo,
-               conv=dict(Cin=Cin_pad, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=stride, upsample=int(upsample),
-                         x_halo_off=xoff),
-               bias=bias, act=E._hip.ACT_SILU if act_silu else E._hip.ACT_NONE,
-               out32=o32, ldc32=Cout, out16=o16, ldc16=Cout,
-               a16_lo=planes[1] if x16_lo is not None else None, out16_lo=o16lo)
-    return Act(F, Hout, Wout, Cout, f32=o32, f16=o16, f16_lo=o16lo)
+    o16 = rt.operand((M, Cout), split_out) if out16 else None
+    E.gemm(rt, x, pk, key, o16, M=M, N=Cout, K=9 * Cin_pad, a_mode=E._hip.A_CONV3X3, conv=conv, bias=bias,
+           act=E._hip.ACT_SILU if act_silu else E._hip.ACT_NONE, out32=o32, ldc32=Cout, ldc16=Cout)
+    return Act(F, Hout, Wout, Cout, f32=o32, f16=o16)
 
 
 class TimestepEmbedSequential(nn.Sequential, TimestepBlock, Packable):
@@ -117,21 +93,15 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock, Packable):
             elif isinstance(layer, (Upsample, Downsample)):
                 x = layer._run(rt, x, want_f16=wf)
             elif isinstance(layer, nn.Conv2d):
-                pk = self.packed()
-                w16, b = pk[i]
-                x16 = x.need_f16(rt)
-                w_lo = E.wlo(pk, i, x.f16_lo, w16, rt=rt)
+                pk, Co = self.packed(), layer.out_channels           # pk[i] = (weight, bias)
                 if layer.kernel_size[0] == 3:
-                    x = run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, w16, b, layer.out_channels,
-                                    stride=layer.stride[0], out16=wf, x16_lo=x.f16_lo, split_out="stream", w_lo=w_lo)
+                    x = run_conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, x.C, pk, i, Co, stride=layer.stride[0], out16=wf,
+                                    split_out="stream")
                 else:
-                    o32 = rt.empty((x.M, layer.out_channels), torch.float32)
-                    o16 = rt.empty((x.M, layer.out_channels), torch.float16) if wf else None
-                    o16lo = rt.lo_plane((x.M, layer.out_channels), "stream", on=wf)
-                    rt.be.gemm(x16, w16, M=x.M, N=layer.out_channels, K=x.C, lda=x.C, bias=b,
-                               out32=o32, ldc32=layer.out_channels, out16=o16, ldc16=layer.out_channels,
-                               a16_lo=x.f16_lo, out16_lo=o16lo, w_lo=w_lo)
-                    x = Act(x.F, x.H, x.W, layer.out_channels, f32=o32, f16=o16, f16_lo=o16lo)
+                    o32 = rt.empty((x.M, Co), torch.float32)
+                    o16 = rt.operand((x.M, Co), "stream") if wf else None
+                    E.gemm(rt, x.need_f16(rt), pk, i, o16, M=x.M, N=Co, K=x.C, lda=x.C, out32=o32, ldc32=Co, ldc16=Co)
+                    x = Act(x.F, x.H, x.W, Co, f32=o32, f16=o16)
             else:
                 raise NotImplementedError(f"{type(layer).__name__} inside TimestepEmbedSequential")
         return x
@@ -159,9 +129,10 @@ class Upsample(nn.Module, Packable):
     def _run(self, rt: Runtime, x: Act, want_f16=False) -> Act:
         pk = self.packed()
         x16 = x.need_f16(rt)
-        lo = x.f16_lo if self.precise_operand else None
-        return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk["w"], pk["b"], self.out_channels,
-                           upsample=True, out16=want_f16, x16_lo=lo, split_out="stream", w_lo=E.wlo(pk, "w", lo, rt=rt))
+        if not self.precise_operand:
+            x16 = E.Operand(x16.hi)
+        return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk, "w", self.out_channels, pk["b"], upsample=True, out16=want_f16,
+                           split_out="stream")
 
 
 class Downsample(nn.Module, Packable):
@@ -181,9 +152,8 @@ class Downsample(nn.Module, Packable):
 
     def _run(self, rt: Runtime, x: Act, want_f16=False) -> Act:
         pk = self.packed()
-        x16 = x.need_f16(rt)
-        return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk["w"], pk["b"], self.out_channels,
-                           stride=2, out16=want_f16, x16_lo=x.f16_lo, split_out="stream", w_lo=E.wlo(pk, "w", x.f16_lo, rt=rt))
+        return run_conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, x.C, pk, "w", self.out_channels, pk["b"], stride=2, out16=want_f16,
+                           split_out="stream")
 
 
 class ResBlock3D(TimestepBlock, Packable):
@@ -240,7 +210,7 @@ class ResBlock3D(TimestepBlock, Packable):
         out = rt.emb_proj.get(id(self))
         if out is not None and out.shape == (F, Co):
             return out
-        return E.small_linear(rt, emb32, pk["we"], pk["be"], F, Co, self.emb_channels, w_lo=E.wlo32(pk, "we", rt))
+        return E.small_linear(rt, emb32, pk, "we", "be", F, Co, self.emb_channels)
 
     def _run(self, rt: Runtime, x: Act, emb32: torch.Tensor, want_f16: bool = False, want_stats: bool = False) -> Act:
         if rt.T != self.num_frames:
@@ -256,9 +226,9 @@ class ResBlock3D(TimestepBlock, Packable):
         Mt = rt.B * rt.T * Nt
         tconv = dict(C=Co, T=rt.T, Npix=Nt)
         # in_layers: GN + SiLU + conv3x3
-        tail = 2 * F * x.H if rt.vshard is not None else 0      # room for a view band's neighbour columns (_conv3x3_view_band)
-        a16, a16lo = E.gn_spatial(rt, x.f32, F, N, Cin, pk["g1"], pk["b1"], 1e-5, True, split="gn_res", tail_rows=tail, part=x.gn_part)
-        h = run_conv3x3(rt, a16, F, H, W, Cin, pk["w1"], pk["c1"], Co, x16_lo=a16lo, w_lo=E.wlo(pk, "w1", a16lo, rt=rt)).f32
+        tail = 2 * F * x.H if rt.vshard is not None else 0      # room for a view band's neighbour columns (run_conv3x3)
+        a = E.gn_spatial(rt, x.f32, F, N, Cin, pk["g1"], pk["b1"], 1e-5, True, split="gn_res", tail_rows=tail, part=x.gn_part)
+        h = run_conv3x3(rt, a, F, H, W, Cin, pk, "w1", Co, pk["c1"]).f32
         # h = h + conv1d_t(SiLU(GN_t(h))) + emb_layers(emb)[frame]      (:505-531)
         # emb32 arrives as SiLU(emb): the activation of `emb_layers` is applied ONCE per network evaluation by
         # _time_embedding (32 ResBlocks x 16 x 1280 identical SiLUs otherwise), the Linear runs here
@@ -269,71 +239,66 @@ class ResBlock3D(TimestepBlock, Packable):
             # group (256 B per pixel), the normalised fp16 operand gets ONE halo frame from each neighbour rank, and the temporal
             # conv reads the (T_local + 2)-frame layout (PncGemmParams.t_halo); the fp32 stream h never leaves the rank.
             emb_out = self._emb_out(rt, emb32, pk, F, Co)
-            t16, t16lo = E.gn_temporal_sharded(rt, sh, h, N, Co, pk["gt1"], pk["bt1"], 1e-5)
+            t = E.gn_temporal_sharded(rt, sh, h, N, Co, pk["gt1"], pk["bt1"], 1e-5)
             tch = dict(C=Co, T=rt.T_local, Npix=N, halo=1)
             part1 = E.gn_records(rt, F, N)
-            rt.be.gemm(t16, pk["wt1"], M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tch, bias=pk["ct1"],
-                       rowbias=emb_out, rb_rows=N, rb_mod=F, res1=h, ldr1=Co, out32=h, ldc32=Co, a16_lo=t16lo,
-                       w_lo=E.wlo(pk, "wt1", t16lo, rt=rt), gn_part=part1)
+            E.gemm(rt, t, pk, "wt1", M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tch, bias=pk["ct1"],
+                   rowbias=emb_out, rb_rows=N, rb_mod=F, res1=h, ldr1=Co, out32=h, ldc32=Co, gn_part=part1)
         elif sh is not None:
             # (round 2's form, FrameShard(resblock="transpose"): the fp32 stream to the pixel sharding and back)
             # the exchange runs on the communicator's stream; what this site computes independently of it — the timestep
             # embedding's linear and the skip path — is enqueued under the transfer
             pend = sh.to_pixels_start(h, rt.B, N)
-            emb_out = E.small_linear(rt, rt.emb_all, pk["we"], pk["be"], rt.B * rt.T, Co, self.emb_channels, w_lo=E.wlo32(pk, "we", rt))
+            emb_out = E.small_linear(rt, rt.emb_all, pk, "we", "be", rt.B * rt.T, Co, self.emb_channels)
             s = self._skip(rt, x, pk)
             h = pend.result()
         else:
             emb_out = self._emb_out(rt, emb32, pk, F, Co)
         if not halo:
-            t16, t16lo = E.gn_temporal(rt, h, Nt, Co, pk["gt1"], pk["bt1"], 1e-5)
+            t = E.gn_temporal(rt, h, Nt, Co, pk["gt1"], pk["bt1"], 1e-5)
             # the GroupNorm of out_layers reads what this conv writes: its statistics come out of the conv's epilogue (frame layout only)
             part1 = E.gn_records(rt, F, N) if sh is None else None
-            rt.be.gemm(t16, pk["wt1"], M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct1"],
-                       rowbias=emb_out, rb_rows=Nt, rb_mod=rt.B * rt.T, res1=h, ldr1=Co, out32=h, ldc32=Co, a16_lo=t16lo,
-                       w_lo=E.wlo(pk, "wt1", t16lo, rt=rt), gn_part=part1)
+            E.gemm(rt, t, pk, "wt1", M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct1"],
+                   rowbias=emb_out, rb_rows=Nt, rb_mod=rt.B * rt.T, res1=h, ldr1=Co, out32=h, ldc32=Co, gn_part=part1)
             if sh is not None:
                 h = sh.to_frames(h, rt.B, N)
         # out_layers: GN + SiLU + conv3x3
-        a16, a16lo = E.gn_spatial(rt, h, F, N, Co, pk["g2"], pk["b2"], 1e-5, True, split="gn_res", tail_rows=tail, part=part1)
-        g = run_conv3x3(rt, a16, F, H, W, Co, pk["w2"], pk["c2"], Co, x16_lo=a16lo, w_lo=E.wlo(pk, "w2", a16lo, rt=rt)).f32
+        a = E.gn_spatial(rt, h, F, N, Co, pk["g2"], pk["b2"], 1e-5, True, split="gn_res", tail_rows=tail, part=part1)
+        g = run_conv3x3(rt, a, F, H, W, Co, pk, "w2", Co, pk["c2"]).f32
         # skip path
         if s is None:
             s = self._skip(rt, x, pk)
         # return skip(x) + (g + conv1d_t(SiLU(GN_t(g))))                 (:533-542)
-        o16 = rt.empty((M, Co), torch.float16) if want_f16 else None
-        o16lo = rt.lo_plane((M, Co), "stream", on=want_f16)
+        o16 = rt.operand((M, Co), "stream") if want_f16 else None
         part2 = None
         if sh is None or halo:
             if halo:
-                t16, t16lo = E.gn_temporal_sharded(rt, sh, g, N, Co, pk["gt2"], pk["bt2"], 1e-5)
+                t = E.gn_temporal_sharded(rt, sh, g, N, Co, pk["gt2"], pk["bt2"], 1e-5)
                 tc2 = dict(C=Co, T=rt.T_local, Npix=N, halo=1)
             else:
-                t16, t16lo = E.gn_temporal(rt, g, N, Co, pk["gt2"], pk["bt2"], 1e-5)
+                t = E.gn_temporal(rt, g, N, Co, pk["gt2"], pk["bt2"], 1e-5)
                 tc2 = tconv
             # ... and so do the statistics of the block's output, for the GroupNorm the next layer starts with
             part2 = E.gn_records(rt, F, N) if want_stats else None
-            rt.be.gemm(t16, pk["wt2"], M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tc2, bias=pk["ct2"],
-                       res1=g, ldr1=Co, res2=s, ldr2=Co, out32=g, ldc32=Co, out16=o16, ldc16=Co, a16_lo=t16lo,
-                       out16_lo=o16lo, w_lo=E.wlo(pk, "wt2", t16lo, rt=rt), gn_part=part2)
+            E.gemm(rt, t, pk, "wt2", o16, M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tc2, bias=pk["ct2"],
+                   res1=g, ldr1=Co, res2=s, ldr2=Co, out32=g, ldc32=Co, ldc16=Co, gn_part=part2)
         else:
             # the skip path stays in the frame layout: g + conv1d in the pixel layout, exchange back, then + skip
             gp = sh.to_pixels(g, rt.B, N)
-            t16, t16lo = E.gn_temporal(rt, gp, Nt, Co, pk["gt2"], pk["bt2"], 1e-5)
-            rt.be.gemm(t16, pk["wt2"], M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct2"],
-                       res1=gp, ldr1=Co, out32=gp, ldc32=Co, a16_lo=t16lo, w_lo=E.wlo(pk, "wt2", t16lo, rt=rt))
+            t = E.gn_temporal(rt, gp, Nt, Co, pk["gt2"], pk["bt2"], 1e-5)
+            E.gemm(rt, t, pk, "wt2", M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct2"],
+                   res1=gp, ldr1=Co, out32=gp, ldc32=Co)
             g = sh.to_frames(gp, rt.B, N)
-            rt.be.add_f32(g, s, M * Co, g, o16, o16lo)
-        return Act(F, H, W, Co, f32=g, f16=o16, f16_lo=o16lo, gn_part=part2)
+            rt.be.add_f32(g, s, M * Co, g, *(o16 or (None, None)))
+        return Act(F, H, W, Co, f32=g, f16=o16, gn_part=part2)
 
     def _skip(self, rt: Runtime, x: Act, pk: dict) -> torch.Tensor:
         """skip_connection(x): the 1x1 conv where the channel count changes (openaimodel.py:486), else x itself"""
         if "ws" not in pk:
             return x.f32
         s = rt.empty((x.M, self.out_channels), torch.float32)
-        x16 = x.need_f16(rt)
-        rt.be.gemm(x16, pk["ws"], M=x.M, N=self.out_channels, K=self.channels, lda=self.channels, bias=pk["bs"], out32=s,
-                   ldc32=self.out_channels, a16_lo=x.f16_lo, w_lo=E.wlo(pk, "ws", x.f16_lo, rt=rt))
+        E.gemm(rt, x.need_f16(rt), pk, "ws", M=x.M, N=self.out_channels, K=self.channels, lda=self.channels, bias=pk["bs"], out32=s,
+               ldc32=self.out_channels)
         return s
 
     precision = "precise"      # operand policy of the reference-compatible entry below (the network sets rt.prec itself)
@@ -765,9 +730,9 @@ class UNetModel3D(nn.Module, Packable):
         if mc % 8:
             raise NotImplementedError("model_channels must be a multiple of 8")
         t_emb = timestep_embedding(timesteps.to(rt.device), mc)
-        h = E.small_linear(rt, t_emb, pk["tw0"], pk["tb0"], rt.F, td, mc, silu_out=True, w_lo=E.wlo32(pk, "tw0", rt))
+        h = E.small_linear(rt, t_emb, pk, "tw0", "tb0", rt.F, td, mc, silu_out=True)
         # returns SiLU(emb): every consumer of emb (ResBlock3D.emb_layers, :468-476) starts with nn.SiLU
-        emb = E.small_linear(rt, h, pk["tw2"], pk["tb2"], rt.F, td, td, silu_out=True, w_lo=E.wlo32(pk, "tw2", rt))
+        emb = E.small_linear(rt, h, pk, "tw2", "tb2", rt.F, td, td, silu_out=True)
         if rt.shard is not None:
             # the temporal sites run on all T frames of a pixel: they index the embedding rows of ALL frames (40 KB)
             rt.emb_all = rt.shard.gather_rows(emb, rt.B)
@@ -777,10 +742,9 @@ class UNetModel3D(nn.Module, Packable):
         """self.out: GN + SiLU + conv3x3 -> NCHW fp32 (:1245-1253, controlmodel.py:197-202); `tokens`: the channels-last
         fp32 tokens instead (consumed by the fused sampler-step exit, pnc_cfg_euler_step)."""
         pk = self.packed()
-        a16, a16lo = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, pk["og"], pk["ob"], 1e-5, True, split="gn_head",
-                                  tail_rows=2 * h.F * h.H if rt.vshard is not None else 0)
-        o = run_conv3x3(rt, a16, h.F, h.H, h.W, h.C, pk["ow"], pk["oc"], self.out_channels, x16_lo=a16lo,
-                        w_lo=E.wlo(pk, "ow", a16lo, rt=rt))
+        a = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, pk["og"], pk["ob"], 1e-5, True, split="gn_head",
+                         tail_rows=2 * h.F * h.H if rt.vshard is not None else 0)
+        o = run_conv3x3(rt, a, h.F, h.H, h.W, h.C, pk, "ow", self.out_channels, pk["oc"])
         if tokens:
             return o
         out = rt.empty((h.F, self.out_channels, h.H, h.W), torch.float32)
@@ -798,10 +762,9 @@ class UNetModel3D(nn.Module, Packable):
         cp = (C + C2 + 7) // 8 * 8
         x32 = x.detach().to(torch.float32).contiguous()
         b32 = None if concat is None else concat.detach().to(torch.float32).contiguous()
-        t16 = rt.empty((F * H * W, cp), torch.float16)
-        t16lo = rt.lo_plane((F * H * W, cp), "stem")
-        rt.be.nchw_to_tokens_f16(x32, C, b32, C2, F, H * W, cp, t16, t16lo, a_scale=scale, a_frames=Fx)
-        return Act(F, H, W, cp, f16=t16, f16_lo=t16lo)
+        t16 = rt.operand((F * H * W, cp), "stem")
+        rt.be.nchw_to_tokens_f16(x32, C, b32, C2, F, H * W, cp, *t16, a_scale=scale, a_frames=Fx)
+        return Act(F, H, W, cp, f16=t16)
 
     def _own_blocks(self):
         for name in ("input_blocks", "middle_block", "output_blocks"):
@@ -837,17 +800,16 @@ class UNetModel3D(nn.Module, Packable):
             c = control.pop() if control is not None else None
             ct = h.C + s.C
             cat32 = rt.empty((h.M, ct), torch.float32)
-            cat16 = rt.empty((h.M, ct), torch.float16)
-            cat16lo = rt.lo_plane((h.M, ct), "stream")
+            cat16 = rt.operand((h.M, ct), "stream")
             # th.cat([h, hs.pop() + control.pop()], dim=1): one pass, fp32 stream + fp16 operand (of the skip 1x1 conv)
             # (round 5: the same pass writes the statistics of the GroupNorm that reads the concat — the first norm of the block's
             # ResBlock3D —: 12 statistics launches and their read of C1 + C2 fp32 channels per step gone)
             part, ppc = None, E._ppc(h.H * h.W)
             if ct % 64 == 0 and E.GN_FROM_EPILOGUE:
                 part = rt.empty((h.F * (-(-(h.H * h.W) // ppc)) * 96,), torch.float32)
-            rt.be.concat_add(h.f32, h.C, s.f32, None if c is None else c.f32, s.C, h.M, cat32, cat16, cat16lo,
+            rt.be.concat_add(h.f32, h.C, s.f32, None if c is None else c.f32, s.C, h.M, cat32, *cat16,
                              **({} if part is None else dict(gn_part=part, frames=h.F, ppc=ppc)))
-            h = module._run(rt, Act(h.F, h.H, h.W, ct, f32=cat32, f16=cat16, f16_lo=cat16lo, gn_part=part), emb32)
+            h = module._run(rt, Act(h.F, h.H, h.W, ct, f32=cat32, f16=cat16, gn_part=part), emb32)
             if rt.trace is not None:
                 rt.trace[f"output_blocks.{i}"] = h.to_nchw()
         return self._head(rt, h, tokens)

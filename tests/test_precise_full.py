@@ -226,6 +226,6 @@ def test_hoisted_invariants_run_under_precise_full(full_emu):
     with torch.no_grad():
         plain = m.denoise(x, inp["t"], ctx, hint)
         inv = m.prepare(ctx, hint)
-        assert inv.prec == E.PRECISE_FULL and inv.ctx16_lo is not None
+        assert inv.prec == E.PRECISE_FULL and inv.ctx16.lo is not None
         hoisted = m.denoise(x, inp["t"], ctx, hint, invariants=inv)
     assert torch.equal(plain, hoisted)

@@ -114,10 +114,10 @@ def test_escalate_rebuilds_the_hoisted_invariants(wide_emu):
     m.on_range_exceeded = "escalate"
     with torch.no_grad():
         inv = m.prepare(ctx, hint)
-        assert inv.prec == E.PRECISE and inv.ctx16_lo is None
+        assert inv.prec == E.PRECISE and inv.ctx16.lo is None
         got = m.denoise(x, inp["t"], ctx, hint, invariants=inv)
     assert m.escalated
-    assert inv.prec == E.PRECISE_WIDE and inv.ctx16_lo is not None           # rebuilt in place under the new policy
+    assert inv.prec == E.PRECISE_WIDE and inv.ctx16.lo is not None           # rebuilt in place under the new policy
     assert torch.equal(got, direct)
 
 

@@ -37,7 +37,7 @@ def classify(site: str) -> str:
     """operand class of the rounding that `site` performs, from the host function that called the backend"""
     fn = None
     for fr in inspect.stack()[2:12]:
-        if "/panacea_amd/" in fr.filename:
+        if "/panacea_amd/" in fr.filename and fr.function not in ("gemm", "_gemm_ln"):      # (engine.gemm: every site launches through it)
             fn = fr.function
             break
     if site == "layernorm":
@@ -163,7 +163,7 @@ class Experiment:
             c = torch.zeros((B, E.TEXT_PAD, D), dtype=torch.float32)
             exp.count["ctx"] += context.numel()
             c[:, :n] = rounder(exp.modes["ctx"])(context.float())
-            rt.ctx16 = c.view(B * E.TEXT_PAD, D)
+            rt.ctx16 = E.Operand(c.view(B * E.TEXT_PAD, D))
         E.Runtime.set_context = set_context
         # modes M / M4: the WEIGHTS of the lo pass are MX fp8 / fp4 too.  The A operand arrives as hi + lo_q (fp32 buffer); its lo
         # part is what fp16 rounding leaves, and the lo pass contributes lo_q . (W_mx - W) on top of the exact product.
