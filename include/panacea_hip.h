@@ -378,7 +378,10 @@ int pnc_groupnorm_temporal_silu(const float* x, int B, int T, int Npix, int C,
  *   mode 1: stats[((b*Npix + p)*32 + g)*2 + {0,1}] = {sum, sum of squares} over the (C/32, T) values this rank holds;
  *   mode 2: normalise + SiLU with `stats` = those sums added over the ranks and T_total = frames per sample over all ranks;
  *           t_pad = 1 writes y into the (T + 2)-frame layout PncGemmParams.t_halo reads (frame t at slot t + 1).
- *    -> the same nn.GroupNorm on "(b h w) c t" when the T frames of a pixel live on several ranks */
+ *    -> the same nn.GroupNorm on "(b h w) c t" when the T frames of a pixel live on several ranks
+ * The exchanged sums are raw moments (they have to add up over the ranks), so mode 2 forms var = E[x^2] - mean^2 in fp32: its
+ * relative error grows as r^2 * 2^-24 times the growth of the accumulation, r = |mean| / std of a (pixel, group).  The frame-sharded
+ * path inherits that law; pnc_groupnorm_temporal_silu (every frame local) subtracts the mean before it squares and does not. */
 int pnc_groupnorm_temporal_part(const float* x, int B, int T, int Npix, int C,
                                 const float* gamma, const float* beta, float eps,
                                 float* stats, int mode, int T_total,

@@ -14,21 +14,104 @@ constexpr int GROUPS = 32;
 //          a 1e-7 run-to-run wobble here would decorrelate the fp16 rounding of everything downstream)
 //          -> partial {n, mean, M2} per (frame, chunk, group)
 //   apply: Chan-combine the chunk partials, tabulate y = x*A[c] + B[c] per channel in LDS, stream.
+// The sums are taken of d = x - pivot, the pivot of a (wave, channel pair) being the first value it meets (a pair
+// never straddles two groups: C / 32 is even): sum(x^2) - sum(x)^2 / n loses (mean / std)^2 * 2^-24 of the variance,
+// d does not see the mean at all.  The pivot's own size comes back once, in mean = pivot + sum(d) / n (one rounding
+// of a value of the mean's size: linear in mean / std).
+
+// pixels of a chunk of np that wave w of 4 walks (pixel w, w + 4, ...)
+__device__ __forceinline__ int gn_wave_pixels(int np, int w) { return np > w ? (np - w + 3) >> 2 : 0; }
+
+// The tail of a statistics workgroup: per-(wave, channel) {pivot, sum d, sum d^2} in registers -> one {n, mean, M2} per group.
+// Cs channels = ng whole groups of cpg; sm: [4][Cs] floats, then ng floats.  Two rounds through sm, each added up by one thread
+// per group in the fixed order (wave, channel):
+//   1. means m_wc = pivot + sum d / n_w;  group mean = P + sum n_w (m_wc - P) / n, P = the group's first m_0c (wave 0 always
+//      holds a pixel; a wave without one has n_w = 0 and m_wc = 0)
+//   2. M2_wc + n_w (m_wc - group mean)^2, M2_wc = sum d^2 - (sum d)^2 / n_w
+// Returns true in the threads tid < ng, with the record of group tid in (n, mean, m2).
+template <int J>
+__device__ __forceinline__ bool gn_reduce_records(float* sm, int Cs, int cpg, int ng, int np, const float2 (&pv)[J],
+                                                  const f32x4 (&sum)[J], const f32x4 (&sq)[J], float& n, float& mean, float& m2) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int CVs = Cs >> 2;
+    float* mine = sm + wave * Cs;
+    float* s_gmean = sm + 4 * Cs;
+    const float nw = (float)gn_wave_pixels(np, wave);
+    const float inw = nw > 0.0f ? 1.0f / nw : 0.0f;
+    const float icpg = 1.0f / (float)cpg;
+    f32x4 m[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int cv = lane + j * 64;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[j][e] = fmaf(sum[j][e], inw, e < 2 ? pv[j].x : pv[j].y);
+        if (cv < CVs) *reinterpret_cast<f32x4*>(mine + cv * 4) = m[j];
+    }
+    __syncthreads();
+    n = (float)np * (float)cpg;
+    mean = 0.0f; m2 = 0.0f;
+    if (tid < ng) {
+        const float P = sm[tid * cpg];
+        float acc = 0.0f;
+        for (int w = 0; w < 4; ++w) {
+            const float k = (float)gn_wave_pixels(np, w);
+            float a = 0.0f;
+            for (int c = 0; c < cpg; ++c) a += sm[w * Cs + tid * cpg + c] - P;
+            acc = fmaf(k, a, acc);
+        }
+        mean = P + acc / n;
+        s_gmean[tid] = mean;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int cv = lane + j * 64;
+        if (cv < CVs) {
+            f32x4 r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float dm = m[j][e] - s_gmean[(int)(((float)(cv * 4 + e) + 0.5f) * icpg)];     // (c / cpg without the integer division)
+                r[e] = fmaf(nw * dm, dm, fmaxf(fmaf(-sum[j][e] * inw, sum[j][e], sq[j][e]), 0.0f));
+            }
+            *reinterpret_cast<f32x4*>(mine + cv * 4) = r;
+        }
+    }
+    __syncthreads();
+    if (tid < ng)
+        for (int w = 0; w < 4; ++w)
+            for (int c = 0; c < cpg; ++c) m2 += sm[w * Cs + tid * cpg + c];
+    return tid < ng;
+}
+
 template <int J>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, int ldx, int Npix, int C,
                                                        int ppc, float* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];     // [4][C]: per-wave sums, then per-wave squares
+    extern __shared__ __attribute__((aligned(16))) float sm[];     // [4][C]: per-wave means, then per-wave M2; 32 group means
     const int f = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int CV = C >> 2, cpg = C / GROUPS;
     const int p0 = chunk * ppc;
     const int p1 = min(Npix, p0 + ppc);
     f32x4 sum[J], sq[J];
+    float2 pv[J];
     const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int j = 0; j < J; ++j) { sum[j] = z; sq[j] = z; }
+    for (int j = 0; j < J; ++j) { sum[j] = z; sq[j] = z; pv[j] = make_float2(0.0f, 0.0f); }
+    if (p0 + wave < p1) {                                          // the pivots come from this wave's first pixel
+        const float* row = x + ((int64_t)f * Npix + p0 + wave) * ldx;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const int cv = lane + j * 64;
+            if (cv < CV) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(row + cv * 4);
+                pv[j] = make_float2(v[0], v[2]);
+                sum[j] = f32x4{0.0f, v[1] - v[0], 0.0f, v[3] - v[2]};
+                sq[j] = sum[j] * sum[j];
+            }
+        }
+    }
 #pragma unroll 2
-    for (int pix = p0 + wave; pix < p1; pix += 4) {
+    for (int pix = p0 + wave + 4; pix < p1; pix += 4) {
         const float* row = x + ((int64_t)f * Npix + pix) * ldx;
         f32x4 v[J];
 #pragma unroll
@@ -38,36 +121,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
         }
 #pragma unroll
         for (int j = 0; j < J; ++j) {
-            sum[j] += v[j];
+            const f32x4 d = v[j] - f32x4{pv[j].x, pv[j].x, pv[j].y, pv[j].y};
+            sum[j] += d;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sq[j][e] = fmaf(v[j][e], v[j][e], sq[j][e]);
+            for (int e = 0; e < 4; ++e) sq[j][e] = fmaf(d[e], d[e], sq[j][e]);
         }
     }
-    // two rounds through one [4][C] LDS array (sums, then squares): 16*C bytes, 40 KB at C = 2560
-    float* mine = sm + wave * C;
-    float ts = 0.0f, tq = 0.0f;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int cv = lane + j * 64;
-        if (cv < CV) *reinterpret_cast<f32x4*>(mine + cv * 4) = sum[j];
-    }
-    __syncthreads();
-    if (tid < GROUPS)
-        for (int w = 0; w < 4; ++w)
-            for (int c = 0; c < cpg; ++c) ts += sm[w * C + tid * cpg + c];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int cv = lane + j * 64;
-        if (cv < CV) *reinterpret_cast<f32x4*>(mine + cv * 4) = sq[j];
-    }
-    __syncthreads();
-    if (tid < GROUPS) {
-        for (int w = 0; w < 4; ++w)
-            for (int c = 0; c < cpg; ++c) tq += sm[w * C + tid * cpg + c];
-        const float n = (float)(p1 - p0) * (float)cpg;
-        const float mean = n > 0 ? ts / n : 0.0f;
-        const float m2 = n > 0 ? fmaxf(tq - ts * mean, 0.0f) : 0.0f;
+    float n, mean, m2;
+    if (gn_reduce_records<J>(sm, C, cpg, GROUPS, p1 - p0, pv, sum, sq, n, mean, m2)) {
         float* o = partial + ((int64_t)(f * nchunk + chunk) * GROUPS + tid) * 3;
         o[0] = n; o[1] = mean; o[2] = m2;
     }
@@ -217,38 +278,91 @@ __global__ __launch_bounds__(512 / NIT) void gn_temporal_kernel(const float* __r
             off[it] = ((b * T) * Npix + pix) * C + c4 * 4;
             offo[it] = ((b * (T + 2 * t_pad) + t_pad) * Npix + pix) * C + c4 * 4;
 #pragma unroll
-            for (int t = 0; t < T; ++t) {
-                v[it][t] = *reinterpret_cast<const f32x4*>(x + off[it] + (int64_t)t * Npix * C);
-                s0 += v[it][t][0] + v[it][t][1]; q0 = fmaf(v[it][t][0], v[it][t][0], q0); q0 = fmaf(v[it][t][1], v[it][t][1], q0);
-                s1 += v[it][t][2] + v[it][t][3]; q1 = fmaf(v[it][t][2], v[it][t][2], q1); q1 = fmaf(v[it][t][3], v[it][t][3], q1);
+            for (int t = 0; t < T; ++t) v[it][t] = *reinterpret_cast<const f32x4*>(x + off[it] + (int64_t)t * Npix * C);
+            if constexpr (MODE == 0) {
+                // the mean of a channel pair as pivot + mean(x - pivot), the pivot its first value: the sum does not grow with
+                // mean / std.  (s0, s1) = the two pair means; the squares follow in a second pass over v, about the group mean.
+                const float pa = v[it][0][0], pb = v[it][0][2];
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    s0 += (v[it][t][0] - pa) + (v[it][t][1] - pa);
+                    s1 += (v[it][t][2] - pb) + (v[it][t][3] - pb);
+                }
+                s0 = fmaf(s0, 1.0f / (float)(2 * T), pa);
+                s1 = fmaf(s1, 1.0f / (float)(2 * T), pb);
+            } else {
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    s0 += v[it][t][0] + v[it][t][1]; q0 = fmaf(v[it][t][0], v[it][t][0], q0); q0 = fmaf(v[it][t][1], v[it][t][1], q0);
+                    s1 += v[it][t][2] + v[it][t][3]; q1 = fmaf(v[it][t][2], v[it][t][2], q1); q1 = fmaf(v[it][t][3], v[it][t][3], q1);
+                }
             }
         }
         if (wi < nwork) {
             float* d = s_part + ((size_t)pl * CP + c4 * 2) * 2;
-            d[0] = s0; d[1] = q0; d[2] = s1; d[3] = q1;
+            d[0] = s0; d[2] = s1;
+            if constexpr (MODE != 0) { d[1] = q0; d[3] = q1; }
         }
     }
     __syncthreads();
-    for (int gi = tid; gi < PB * GROUPS; gi += NT) {
-        const int pl = gi / GROUPS, g = gi - pl * GROUPS;
-        float s = 0.0f, q = 0.0f;
-        for (int j = 0; j < cpg2; ++j) {
-            const int wi = pl * CP + g * cpg2 + j;
-            s += s_part[wi * 2]; q += s_part[wi * 2 + 1];
+    if constexpr (MODE == 0) {
+        // two-pass statistics on the register-resident values: group mean = P + mean(pair mean - P), P = the group's first pair
+        // mean; then sum (x - group mean)^2 per pair, added up per group in the same fixed order
+        for (int gi = tid; gi < PB * GROUPS; gi += NT) {
+            const int pl = gi / GROUPS, g = gi - pl * GROUPS;
+            const float P = s_part[(pl * CP + g * cpg2) * 2];
+            float s = 0.0f;
+            for (int j = 0; j < cpg2; ++j) s += s_part[(pl * CP + g * cpg2 + j) * 2] - P;
+            s_stat[gi * 2] = P + s / (float)cpg2;
         }
-        if constexpr (MODE == 1) {                 // this rank's partial sums: the frame group adds them up
-            const int64_t bp = bp0 + pl;
-            if (bp < total) { stats[(bp * GROUPS + g) * 2] = s; stats[(bp * GROUPS + g) * 2 + 1] = q; }
-            continue;
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int wi = tid + it * NT;
+            if (wi >= nwork) continue;
+            const int pl = wi / C4, c4 = wi - pl * C4;
+            float q0 = 0.0f, q1 = 0.0f;
+            if (live[it]) {
+                const float ma = s_stat[(pl * GROUPS + (c4 * 2) / cpg2) * 2], mb = s_stat[(pl * GROUPS + (c4 * 2 + 1) / cpg2) * 2];
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const float d0 = v[it][t][0] - ma, d1 = v[it][t][1] - ma, d2 = v[it][t][2] - mb, d3 = v[it][t][3] - mb;
+                    q0 = fmaf(d0, d0, q0); q0 = fmaf(d1, d1, q0);
+                    q1 = fmaf(d2, d2, q1); q1 = fmaf(d3, d3, q1);
+                }
+            }
+            float* d = s_part + ((size_t)pl * CP + c4 * 2) * 2;
+            d[1] = q0; d[3] = q1;
         }
-        if constexpr (MODE == 2) {                 // the sums over all ranks' frames
-            const int64_t bp = bp0 + pl;
-            if (bp < total) { s = stats[(bp * GROUPS + g) * 2]; q = stats[(bp * GROUPS + g) * 2 + 1]; }
+        __syncthreads();
+        for (int gi = tid; gi < PB * GROUPS; gi += NT) {
+            const int pl = gi / GROUPS, g = gi - pl * GROUPS;
+            float q = 0.0f;
+            for (int j = 0; j < cpg2; ++j) q += s_part[(pl * CP + g * cpg2 + j) * 2 + 1];
+            s_stat[gi * 2 + 1] = rsqrtf(q / (float)(cpg2 * 2 * T) + eps);
         }
-        const float n = (float)(cpg2 * 2 * (MODE == 2 ? T_total : T));
-        const float mean = s / n;
-        const float var = fmaxf(q / n - mean * mean, 0.0f);
-        s_stat[gi * 2] = mean; s_stat[gi * 2 + 1] = rsqrtf(var + eps);
+    } else {
+        for (int gi = tid; gi < PB * GROUPS; gi += NT) {
+            const int pl = gi / GROUPS, g = gi - pl * GROUPS;
+            float s = 0.0f, q = 0.0f;
+            for (int j = 0; j < cpg2; ++j) {
+                const int wi = pl * CP + g * cpg2 + j;
+                s += s_part[wi * 2]; q += s_part[wi * 2 + 1];
+            }
+            if constexpr (MODE == 1) {                 // this rank's partial sums: the frame group adds them up
+                const int64_t bp = bp0 + pl;
+                if (bp < total) { stats[(bp * GROUPS + g) * 2] = s; stats[(bp * GROUPS + g) * 2 + 1] = q; }
+                continue;
+            }
+            if constexpr (MODE == 2) {                 // the sums over all ranks' frames
+                const int64_t bp = bp0 + pl;
+                if (bp < total) { s = stats[(bp * GROUPS + g) * 2]; q = stats[(bp * GROUPS + g) * 2 + 1]; }
+            }
+            const float n = (float)(cpg2 * 2 * T_total);
+            const float mean = s / n;
+            const float var = fmaxf(q / n - mean * mean, 0.0f);
+            s_stat[gi * 2] = mean; s_stat[gi * 2 + 1] = rsqrtf(var + eps);
+        }
     }
     if constexpr (MODE == 1) return;
     __syncthreads();
@@ -275,7 +389,7 @@ __global__ __launch_bounds__(512 / NIT) void gn_temporal_kernel(const float* __r
 }
 
 // ---- LayerNorm: one wave per row, LN_R rows per wave in flight (all loads issued before the first reduction),
-// float4 vectors, two-pass variance in registers ------------------------------------------------------------
+// float4 vectors, two-pass variance in registers (the second pass also corrects the mean) -------------------
 constexpr int LN_R = 4;
 template <int J>     // J = float4 vectors per lane = ceil(C / 256)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, int M, int C,
@@ -305,7 +419,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         g[j] = (cv < CV) ? *reinterpret_cast<const f32x4*>(gamma + cv * 4) : z;
         b[j] = (cv < CV) ? *reinterpret_cast<const f32x4*>(beta + cv * 4) : z;
     }
-    float mean[LN_R], rstd[LN_R];
+    float mean[LN_R], rstd[LN_R], corr[LN_R];
     const float invc = 1.0f / (float)C;
 #pragma unroll
     for (int r = 0; r < LN_R; ++r) {
@@ -318,28 +432,36 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
         for (int r = 0; r < LN_R; ++r) mean[r] += __shfl_xor(mean[r], o, 64);
+    // second pass about the first mean m0: the squares, and the sum of the differences — what the C roundings of sums of the
+    // mean's size left in m0 (a few 2^-24 |mean|) comes back as mean(x - m0): mean = m0 + that, var = mean((x - m0)^2) - that^2
 #pragma unroll
     for (int r = 0; r < LN_R; ++r) {
         mean[r] *= invc;
-        float q = 0.0f;
+        float q = 0.0f, s1 = 0.0f;
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             const int cv = lane + j * 64;
             if (cv < CV) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const float d = v[r][j][e] - mean[r]; q = fmaf(d, d, q); }
+                for (int e = 0; e < 4; ++e) { const float d = v[r][j][e] - mean[r]; q = fmaf(d, d, q); s1 += d; }
             }
         }
-        rstd[r] = q;
+        rstd[r] = q; corr[r] = s1;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
-        for (int r = 0; r < LN_R; ++r) rstd[r] += __shfl_xor(rstd[r], o, 64);
+        for (int r = 0; r < LN_R; ++r) { rstd[r] += __shfl_xor(rstd[r], o, 64); corr[r] += __shfl_xor(corr[r], o, 64); }
+#pragma unroll
+    for (int r = 0; r < LN_R; ++r) {
+        const float dm = corr[r] * invc;
+        mean[r] += dm;
+        rstd[r] = fmaf(-dm, dm, rstd[r] * invc);
+    }
 #pragma unroll
     for (int r = 0; r < LN_R; ++r) {
         if (row0 + r >= M) break;
-        const float rs = rsqrtf(rstd[r] * invc + eps);
+        const float rs = rsqrtf(rstd[r] + eps);
         half_t* yr = y + (row0 + r) * ldy;
 #pragma unroll
         for (int j = 0; j < J; ++j) {
@@ -407,7 +529,7 @@ __global__ __launch_bounds__(256) void concat_add_stats_kernel(const float* __re
                                                                const float* __restrict__ c, int C2, int Npix, int ppc,
                                                                float* __restrict__ out32, half_t* __restrict__ out16,
                                                                void* __restrict__ out16_lo, int lo_fmt, float* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];     // [4][Cs]: per-wave sums, then per-wave squares
+    extern __shared__ __attribute__((aligned(16))) float sm[];     // [4][Cs]: per-wave means, then per-wave M2; gps group means
     const int f = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x, S = gridDim.z, z = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = C1 + C2, cpg = C / GROUPS;
@@ -415,9 +537,10 @@ __global__ __launch_bounds__(256) void concat_add_stats_kernel(const float* __re
     const int p0 = chunk * ppc;
     const int p1 = min(Npix, p0 + ppc);
     f32x4 sum[J], sq[J];
+    float2 pv[J];
     const f32x4 zz = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int j = 0; j < J; ++j) { sum[j] = zz; sq[j] = zz; }
+    for (int j = 0; j < J; ++j) { sum[j] = zz; sq[j] = zz; pv[j] = make_float2(0.0f, 0.0f); }
 #pragma unroll 2
     for (int pix = p0 + wave; pix < p1; pix += 4) {
         const int64_t m = (int64_t)f * Npix + pix;
@@ -435,6 +558,7 @@ __global__ __launch_bounds__(256) void concat_add_stats_kernel(const float* __re
                 }
             }
         }
+        const bool first = pix == p0 + wave;                       // the pivots come from this wave's first pixel
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             const int cv = lane + j * 64, ch = c0 + cv * 4;
@@ -449,35 +573,15 @@ __global__ __launch_bounds__(256) void concat_add_stats_kernel(const float* __re
                     }
                 }
             }
-            sum[j] += v[j];
+            if (first) pv[j] = make_float2(v[j][0], v[j][2]);
+            const f32x4 d = v[j] - f32x4{pv[j].x, pv[j].x, pv[j].y, pv[j].y};
+            sum[j] += d;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sq[j][e] = fmaf(v[j][e], v[j][e], sq[j][e]);
+            for (int e = 0; e < 4; ++e) sq[j][e] = fmaf(d[e], d[e], sq[j][e]);
         }
     }
-    float* mine = sm + wave * Cs;
-    float ts = 0.0f, tq = 0.0f;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int cv = lane + j * 64;
-        if (cv < CVs) *reinterpret_cast<f32x4*>(mine + cv * 4) = sum[j];
-    }
-    __syncthreads();
-    if (tid < gps)
-        for (int w = 0; w < 4; ++w)
-            for (int cc = 0; cc < cpg; ++cc) ts += sm[w * Cs + tid * cpg + cc];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const int cv = lane + j * 64;
-        if (cv < CVs) *reinterpret_cast<f32x4*>(mine + cv * 4) = sq[j];
-    }
-    __syncthreads();
-    if (tid < gps) {
-        for (int w = 0; w < 4; ++w)
-            for (int cc = 0; cc < cpg; ++cc) tq += sm[w * Cs + tid * cpg + cc];
-        const float n = (float)(p1 - p0) * (float)cpg;
-        const float mean = n > 0 ? ts / n : 0.0f;
-        const float m2 = n > 0 ? fmaxf(tq - ts * mean, 0.0f) : 0.0f;
+    float n, mean, m2;
+    if (gn_reduce_records<J>(sm, Cs, cpg, gps, p1 - p0, pv, sum, sq, n, mean, m2)) {
         float* o = partial + ((int64_t)(f * nchunk + chunk) * GROUPS + z * gps + tid) * 3;
         o[0] = n; o[1] = mean; o[2] = m2;
     }
@@ -504,7 +608,7 @@ extern "C" int pnc_groupnorm_stats(const float* x, int ldx, int F, int Npix, int
     if (C % 64 || C > GN_MAXC || ldx % 4) return PNC_EINVAL;
     if ((uintptr_t)x & 15) return PNC_EALIGN;
     const int nchunk = (Npix + pix_per_chunk - 1) / pix_per_chunk;
-    const size_t lds = (size_t)4 * C * sizeof(float);
+    const size_t lds = ((size_t)4 * C + GROUPS) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     PNC_GN_DISPATCH(gn_stats_kernel, dim3(nchunk, F), dim3(256), lds, st, x, ldx, Npix, C, pix_per_chunk, partial);
     return pnc_launch_status();
@@ -524,7 +628,7 @@ extern "C" int pnc_concat_add_stats(const float* a, int C1, const float* s, cons
     while (S < 8 && (C / S / 4 + 63) / 64 > 3 && (C / (2 * S)) % 4 == 0) S *= 2;        // slices of whole groups AND whole float4 vectors
     if ((C / S / 4 + 63) / 64 > 3) return PNC_EINVAL;
     const int J = (C / S / 4 + 63) / 64;
-    const size_t lds = (size_t)4 * (C / S) * sizeof(float);
+    const size_t lds = ((size_t)4 * (C / S) + GROUPS) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     half_t* o16 = reinterpret_cast<half_t*>(out16);
     const dim3 grid(nchunk, F, S);

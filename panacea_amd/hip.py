@@ -338,6 +338,35 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
     format (fp16, or uint8 = e4m3 bytes).  `w_lo` = (W_lo e4m3 bytes [N, K], w_lo_exp E8M0 byte of the tensor) — engine.pk_lo8 —
     is the weight side of an e4m3 lo pass; `w_lo` = an fp16 tensor in w16's layout is the lo plane of split weights (engine.wlo under
     the `precise-full` policy, PncGemmParams.W_lo): it goes with an fp16 `a16_lo`."""
+    p, lib, _ws = _gemm_params(a16, w16, M=M, N=N, K=K, lda=lda, a_mode=a_mode, conv=conv, tconv=tconv, bias=bias, rowbias=rowbias,
+                               rb_rows=rb_rows, rb_mod=rb_mod, res1=res1, ldr1=ldr1, res2=res2, ldr2=ldr2, out32=out32, ldc32=ldc32,
+                               out16=out16, ldc16=ldc16, out16t=out16t, ldt=ldt, t_rows=t_rows, t_gstride=t_gstride, n_split=n_split,
+                               act=act, geglu=geglu, a16_lo=a16_lo, out16_lo=out16_lo, w_ld=w_ld, w_lo=w_lo, ln_gamma=ln_gamma,
+                               ln_beta=ln_beta, ln_out16=ln_out16, ldln=ldln, ln_eps=ln_eps, gn_part=gn_part)
+    fam = ("gemm_plain", "gemm_conv3x3", "gemm_conv1d_t")[a_mode]
+    trailing_ln = ln_out16 is not None and not ln_in_library and not lib.pnc_gemm_fuses_layernorm(C.byref(p))
+    if trailing_ln:
+        # rows span several workgroups: the library would launch its LayerNorm kernel after the GEMM.  Issue the two launches
+        # from here instead (the same two kernels) so that the per-family timing of bench.py sees them separately.
+        p.ln_gamma = p.ln_beta = p.ln_out16 = None
+    _check(_timed(fam, 2.0 * M * N * K, 0.0, lib.pnc_gemm_f16, C.byref(p), _stream()), "pnc_gemm_f16")
+    if trailing_ln:
+        layernorm(out32, ldc32, M, N, ln_gamma, ln_beta, ln_eps, ln_out16, ldln)
+
+
+def gemm_fuses_layernorm(**kw) -> bool:
+    """pnc_gemm_fuses_layernorm for the arguments of `gemm`: does the launch normalise its rows in its own epilogue?"""
+    kw.pop("ln_in_library", None)
+    p, lib, _ws = _gemm_params(**kw, workspace=False)
+    return bool(lib.pnc_gemm_fuses_layernorm(C.byref(p)))
+
+
+def _gemm_params(a16, w16, *, M, N, K, lda=0, a_mode=A_PLAIN, conv=None, tconv=None, bias=None, rowbias=None, rb_rows=0, rb_mod=0,
+                 res1=None, ldr1=0, res2=None, ldr2=0, out32=None, ldc32=0, out16=None, ldc16=0, out16t=None, ldt=0, t_rows=0,
+                 t_gstride=0, n_split=0, act=ACT_NONE, geglu=False, a16_lo=None, out16_lo=None, w_ld=0, w_lo=None, ln_gamma=None,
+                 ln_beta=None, ln_out16=None, ldln=0, ln_eps=1e-5, gn_part=None, workspace=True):
+    """-> (PncGemmParams of the arguments of `gemm`, the library, the split-K workspace the struct points to or None); workspace =
+    False: a struct for a query only, no workspace is allocated"""
     p = GemmParams()
     p.struct_bytes = C.sizeof(GemmParams)
     f16, f32 = torch.float16, torch.float32
@@ -375,18 +404,10 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
     lib = load()
     nws = lib.pnc_gemm_workspace_floats(C.byref(p))      # > 0: the library wants to split K (small-M shapes)
     ws = None
-    if nws > 0:
+    if nws > 0 and workspace:
         ws = torch.empty(nws, device=a16.device, dtype=torch.float32)
         p.ws, p.ws_floats = _ptr(ws), nws
-    fam = ("gemm_plain", "gemm_conv3x3", "gemm_conv1d_t")[a_mode]
-    trailing_ln = ln_out16 is not None and not ln_in_library and not lib.pnc_gemm_fuses_layernorm(C.byref(p))
-    if trailing_ln:
-        # rows span several workgroups: the library would launch its LayerNorm kernel after the GEMM.  Issue the two launches
-        # from here instead (the same two kernels) so that the per-family timing of bench.py sees them separately.
-        p.ln_gamma = p.ln_beta = p.ln_out16 = None
-    _check(_timed(fam, 2.0 * M * N * K, 0.0, lib.pnc_gemm_f16, C.byref(p), _stream()), "pnc_gemm_f16")
-    if trailing_ln:
-        layernorm(out32, ldc32, M, N, ln_gamma, ln_beta, ln_eps, ln_out16, ldln)
+    return p, lib, ws
 
 
 def _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
