@@ -42,7 +42,8 @@ const char* pnc_version(void);
  *  weights, + pnc_linear_smallm_split / pnc_linear_smallm_segments_split.  One check is stricter for existing callers: a non-NULL
  *  PncGemmParams.W_lo with A_lo = NULL, which pnc_gemm_f16 used to ignore, is now PNC_EINVAL — clear the field with A_lo;
  *  still 8 (additive): + pnc_attn_uses_text_kernel.  One dispatch is narrower: the few-key kernel takes key buffers whose row count
- *  kvH * kvW is a multiple of 8 only, a ragged buffer (77 rows) runs on the general kernel — same attention, see PncAttnParams.kv_valid) */
+ *  kvH * kvW is a multiple of 8 only, a ragged buffer (77 rows) runs on the general kernel — same attention, see PncAttnParams.kv_valid;
+ *  still 8 (additive): + pnc_gemm_wsplit_f16) */
 #define PNC_ABI_VERSION 8
 int pnc_abi_version(void);
 /* hex SHA-256 of the sources + compile flags the library was built from (panacea_amd/build.py computes the same digest over
@@ -252,6 +253,22 @@ typedef struct PncGemmParams {
 } PncGemmParams;
 
 int pnc_gemm_f16(const PncGemmParams* p, void* stream);
+/* pnc_gemm_f16 with SPLIT WEIGHTS BESIDE the parameter block (the `precise-ckpt` operand policy: the operand classes and e4m3 lo planes
+ * of `precise`, on an fp32 checkpoint).  W_lo16[n][k] = fp16((w - fp16(w)) * 2^11) is the fp16 lo plane of the weights as in
+ * PncGemmParams.W_lo: W's layout, K order and leading dimension (p->ldw), 16-byte aligned.  *p is validated exactly as by pnc_gemm_f16
+ * and keeps every meaning it has there — p->W_lo stays the e4m3 copy that goes with an e4m3 A_lo, and is NULL otherwise.
+ *   p->A_lo NULL or e4m3: the weight part runs FIRST — the K tiles (of the slice, when K is split) with A's hi plane against W_lo16 into
+ *     zeroed accumulators, then the one exact 2^-11 scaling — followed by the launch as pnc_gemm_f16 runs it (the e4m3 lo tiles, whose
+ *     block scale lands their products at their final weight, then the hi pass):
+ *         A w ~= A_hi W_hi + 2^-11 (A_lo W_hi [if A_lo] + A_hi W_lo16)
+ *     One more fp16 pass over K.  With W_lo16 all zero the result is bit-identical to pnc_gemm_f16(p).  The tile and split-K choice,
+ *     pnc_gemm_workspace_floats and pnc_gemm_fuses_layernorm answer for this launch what they answer for pnc_gemm_f16(p); the
+ *     persistent GEGLU kernel (PNC_OPT_GEMM_PERSIST bit 0) runs the part in the same order; the persistent plain-A kernel (bit 1) has
+ *     none: its launches run one tile per workgroup on the same tiles.
+ *   p->A_lo fp16: FORWARDED to pnc_gemm_f16 with W_lo = W_lo16 (the three-part launch described at PncGemmParams.W_lo); a non-NULL
+ *     p->W_lo next to it is PNC_EINVAL.
+ * W_lo16 NULL: PNC_EINVAL.  W_lo16 not 16-byte aligned: PNC_EALIGN. */
+int pnc_gemm_wsplit_f16(const PncGemmParams* p, const void* W_lo16, void* stream);
 /* 1 when pnc_gemm_f16 would reduce p->ln_* inside the GEMM epilogue for this problem, 0 when it would launch its LayerNorm
  * kernel after the GEMM (a caller that times kernel families separately can then issue pnc_layernorm itself) */
 int pnc_gemm_fuses_layernorm(const PncGemmParams* p);

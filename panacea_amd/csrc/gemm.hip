@@ -10,6 +10,10 @@ namespace pnc_gemm {
 int dispatch_plain(const PncGemmParams& p, unsigned epi, hipStream_t st, bool* ln_fused);
 int dispatch_conv3x3(const PncGemmParams& p, unsigned epi, hipStream_t st);
 int dispatch_conv1d(const PncGemmParams& p, unsigned epi, hipStream_t st);
+// the same with the weight part (gemm_*_ws.hip): wlo16 = the fp16 lo plane of W beside the parameter block
+int dispatch_plain_ws(const PncGemmParams& p, unsigned epi, hipStream_t st, bool* ln_fused, const void* wlo16);
+int dispatch_conv3x3_ws(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16);
+int dispatch_conv1d_ws(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16);
 
 __device__ __attribute__((aligned(16))) float g_phi_table[2 * PHI_N];
 
@@ -267,6 +271,35 @@ extern "C" int pnc_gemm_f16(const PncGemmParams* pp, void* stream) {
         default: rc2 = dispatch_conv1d(p, epi, st); break;
     }
     if (rc2 == PNC_OK && p.ln_out16 && !ln_fused)      // rows span several workgroups (or a generic launch): the LayerNorm kernel
+        rc2 = pnc_layernorm(p.out32, p.ldc32, p.M, p.N, p.ln_gamma, p.ln_beta, p.ln_eps, p.ln_out16, p.ldln, nullptr, stream);
+    return rc2;
+}
+
+// pnc_gemm_f16 with the fp16 lo plane of the weights BESIDE the parameter block (include/panacea_hip.h)
+extern "C" int pnc_gemm_wsplit_f16(const PncGemmParams* pp, const void* W_lo16, void* stream) {
+    if (!pp || !W_lo16) return PNC_EINVAL;
+    const int rc = validate(*pp);
+    if (rc != PNC_OK) return rc;
+    if ((uintptr_t)W_lo16 & 15) return PNC_EALIGN;
+    if (pp->A_lo && pp->a_lo_fmt == PNC_LO_F16) {
+        // an fp16 A_lo: the three-part launch pnc_gemm_f16 already has, the plane in the place that launch reads it from
+        if (pp->W_lo) return PNC_EINVAL;
+        PncGemmParams q = *pp;
+        q.W_lo = W_lo16; q.ldw_lo = 0;
+        return pnc_gemm_f16(&q, stream);
+    }
+    PncGemmParams p = *pp;
+    normalise(p);
+    const unsigned epi = epilogue_with_ln(p);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    bool ln_fused = false;
+    int rc2;
+    switch (p.a_mode) {
+        case PNC_A_PLAIN: rc2 = dispatch_plain_ws(p, epi, st, &ln_fused, W_lo16); break;
+        case PNC_A_CONV3X3: rc2 = dispatch_conv3x3_ws(p, epi, st, W_lo16); break;
+        default: rc2 = dispatch_conv1d_ws(p, epi, st, W_lo16); break;
+    }
+    if (rc2 == PNC_OK && p.ln_out16 && !ln_fused)
         rc2 = pnc_layernorm(p.out32, p.ldc32, p.M, p.N, p.ln_gamma, p.ln_beta, p.ln_eps, p.ln_out16, p.ldln, nullptr, stream);
     return rc2;
 }

@@ -767,549 +767,31 @@ __device__ __forceinline__ void epi_generic(const PncGemmParams& p, f32x16 (&acc
     });
 }
 
+// gemm_glds_body.inc is the kernel body, shared as TEXT by the two kernels below (a device function taking the parameter block by
+// reference changed the code of the existing instantiations: the block is read from the kernel arguments in another order).
+// WS (compile time; pnc_gemm_wsplit_f16): `wlo16` is the fp16 lo plane of the weights, in W's layout and leading dimension, travelling
+// BESIDE the parameter block, whose A_lo is NULL or e4m3 and whose W_lo keeps its e4m3 meaning.  The weight part runs first: the
+// slice's K tiles, A's hi plane against wlo16, into the zeroed accumulators, then the one exact 2^-11 scaling; the e4m3 lo tiles
+// (their block scale lands them at their final weight) and the hi pass follow unchanged:
+//   A W ~= A_hi W_hi + 2^-11 (A_lo W_hi + A_hi W_lo).   With wlo16 all zero the part leaves +0 everywhere: the bits of WS = false.
 template <int AMODE, int BM, int BN, int WGM, int WGN, int STAGES, bool PIPE, unsigned EPI>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_glds_kernel(const PncGemmParams pin, const int ksplit,
                                                                    const int nfull, const int tail_f,
                                                                    const float* __restrict__ phi_g, const int group_m,
                                                                    const int stagger_min_in) {
-    PncGemmParams p = pin;
-    constexpr int NW = WGM * WGN;                          // waves per workgroup
-    constexpr int MI = BM / WGM / 32, NI = BN / WGN / 32;
-    constexpr int RPI = NW * 8;                            // rows staged per DMA iteration (8 rows per wave)
-    constexpr int A_IT = BM / RPI, B_IT = BN / RPI;
-    constexpr int LOADS = A_IT + B_IT;                     // DMA instructions per thread per K tile
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
-    static_assert(BM % RPI == 0 && BN % RPI == 0, "tile rows must be a multiple of the DMA row group");
-    constexpr int ENI = NI < 2 ? NI : 2;                   // column blocks staged per epilogue pass
-    constexpr int EPITCH = ENI * 32 + 4;                   // floats per staged epilogue row
-    constexpr bool GEGLU = (EPI & E_GEGLU) != 0;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool WS = false;
+    const void* const wlo16 = nullptr;
+#include "gemm_glds_body.inc"
+}
 
-    const half_t* __restrict__ A = reinterpret_cast<const half_t*>(p.A);
-    const half_t* __restrict__ A_lo = reinterpret_cast<const half_t*>(p.A_lo);
-    const half_t* __restrict__ Wt = reinterpret_cast<const half_t*>(p.W);
-
-    const int tiles_n = (p.N + BN - 1) / BN;
-    const int tiles_m = (p.M + BM - 1) / BM;
-    // split K (ksplit > 1): block b = (slice, tile); slice s runs K tiles [s*nt/S, (s+1)*nt/S) and writes its raw fp32
-    // accumulators to ws[s][M][N] (the host launches the E_O32 variant with the epilogue options cleared);
-    // splitk_reduce_kernel sums the slices in order and applies the epilogue.
-    // Tail split (tail_f = 2 or 4): the last (ntile_mn - nfull) output tiles - the partial round that would leave most
-    // CUs idle - are each run by tail_f workgroups that own BM / tail_f rows of the tile: the waves of the other row
-    // groups skip their MFMAs and epilogue (their A rows are DMA'd as out-of-bounds offsets = zeros), all waves still stage W.  Rows are
-    // independent in a GEMM, so the result does not depend on the split.
-    const int ntile_mn = tiles_m * tiles_n;
-    int kslice = 0, tile, part = 0;
-    if (ksplit > 1) {
-        const int blk = xcd_remap(blockIdx.x, ntile_mn * ksplit);
-        kslice = blk / ntile_mn; tile = blk - kslice * ntile_mn;
-    } else if ((int)blockIdx.x < nfull) {
-        tile = xcd_remap(blockIdx.x, nfull);
-    } else {
-        const int j = (int)blockIdx.x - nfull;
-        tile = nfull + j / tail_f; part = j - (j / tail_f) * tail_f;
-    }
-    const bool split_rows = (ksplit == 1) && ((int)blockIdx.x >= nfull) && (tail_f > 1);
-    // Tile id -> (tm, tn).  Default: tn fastest, so the ~32 tiles an XCD runs at once are 32 / tiles_n row panels x all
-    // column tiles.  With many column tiles (FF1: 10-40, QKV at C = 1280: 12-15) that is ONE panel against the whole of W,
-    // and where W exceeds the 4 MB L2 (every level but 0) W is re-streamed from the fabric once per row panel: 1.26 GB per
-    // FF1 launch at every level (profiles/round2/pmc_precise_fetch_by_kernel.txt: 52 GB per step in the GEGLU kernel alone).
-    // group_m > 0: walk group_m row panels x the column tiles instead (tm fastest inside a group), so the concurrent set
-    // is group_m x (32 / group_m) tiles and each W column tile is fetched once per GROUP of panels.  Same tiles, same
-    // arithmetic: results are bit-identical.
-    int tn, tm;
-    if (group_m > 0) {
-        const int width = group_m * tiles_n;
-        const int gid = tile / width, first_m = gid * group_m;
-        const int gsz = min(tiles_m - first_m, group_m);
-        const int in = tile - gid * width;
-        tm = first_m + in % gsz; tn = in / gsz;
-    } else {
-        tn = tile % tiles_n; tm = tile / tiles_n;
-    }
-    if constexpr (AMODE == PNC_A_CONV1D_T) {
-        // Temporal conv: the three taps of a row panel are the panels of frames t - 1, t, t + 1 at the SAME pixels — with the row
-        // panels in memory order (frame-major) the panel of frame t is fetched again, ~48 panels later and mostly on another
-        // XCD, for frame t + 1 and t - 1: the operand crossed the fabric three times (profiles/round4: 11.2 GB per step for the
-        // first temporal site against 6.2 GB of operands).  Walk the panels FRAME-FASTEST instead (pixel block outer): the
-        // consecutive tile ids one XCD works through are the frames of one pixel block, and two of the three reads hit its L2.
-        // A permutation of the row panels: same tiles, same arithmetic.
-        const int pb_n = p.Npix / BM;                        // row panels per frame
-        if (pb_n * BM == p.Npix && pb_n > 1) {
-            const int nbt = tiles_m / pb_n;                  // frames (b, t) of the launch
-            tm = (tm % nbt) * pb_n + tm / nbt;
-        }
-    }
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int ntiles_all = (p.K + BK - 1) / BK;
-    const int kt_begin = (int)((int64_t)kslice * ntiles_all / ksplit);
-    const int ntiles = (int)((int64_t)(kslice + 1) * ntiles_all / ksplit) - kt_begin;
-    if (ksplit > 1) p.out32 = p.ws + (int64_t)kslice * p.M * p.N;
-    // precise operand: the lo plane's K tiles run first.  fp16 lo plane: the same K tiles as the hi plane, then the accumulators
-    // are scaled by 2^-11.  e4m3 lo plane (lo8): 128 k per 128-byte LDS row -> half the tiles, DMA pieces and barriers; the
-    // block-scaled fp8 MFMA carries the 2^-11 as its A scale and the weight row's exponent as its B scale, so the lo products
-    // land in the accumulators at their final weight and the hi pass simply continues.
-    const bool lo8 = A_lo && p.a_lo_fmt == PNC_LO_E4M3;
-    const int nlo_all = lo8 ? (p.K + BK8 - 1) / BK8 : ntiles_all;
-    const int kt_begin_lo = (int)((int64_t)kslice * nlo_all / ksplit);
-    const int nt_alo = A_lo ? (int)((int64_t)(kslice + 1) * nlo_all / ksplit) - kt_begin_lo : 0;
-    // split weights (fp16 W_lo next to an fp16 A_lo): the lo pass runs the slice's K tiles a second time, A's hi plane against W_lo,
-    // before the scaling — a slice of a split-K launch runs its own K range in all three parts
-    const bool wl16 = A_lo && !lo8 && p.W_lo != nullptr;
-    const int nt_lo = wl16 ? 2 * nt_alo : nt_alo;
-    const int ntot = ntiles + nt_lo;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: LDS-DMA destinations (M0) and wave-row tests stay on the SALU
-    const int wm = wave / WGN, wn = wave % WGN;
-
-    // DMA assignment: lane l of wave w fills slot (l&7) of row i*32 + w*8 + (l>>3); the slot holds the
-    // chunk slot ^ ((row>>1)&7), and (row>>1)&7 does not depend on i
-    const int srow = wave * 8 + (lane >> 3);
-    const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
-    const int rows_lo = split_rows ? part * (BM / tail_f) : 0;                 // tile-local row range of this workgroup
-    const int rows_hi = split_rows ? rows_lo + BM / tail_f : BM;
-    const bool wave_on = (wm * (MI * 32) >= rows_lo) && (wm * (MI * 32) < rows_hi);
-    RowState rows[A_IT];
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) {
-        const int r = i * RPI + srow;
-        rows[i] = make_row<AMODE>(p, m0 + r, m0);
-        rows[i].valid = rows[i].valid && (r >= rows_lo) && (r < rows_hi);
-    }
-    // buffer resources: the A plane(s) from the tile's window origin, W from the tile's first row.  A row's offset is fixed over
-    // the K loop for plain A and for W (the K tile enters as the scalar offset); the gathers recompute theirs per K tile.
-    const int64_t a_origin = a_window_origin<AMODE>(p, m0);
-    const buffer_rsrc_t rs_a = make_rsrc(A + a_origin, 0x7FFFFF00u);
-    const buffer_rsrc_t rs_alo = make_rsrc(lo8 ? static_cast<const void*>(reinterpret_cast<const char*>(p.A_lo) + a_origin)
-                                               : static_cast<const void*>((A_lo ? A_lo : A) + a_origin), 0x7FFFFF00u);
-    const buffer_rsrc_t rs_whi = make_rsrc(Wt + (int64_t)n0 * p.ldw, 0x7FFFFF00u);
-    const buffer_rsrc_t rs_wlo = make_rsrc(lo8 ? static_cast<const void*>(reinterpret_cast<const char*>(p.W_lo) + (int64_t)n0 * p.ldw_lo)
-                                               : static_cast<const void*>((wl16 ? reinterpret_cast<const half_t*>(p.W_lo) : Wt) + (int64_t)n0 * p.ldw),
-                                           0x7FFFFF00u);
-    unsigned woff[B_IT], aoff[A_IT];
-#pragma unroll
-    for (int i = 0; i < B_IT; ++i) {
-        const int nl = i * RPI + srow;
-        woff[i] = (n0 + nl < p.N) ? (unsigned)(nl * p.ldw + schunk * 8) * 2u : PNC_BUF_OOB;
-    }
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i)
-        aoff[i] = (AMODE == PNC_A_PLAIN && rows[i].valid) ? (unsigned)(rows[i].rel + schunk * 8) * 2u : PNC_BUF_OOB;
-    const int kt_tail = (p.K & (BK - 1)) ? ntiles_all - 1 : -1;      // the one K tile with chunks beyond K, if any
-    // DMA pieces [Q0, Q1) of K tile kt_local into `stage` (pieces 0 .. A_IT-1: the A row groups, A_IT .. LOADS-1: the W row groups;
-    // the range is compile-time so that the staggered schedule below can spread a tile's pieces over its phases)
-    auto issue_part = [&](int kt_local, int stage, auto q0_, auto q1_) __attribute__((always_inline)) {
-        constexpr int Q0 = decltype(q0_)::value, Q1 = decltype(q1_)::value;
-        const bool lo = kt_local < nt_lo;
-        char* sa = smem + stage * STAGE + wave * 1024;
-        char* sb = sa + A_BYTES;
-        if (lo && lo8) {                                 // (uniform) e4m3 tile: chunk = 16 k, byte offsets = element offsets
-            // The lane offsets of this branch are derived from the hi pass's on the spot.  Opaque copies of the two lane constants
-            // keep hipcc from hoisting them out of the K loop as a second set of loop invariants: next to 160 accumulator
-            // registers the kernel has ~12 VGPRs to spare, and 9-20 more invariants spilled 100-300 registers (round 3).
-            int schunk8 = schunk, srow8 = srow;
-            asm volatile("" : "+v"(schunk8), "+v"(srow8));
-            const int kt8 = kt_begin_lo + kt_local;
-            const int kc8 = kt8 * BK8 + schunk8 * 16;
-            const unsigned ks8 = (unsigned)kt8 * BK8;
-            const bool k_on = kc8 < p.K;                 // false only in the chunks of the last tile beyond K
-#pragma unroll
-            for (int i = 0; i < A_IT; ++i) {
-                if (i < Q0 || i >= Q1) continue;
-                if constexpr (AMODE == PNC_A_PLAIN)      // (rel + 8 schunk) * 2 -> rel + 16 schunk
-                    glds16_buf(rs_alo, (k_on && aoff[i] != PNC_BUF_OOB) ? (aoff[i] >> 1) + (unsigned)schunk8 * 8u : PNC_BUF_OOB, ks8,
-                               sa + i * (RPI * 128));
-                else glds16_buf(rs_alo, a_chunk_off<AMODE, 1u>(p, rows[i], kc8), 0u, sa + i * (RPI * 128));
-            }
-#pragma unroll
-            for (int i = 0; i < B_IT; ++i) {
-                if (A_IT + i < Q0 || A_IT + i >= Q1) continue;
-                glds16_buf(rs_wlo, (k_on && woff[i] != PNC_BUF_OOB) ? (unsigned)((i * RPI + srow8) * p.ldw_lo + schunk8 * 16) : PNC_BUF_OOB,
-                           ks8, sb + i * (RPI * 128));
-            }
-            return;
-        }
-        const bool wl = lo && kt_local >= nt_alo;        // (uniform) second part of an fp16 lo pass: (A hi plane, W lo plane)
-        const int kt = (lo ? kt_begin_lo - (wl ? nt_alo : 0) : kt_begin - nt_lo) + kt_local;
-        // (one flat select per resource on a precomputed flag: with a short-circuit condition or a nested select here hipcc kept the
-        // closure, and with it the parameter block, in scratch memory — 624 B per lane in every variant)
-        const bool alo = lo & !wl;
-        const buffer_rsrc_t rs = alo ? rs_alo : rs_a;
-        const buffer_rsrc_t rs_w = wl ? rs_wlo : rs_whi;
-        const int kc = kt * BK + schunk * 8;
-        const unsigned ks = (unsigned)kt * (BK * 2);     // the K tile as the scalar byte offset of plain rows
-        if (kt != kt_tail) {                             // (uniform) no per-lane predicate on the K index
-#pragma unroll
-            for (int i = 0; i < A_IT; ++i) {
-                if (i < Q0 || i >= Q1) continue;
-                if constexpr (AMODE == PNC_A_PLAIN) glds16_buf(rs, aoff[i], ks, sa + i * (RPI * 128));
-                else glds16_buf(rs, a_chunk_off<AMODE>(p, rows[i], kc), 0u, sa + i * (RPI * 128));
-            }
-#pragma unroll
-            for (int i = 0; i < B_IT; ++i) {
-                if (A_IT + i < Q0 || A_IT + i >= Q1) continue;
-                glds16_buf(rs_w, woff[i], ks, sb + i * (RPI * 128));
-            }
-        } else {
-            const bool k_on = kc < p.K;
-#pragma unroll
-            for (int i = 0; i < A_IT; ++i) {
-                if (i < Q0 || i >= Q1) continue;
-                if constexpr (AMODE == PNC_A_PLAIN) glds16_buf(rs, k_on ? aoff[i] : PNC_BUF_OOB, ks, sa + i * (RPI * 128));
-                else glds16_buf(rs, a_chunk_off<AMODE>(p, rows[i], kc), 0u, sa + i * (RPI * 128));
-            }
-#pragma unroll
-            for (int i = 0; i < B_IT; ++i) {
-                if (A_IT + i < Q0 || A_IT + i >= Q1) continue;
-                glds16_buf(rs_w, k_on ? woff[i] : PNC_BUF_OOB, ks, sb + i * (RPI * 128));
-            }
-        }
-    };
-    auto issue_tile = [&](int kt_local, int stage) __attribute__((always_inline)) {
-        issue_part(kt_local, stage, std::integral_constant<int, 0>{}, std::integral_constant<int, LOADS>{});
-    };
-
-    // GEGLU: the Phi table rides into LDS (behind the operand ring) with the first K tile
-    constexpr int RING_BYTES = STAGES * STAGE;
-    if constexpr (GEGLU) {
-        const char* tab = reinterpret_cast<const char*>(phi_g);
-#pragma unroll
-        for (int c = wave; c < PHI_BYTES / 1024; c += NW)
-            glds16(reinterpret_cast<const half_t*>(tab + c * 1024 + lane * 16), smem + RING_BYTES + c * 1024);
-    }
-
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    const int frow = lane & 31, fk = lane >> 5;
-    auto compute = [&](int stage, int mid_issue = -1) {
-        const char* sa = smem + stage * STAGE;
-        const char* sb = sa + A_BYTES;
-        if (PIPE) {
-            // fragments of k-step ks+1 are read while the MFMAs of k-step ks run (register double buffer)
-            half8v af[2][MI], bf[2][NI];
-            auto frags = [&](int ks, int b) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-                    af[b][i] = *reinterpret_cast<const half8v*>(
-                        sa + lds_off128(wm * (MI * 32) + i * 32 + frow, ks * 2 + fk));
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    bf[b][j] = *reinterpret_cast<const half8v*>(
-                        sb + lds_off128(wn * (NI * 32) + j * 32 + frow, ks * 2 + fk));
-            };
-            frags(0, 0);
-#pragma unroll
-            for (int ks = 0; ks < BK / 16; ++ks) {
-                if (ks + 1 < BK / 16) frags(ks + 1, (ks + 1) & 1);
-                // keep the reads of k-step ks+1 AHEAD of the MFMAs of k-step ks (hipcc otherwise sinks them behind the
-                // MFMAs and then waits lgkmcnt(0) right after issuing them, exposing the LDS latency every k-step)
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks == 1 && mid_issue >= 0) { issue_tile(mid_issue, mid_issue & 1); __builtin_amdgcn_sched_barrier(0); }
-            }
-        } else {
-#pragma unroll
-            for (int ks = 0; ks < BK / 16; ++ks) {
-                half8v af[MI], bf[NI];
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-                    af[i] = *reinterpret_cast<const half8v*>(
-                        sa + lds_off128(wm * (MI * 32) + i * 32 + frow, ks * 2 + fk));
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    bf[j] = *reinterpret_cast<const half8v*>(
-                        sb + lds_off128(wn * (NI * 32) + j * 32 + frow, ks * 2 + fk));
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-                if (ks == 1 && mid_issue >= 0) issue_tile(mid_issue, mid_issue & 1);
-            }
-        }
-    };
-    // e4m3 lo tile: two MFMA windows of 64 k (the last tile of K = 320 holds one).  Lane (row r, group g) supplies bytes
-    // 32 g .. 32 g + 31 of the window for both operands (element j of a lane group pairs with element j of the same group of the
-    // other operand: tools/exp/mx_mfma_probe.hip) = chunks 2g, 2g+1 of the window: two ds_read_b128 per fragment, same swizzle.
-    auto compute8 = [&](int stage, int kt_local) {
-        const char* sa = smem + stage * STAGE;
-        const char* sb = sa + A_BYTES;
-        const int nwin = (p.K - (kt_begin_lo + kt_local) * BK8) > 64 ? 2 : 1;
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-            if (w < nwin) {
-                i32x8 af[MI];
-#pragma unroll
-                for (int i = 0; i < MI; ++i) {
-                    const int row = wm * (MI * 32) + i * 32 + frow;
-                    const i32x4 a0 = *reinterpret_cast<const i32x4*>(sa + lds_off128(row, w * 4 + fk * 2));
-                    const i32x4 a1 = *reinterpret_cast<const i32x4*>(sa + lds_off128(row, w * 4 + fk * 2 + 1));
-                    af[i] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-#pragma unroll
-                for (int j = 0; j < NI; ++j) {
-                    const int row = wn * (NI * 32) + j * 32 + frow;
-                    const i32x4 b0 = *reinterpret_cast<const i32x4*>(sb + lds_off128(row, w * 4 + fk * 2));
-                    const i32x4 b1 = *reinterpret_cast<const i32x4*>(sb + lds_off128(row, w * 4 + fk * 2 + 1));
-                    const i32x8 bf = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                    for (int i = 0; i < MI; ++i)
-                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[i], bf, acc[i][j], 0, 0, 0, E8M0_LO_INV, 0, p.w_lo_exp);
-                    // one B fragment (8 registers) in flight: hipcc otherwise hoists the reads of all NI column blocks (40 registers
-                    // at NI = 5) above the first MFMA and spills next to the 160 accumulator registers
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    };
-    auto scale_lo = [&]() {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] *= LO_INV;
-    };
-
-    // The second-dispatched half of an 8-wave workgroup loses every issue arbitration by age (MI355X_MICROARCH.md, two waves per
-    // SIMD): static priority for it.  Plain-A GEMMs -1.9 ms per step in a same-box A/B; the gathers (+0.3 / +0.4 ms) keep age order.
-    // STAGGERED schedule (round 5; 8-wave geometries on two stages, PNC_OPT_GEMM_STAGGER): a K tile is four PHASES, one per k-step —
-    //     fragment reads of the k-step + a third of the NEXT tile's DMA pieces | s_barrier | MI x NI MFMAs | s_barrier
-    // and waves 4-7 (the second wave of every SIMD) run ONE barrier behind waves 0-3: while one wave of a SIMD is in its MFMA
-    // cluster the other reads its fragments and issues its DMA, and the barriers hold that alternation (the two-group form of the
-    // HIP guide's 256^2 8-phase template on this kernel's stages).  vmcnt(0) once per K tile, before the first barrier of phase 3 — a
-    // whole MFMA cluster after the last DMA issue —, together with lgkmcnt(0): the OTHER group is one barrier away from reading the
-    // next tile / overwriting this one.  Same K order and MFMA order per accumulator as the loops below: bit-identical results.
-    // Measured.  In a stand-alone probe of this geometry under SUSTAINED load (tools/exp/gemm_phase_probe.hip, back-to-back launches,
-    // profiles/round5/gemm_phase_probe_r5a.log, ..._r5c_*.log): +6 .. +19 % on every K >= 640 shape, warm and cold operands alike (L1
-    // conv-K 907 -> 1082 TFLOP/s, L2 FF2 1104 -> 1259 = the vendor GEMM's 1259); the group offset is the whole effect (phases without
-    // it: -2 %), priority flips around the MFMA clusters are flat, DMA inside the MFMA clusters is 40 % slower, a finer ring of k-half
-    // units with counted vmcnt is slower than full-tile stages.  IN THIS KERNEL it does not carry over: the library's launches, timed
-    // alone, already run the loops below at 1.14-1.30 PFLOP/s marginal (profiles/round5/stagger_ksweep_r5f.log; the probe's copy of the
-    // same loop, throttled by its own sustained load, ran 0.9-1.1), the staggered loop adds +3-4 % of marginal rate where W is wide
-    // (N = 1280, operands from L2) and LOSES 16 % where one column tile streams A from HBM (N = 320: its DMA has at most one K tile
-    // to land); whole network 157.31 -> 157.15 ms (stagger_ab_whole_network_r5e.log).  So: ON in the persistent GEGLU kernel (FF1
-    // at levels 1-2: +5-6 % in the network, +11 % alone — wide N, A from L2, the next output tile's first K tile requested inside
-    // the phases), here only on request (PNC_OPT_GEMM_STAGGER = 1: the bit-identity tests and the A/B tools).
-    // Where it can run: plain A (the gathers' per-piece address arithmetic sits on the critical path of a phase: the per-tap conv3x3 /
-    // temporal conv launches measured 4-20 % SLOWER staggered, profiles/round5/stagger_kbench_r5c_generic_issue_path.log), K a
-    // multiple of 64, no fp16 lo plane, and not in the row-split workgroups of a sparse last round (one of the two groups idles there).
-    const bool direct_epi = (stagger_min_in & 0x100) != 0;
-    const int stagger_min = stagger_min_in & 0xFF;
-    bool staggered = false;
-    if constexpr (STAGES == 2 && NW == 8 && AMODE == PNC_A_PLAIN)
-        staggered = stagger_min == 1 && kt_tail < 0 && (!A_lo || lo8) && !split_rows && ksplit == 1;
-    if (AMODE == PNC_A_PLAIN && NW == 8 && wave >= 4 && !staggered) __builtin_amdgcn_s_setprio(1);
-    if (staggered) {
-        if constexpr (STAGES == 2 && NW == 8 && AMODE == PNC_A_PLAIN) {
-            constexpr int Q0 = (LOADS + 2) / 3, Q1 = (LOADS - Q0 + 1) / 2;
-            const int grp = wave >> 2;
-            half8v af[MI], bf[NI];
-            i32x8 af8[MI], bf8[NI];
-            auto rd = [&](int stage, int ks) {
-                const char* sa = smem + stage * STAGE;
-                const char* sb = sa + A_BYTES;
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-                    af[i] = *reinterpret_cast<const half8v*>(sa + lds_off128(wm * (MI * 32) + i * 32 + frow, ks * 2 + fk));
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    bf[j] = *reinterpret_cast<const half8v*>(sb + lds_off128(wn * (NI * 32) + j * 32 + frow, ks * 2 + fk));
-            };
-            auto rd8 = [&](int stage, int w) {
-                const char* sa = smem + stage * STAGE;
-                const char* sb = sa + A_BYTES;
-#pragma unroll
-                for (int i = 0; i < MI; ++i) {
-                    const int row = wm * (MI * 32) + i * 32 + frow;
-                    const i32x4 a0 = *reinterpret_cast<const i32x4*>(sa + lds_off128(row, w * 4 + fk * 2));
-                    const i32x4 a1 = *reinterpret_cast<const i32x4*>(sa + lds_off128(row, w * 4 + fk * 2 + 1));
-                    af8[i] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-#pragma unroll
-                for (int j = 0; j < NI; ++j) {
-                    const int row = wn * (NI * 32) + j * 32 + frow;
-                    const i32x4 b0 = *reinterpret_cast<const i32x4*>(sb + lds_off128(row, w * 4 + fk * 2));
-                    const i32x4 b1 = *reinterpret_cast<const i32x4*>(sb + lds_off128(row, w * 4 + fk * 2 + 1));
-                    bf8[j] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
-            };
-            // first barrier of a phase (+ this wave's fragment reads have returned), second barrier
-            auto bar1 = [&]() {
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            auto bar2 = [&]() {
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-            };
-            issue_tile(0, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            const int n8 = lo8 ? nt_lo : 0;
-            if (grp == 1) __builtin_amdgcn_s_barrier();               // group 1 runs one barrier behind group 0 from here on
-            for (int kt = 0; kt < n8; ++kt) {                         // e4m3 lo tiles: one phase per 64-k MFMA window
-                const int st = kt & 1;
-                const int nwin = (p.K - (kt_begin_lo + kt) * BK8) > 64 ? 2 : 1;
-#pragma unroll
-                for (int w = 0; w < 2; ++w) {
-                    if (w < nwin) {
-                        rd8(st, w);
-                        if (w == 0 && kt + 1 < ntot) issue_tile(kt + 1, st ^ 1);
-                        if (w == nwin - 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                        bar1();
-#pragma unroll
-                        for (int j = 0; j < NI; ++j)
-#pragma unroll
-                            for (int i = 0; i < MI; ++i)
-                                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af8[i], bf8[j], acc[i][j], 0, 0, 0, E8M0_LO_INV, 0, p.w_lo_exp);
-                        bar2();
-                    }
-                }
-            }
-            for (int kt = n8; kt < ntot; ++kt) {
-                const int st = kt & 1;
-                const bool nxt = kt + 1 < ntot;
-                static_for<4>([&](auto ph_) {
-                    constexpr int ph = decltype(ph_)::value;
-                    rd(st, ph);
-                    if (nxt) {
-                        // the next tile is a plain fp16 tile inside K: lane offsets fixed over the loop, the K tile as the scalar offset —
-                        // no per-piece test on this path (the general issue_part() with its uniform branches on lo / K tail made the
-                        // phase's load part longer than its MFMA part: measured 5-10 % slower than the un-staggered loop)
-                        const unsigned ks = (unsigned)(kt_begin - nt_lo + kt + 1) * (BK * 2);
-                        char* sa = smem + (st ^ 1) * STAGE + wave * 1024;
-                        char* sb = sa + A_BYTES;
-                        constexpr int QA = ph == 0 ? 0 : (ph == 1 ? Q0 : Q0 + Q1), QB = ph == 0 ? Q0 : (ph == 1 ? Q0 + Q1 : (ph == 2 ? LOADS : 0));
-#pragma unroll
-                        for (int q = QA; q < QB; ++q) {
-                            if (q < A_IT) glds16_buf(rs_a, aoff[q < A_IT ? q : 0], ks, sa + q * (RPI * 128));
-                            else glds16_buf(rs_whi, woff[q >= A_IT ? q - A_IT : 0], ks, sb + (q - A_IT) * (RPI * 128));
-                        }
-                    }
-                    if (ph == 3) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    bar1();
-#pragma unroll
-                    for (int i = 0; i < MI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NI; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-                    bar2();
-                });
-            }
-            if (grp == 0) __builtin_amdgcn_s_barrier();               // group 0 waits for group 1's last phase
-        }
-    } else if (STAGES == 2) {
-        // one tile in flight: the plain barrier carries the vmcnt(0) that lands the DMA
-        issue_tile(0, 0);
-        __syncthreads();
-        // The second-dispatched half of the waves (4-7: one per SIMD, the arbitration losers) issues its share of the
-        // next tile's DMA in the MIDDLE of its MFMA stream instead of together with waves 0-3 right after the barrier
-        // (s_memtime timeline: 1870 vs 690 cycles per tile in the issue segment, with waves 0-3 then idling ~1400
-        // cycles at the barrier): each SIMD then has one wave issuing DMA while the other runs MFMAs.
-        const bool late = NW == 8 && wave >= 4 && wave_on && ntot >= 8;   // 2-5 % at long K
-        // The e4m3 lo tiles run in a loop of their own (same pipeline, same tile counter): one MFMA kind per loop keeps the
-        // register allocator from moving accumulator blocks between the two passes (a shared loop spilled 170 registers).
-        const int n8 = lo8 ? nt_lo : 0;
-        for (int kt = 0; kt < n8; ++kt) {              // (no mid-stream DMA issue here: the lo pass is 3-20 short tiles)
-            if (kt + 1 < ntot) issue_tile(kt + 1, (kt + 1) & 1);
-            if (wave_on) compute8(kt & 1, kt);
-            __syncthreads();
-        }
-        for (int kt = n8; kt < ntot; ++kt) {
-            const bool nxt = kt + 1 < ntot;
-            if (nxt && !late) issue_tile(kt + 1, (kt + 1) & 1);
-            if (wave_on) {
-                compute(kt & 1, (nxt && late) ? kt + 1 : -1);
-                if (!lo8 && kt + 1 == nt_lo) scale_lo();
-            }
-            __syncthreads();
-        }
-    } else {
-        // ring of three stages, TWO tiles in flight.  Counted waits: after issuing tile kt+2 only its LOADS
-        // DMA instructions may stay outstanding, i.e. tile kt+1 has landed; the raw s_barrier (no compiler
-        // vmcnt(0)) then publishes every wave's part of it and retires all reads of the stage being recycled.
-        issue_tile(0, 0);
-        if (ntot > 1) {
-            issue_tile(1, 1);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        int st = 0;
-        const int n8 = lo8 ? nt_lo : 0;
-        for (int kt = 0; kt < n8; ++kt) {                             // e4m3 lo tiles (see the two-stage loop)
-            const bool ahead = (kt + 2) < ntot;
-            if (ahead) issue_tile(kt + 2, st == 0 ? 2 : st - 1);
-            if (wave_on) compute8(st, kt);
-            if (ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            st = (st == 2) ? 0 : st + 1;
-        }
-        for (int kt = n8; kt < ntot; ++kt) {
-            const bool ahead = (kt + 2) < ntot;
-            if (ahead) issue_tile(kt + 2, st == 0 ? 2 : st - 1);      // (kt + 2) % 3
-            if (wave_on) {
-                compute(st);
-                if (!lo8 && kt + 1 == nt_lo) scale_lo();
-            }
-            if (ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOADS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            st = (st == 2) ? 0 : st + 1;
-        }
-    }
-
-    // ------------------------------ epilogue ------------------------------
-    if (!wave_on) return;                       // row group of another workgroup (tail split)
-    const int mw = m0 + wm * (MI * 32), nw = n0 + wn * (NI * 32);
-    if constexpr ((EPI & E_GENERIC) != 0) {
-        epi_generic<MI, NI>(p, acc, lane, mw, nw);
-    } else {
-        if constexpr ((EPI & E_VT) != 0) {
-            if (n0 >= p.n_split) { epi_vt<MI, NI>(p, acc, lane, mw, nw); return; }
-        }
-        if constexpr (EPI == (E_R1 | E_O32) || EPI == E_O32) {
-            // (uniform) full tile, no activation: the direct epilogue (round 6; PNC_OPT_GEMM_FUSE_LN + 2, A/B: the staged one)
-            if (direct_epi && p.act == PNC_ACT_NONE && m0 + BM <= p.M && n0 + BN <= p.N && !split_rows && ksplit == 1) {
-                epi_direct_o32<MI, NI, (EPI & E_R1) != 0>(p, acc, lane, RowLinear{mw}, nw);
-                return;
-            }
-        }
-        float* ep = reinterpret_cast<float*>(smem) + wave * (32 * EPITCH);
-        __syncthreads();                        // every wave is done reading operand tiles from LDS
-        if constexpr (GEGLU) {
-            epi_geglu<MI, NI>(p, acc, ep, lane, mw, nw, reinterpret_cast<const float*>(smem + RING_BYTES));
-        } else {
-            if constexpr ((EPI & E_LN) != 0) {
-                static_assert(WGN == 2, "the fused LayerNorm pairs the two waves of a row");
-                float2* lnb = reinterpret_cast<float2*>(reinterpret_cast<float*>(smem) + NW * (32 * EPITCH));
-                epi_fast<MI, NI, EPI>(p, acc, ep, lane, RowLinear{mw}, nw, p.N, lnb + wave * 64, lnb + (wave ^ 1) * 64);
-            } else {
-                float* gs_tab = reinterpret_cast<float*>(smem) + NW * (32 * EPITCH) + wave * (NI * 16);
-                epi_fast<MI, NI, (EPI & ~E_VT)>(p, acc, ep, lane, RowLinear{mw}, nw, (EPI & E_VT) ? p.n_split : p.N, nullptr, nullptr,
-                                                (EPI & E_GS) ? gs_tab : nullptr);   // E_GELU rides along
-            }
-        }
-    }
+// ... with the weight part: the fp16 lo plane of W as one more argument
+template <int AMODE, int BM, int BN, int WGM, int WGN, int STAGES, bool PIPE, unsigned EPI>
+__global__ __launch_bounds__(64 * WGM * WGN) void gemm_glds_ws_kernel(const PncGemmParams pin, const int ksplit,
+                                                                      const int nfull, const int tail_f,
+                                                                      const float* __restrict__ phi_g, const int group_m,
+                                                                      const int stagger_min_in, const void* __restrict__ wlo16) {
+    constexpr bool WS = true;
+#include "gemm_glds_body.inc"
 }
 
 // Workgroups of one geometry that are resident at once on the 256 CUs (LDS-limited: 160 KB per CU)
@@ -1346,268 +828,40 @@ const float* phi_table_device(hipStream_t st, int* rc);
 // Same tiles, same K order, same epilogue: bit-identical to the one-tile-per-workgroup kernel.  Preconditions (host): plain A, no lo
 // plane, M % BM == 0, N % BN == 0, K % 64 == 0, fp16 output without lo plane.  Measured (profiles/round3/persist_ab_r3w.txt):
 // level-0 FF1 472-540 -> 409-430 us, level 1 356 -> 334, level 2 316 -> 308.
+// gemm_geglu_persist_body.inc is the kernel body, shared as TEXT by the two kernels below (see gemm_glds_kernel).  WS: the weight part
+// of pnc_gemm_wsplit_f16, `wlo16` = the fp16 lo plane of W beside the parameter block.
 template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_geglu_persist_kernel(const PncGemmParams pin, const float* __restrict__ phi_g,
                                                                             const int group_m, const int stagger_min_in) {
-    PncGemmParams p = pin;
-    constexpr int NW = WGM * WGN, MI = BM / WGM / 32, NI = BN / WGN / 32, RPI = NW * 8, A_IT = BM / RPI, B_IT = BN / RPI;
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES, RING_BYTES = 2 * STAGE;
-    static_assert(BM % RPI == 0 && BN % RPI == 0, "tile rows must be a multiple of the DMA row group");
-    static_assert(NI % 2 == 0, "GEGLU pairs value / gate column blocks inside a wave");
-    extern __shared__ __attribute__((aligned(16))) char smem[];         // the operand ring: the ONLY memory LDS-DMA writes
-    // Everything the epilogue reads lives in LDS objects of its own: hipcc puts s_waitcnt vmcnt(0) in front of any LDS access that
-    // may alias an LDS-DMA in flight — with the staging inside the ring (as in gemm_glds_kernel) the epilogue would wait for the
-    // prefetched K tile before its first table read.  160 KB = ring 128 + table 16 + one 2 KB slab of staging per wave 16.
-    __shared__ __attribute__((aligned(16))) float s_phi[PHI_BYTES / 4];
-    __shared__ __attribute__((aligned(16))) half_t s_stage[NW][32 * 32];
-    const half_t* __restrict__ A = reinterpret_cast<const half_t*>(p.A);
-    const half_t* __restrict__ Wt = reinterpret_cast<const half_t*>(p.W);
-    const int tiles_n = p.N / BN, tiles_m = p.M / BM, ntile = tiles_m * tiles_n, nk = p.K / BK;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WGN, wn = wave % WGN;
-    const int srow = wave * 8 + (lane >> 3);
-    const int schunk = (lane & 7) ^ ((srow >> 1) & 7);
-    const int frow = lane & 31, fk = lane >> 5;
+    constexpr bool WS = false;
+    const void* const wlo16 = nullptr;
+#include "gemm_geglu_persist_body.inc"
+}
 
-    // virtual block v -> output tile: the XCD-contiguous ranges and the grouped (tm, tn) order of gemm_glds_kernel
-    auto tile_origin = [&](int v, int& m0, int& n0) {
-        const int tile = xcd_remap(v, ntile);
-        int tn, tm;
-        if (group_m > 0) {
-            const int width = group_m * tiles_n;
-            const int gid = tile / width, first_m = gid * group_m;
-            const int gsz = min(tiles_m - first_m, group_m);
-            const int in = tile - gid * width;
-            tm = first_m + in % gsz; tn = in / gsz;
-        } else {
-            tn = tile % tiles_n; tm = tile / tiles_n;
-        }
-        m0 = tm * BM; n0 = tn * BN;
-    };
-    unsigned aoff[A_IT], woff[B_IT];                       // per-lane byte offsets inside a tile's windows: the same for every tile
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) aoff[i] = (unsigned)((i * RPI + srow) * p.lda + schunk * 8) * 2u;
-#pragma unroll
-    for (int i = 0; i < B_IT; ++i) woff[i] = (unsigned)((i * RPI + srow) * p.ldw + schunk * 8) * 2u;
-    auto issue_part = [&](int m0, int n0, int kt, int stage, auto q0_, auto q1_) __attribute__((always_inline)) {
-        constexpr int Q0 = decltype(q0_)::value, Q1 = decltype(q1_)::value;       // DMA pieces [Q0, Q1): A row groups, then W row groups
-        const buffer_rsrc_t rs_a = make_rsrc(A + (int64_t)m0 * p.lda, 0x7FFFFF00u);
-        const buffer_rsrc_t rs_w = make_rsrc(Wt + (int64_t)n0 * p.ldw, 0x7FFFFF00u);
-        char* sa = smem + stage * STAGE + wave * 1024;
-        char* sb = sa + A_BYTES;
-        const unsigned ks = (unsigned)kt * (BK * 2);
-#pragma unroll
-        for (int i = 0; i < A_IT; ++i)
-            if (i >= Q0 && i < Q1) glds16_buf(rs_a, aoff[i], ks, sa + i * (RPI * 128));
-#pragma unroll
-        for (int i = 0; i < B_IT; ++i)
-            if (A_IT + i >= Q0 && A_IT + i < Q1) glds16_buf(rs_w, woff[i], ks, sb + i * (RPI * 128));
-    };
-    auto issue = [&](int m0, int n0, int kt, int stage) __attribute__((always_inline)) {
-        issue_part(m0, n0, kt, stage, std::integral_constant<int, 0>{}, std::integral_constant<int, A_IT + B_IT>{});
-    };
-
-    for (int i = tid; i < PHI_BYTES / 16; i += 64 * NW)                 // the Phi table: once per workgroup, by plain stores
-        reinterpret_cast<f32x4*>(s_phi)[i] = reinterpret_cast<const f32x4*>(phi_g)[i];
-    f32x16 acc[MI][NI];
-    auto compute = [&](int stage) {
-        const char* sa = smem + stage * STAGE;
-        const char* sb = sa + A_BYTES;
-        half8v af[2][MI], bf[2][NI];
-        auto frags = [&](int ks, int b) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-                af[b][i] = *reinterpret_cast<const half8v*>(sa + lds_off128(wm * (MI * 32) + i * 32 + frow, ks * 2 + fk));
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-                bf[b][j] = *reinterpret_cast<const half8v*>(sb + lds_off128(wn * (NI * 32) + j * 32 + frow, ks * 2 + fk));
-        };
-        frags(0, 0);
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-            if (ks + 1 < BK / 16) frags(ks + 1, (ks + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks & 1][i], bf[ks & 1][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-    const bool direct16 = (stagger_min_in & 256) == 0;     // (+ 256, A/B: the round-3 epilogue through a 2 KB LDS slab per wave)
-    const int stagger_min = stagger_min_in & 255;
-    if (NW == 8 && wave >= 4 && !(stagger_min > 0 && nk >= stagger_min)) __builtin_amdgcn_s_setprio(1);
-    int v = blockIdx.x;
-    if (v >= ntile) return;
-    int m0, n0, sp = 0;
-    tile_origin(v, m0, n0);
-    float pb[NI], pbn[NI];
-    auto load_bias = [&](int n0_, float (&dst)[NI]) {
-#pragma unroll
-        for (int j = 0; j < NI; ++j) dst[j] = p.bias ? p.bias[n0_ + wn * (NI * 32) + j * 32 + (lane & 31)] : 0.0f;
-    };
-    load_bias(n0, pb);
-    issue(m0, n0, 0, 0);
-    // staggered schedule of the K loop (gemm_glds_kernel; PNC_OPT_GEMM_STAGGER): waves 4-7 one barrier behind waves 0-3 inside an
-    // output tile's K loop, both groups aligned again before the epilogue (their epilogues run together, as before; run one behind
-    // the other they would serialise: a group can do ONE phase while the other is in its epilogue).  The next output tile's first K
-    // tile is requested in phases 0-2 of the LAST K tile instead of in front of the epilogue.
-    const bool staggered = NW == 8 && stagger_min > 0 && nk >= (stagger_min == 1 ? 1 : stagger_min);
-    const int grp = wave >> 2;
-    while (true) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-        const int ls = (sp + nk - 1) & 1;       // the stage of the last K tile: every wave is done with it -> the epilogue's staging
-        const int vn = v + gridDim.x;
-        int m1 = 0, n1 = 0;
-        if (staggered) {
-            constexpr int LOADS = A_IT + B_IT, Q0 = (LOADS + 2) / 3, Q1 = (LOADS - Q0 + 1) / 2;
-            const std::integral_constant<int, 0> C0{};
-            const std::integral_constant<int, Q0> CQ0{};
-            const std::integral_constant<int, Q0 + Q1> CQ1{};
-            const std::integral_constant<int, LOADS> CQ2{};
-            if (v == (int)blockIdx.x) {          // (uniform) first output tile: its K tile 0 was requested above (+ the Phi table's stores)
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }                                    // (later tiles: landed and published by the previous tile's last phase)
-            if (grp == 1) __builtin_amdgcn_s_barrier();
-            if (vn < ntile) tile_origin(vn, m1, n1);
-            half8v af[MI], bf[NI];
-            for (int kt = 0; kt < nk; ++kt) {
-                const int st = (sp + kt) & 1;
-                const bool last = kt + 1 == nk;
-                const bool nxt = !last || vn < ntile;
-                const int nm0 = last ? m1 : m0, nn0 = last ? n1 : n0, nkt = last ? 0 : kt + 1;
-#pragma unroll
-                for (int ph = 0; ph < 4; ++ph) {
-                    const char* sa = smem + st * STAGE;
-                    const char* sb = sa + A_BYTES;
-#pragma unroll
-                    for (int i = 0; i < MI; ++i)
-                        af[i] = *reinterpret_cast<const half8v*>(sa + lds_off128(wm * (MI * 32) + i * 32 + frow, ph * 2 + fk));
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        bf[j] = *reinterpret_cast<const half8v*>(sb + lds_off128(wn * (NI * 32) + j * 32 + frow, ph * 2 + fk));
-                    if (nxt) {
-                        if (ph == 0) {
-                            if (last) load_bias(n1, pbn);         // BEFORE the DMA (vmcnt is in order)
-                            issue_part(nm0, nn0, nkt, st ^ 1, C0, CQ0);
-                        } else if (ph == 1) issue_part(nm0, nn0, nkt, st ^ 1, CQ0, CQ1);
-                        else if (ph == 2) issue_part(nm0, nn0, nkt, st ^ 1, CQ1, CQ2);
-                    }
-                    if (ph == 3) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < MI; ++i)
-#pragma unroll
-                        for (int j = 0; j < NI; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                }
-            }
-            if (grp == 0) __builtin_amdgcn_s_barrier();          // both groups past their last phase: the epilogues start together
-        } else {
-        __syncthreads();                        // K tile 0 of this output tile has landed; the previous epilogue's staging is retired
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 1 < nk) issue(m0, n0, kt + 1, (sp + kt + 1) & 1);
-            compute((sp + kt) & 1);
-            __syncthreads();
-        }
-        if (vn < ntile) {                       // (uniform) the next output tile's first K tile, into the other stage
-            tile_origin(vn, m1, n1);
-            load_bias(n1, pbn);                 // BEFORE the DMA: nothing in the epilogue below may wait on vmcnt
-            issue(m1, n1, 0, ls ^ 1);
-        }
-        }
-        {   // epi_geglu's register path, slab by slab (same operations in the same order: bit-identical)
-            half_t* out16 = reinterpret_cast<half_t*>(p.out16);
-            typedef half_t __attribute__((may_alias)) half_st;
-            typedef int4 __attribute__((may_alias)) int4_st;
-            half_st* sb = reinterpret_cast<half_st*>(&s_stage[wave][0]);
-            const int c = lane & 31, cl = lane & 3, rl = lane >> 2;
-            const int mw = m0 + wm * (MI * 32), nw = n0 + wn * (NI * 32);
-            static_for<NI / 2>([&](auto jc_) {
-                constexpr int jc = decltype(jc_)::value * 2;
-                const float bv = pb[jc], bg = pb[jc + 1];
-                const int ncol0 = (nw + jc * 32) >> 1;
-                static_for<MI>([&](auto i_) {
-                    constexpr int i = decltype(i_)::value;
-                    float gx[16], fr[16];
-                    int ix[16];
-                    float2 e[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        gx[r] = acc[i][jc + 1][r] + bg;
-                        float t = fmaf(gx[r], PHI_SCALE, -PHI_X0 * PHI_SCALE);
-                        t = __builtin_amdgcn_fmed3f(t, 0.0f, (float)PHI_N - 0.001f);
-                        ix[r] = (int)t;
-                        fr[r] = t - (float)ix[r];
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) e[r] = *reinterpret_cast<const float2*>(s_phi + 2 * ix[r]);
-                    if (direct16) {
-                        // round 6: the products leave through two-byte buffer stores straight from the registers (a lane holds one column of
-                        // rows 8 q + 4 h + e: two 64-byte row pieces per instruction, the row inside the block as the scalar offset) instead of
-                        // through the slab (16 two-byte staging writes + 2 reads + 2 sixteen-byte stores per
-                        // block): FF1 −0.5 … −1.7 % at every level, step −0.3 ms (profiles/round6/ff1_direct_stores_r6.log).  Same values.
-                        const buffer_rsrc_t ro = make_rsrc(out16 + (int64_t)(mw + i * 32) * p.ldc16, 0x7FFFFF00u);
-                        const int vo = (4 * (lane >> 5) * p.ldc16 + ncol0 + c) * 2;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            float prod = (acc[i][jc][r] + bv) * (gx[r] * fmaf(fr[r], e[r].y, e[r].x));
-                            asm("" : "+v"(prod));
-                            const half_t hp = (half_t)prod;
-                            __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, hp), ro, vo, ((r & 3) + 8 * (r >> 2)) * p.ldc16 * 2, 0);
-                        }
-                    } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float prod = (acc[i][jc][r] + bv) * (gx[r] * fmaf(fr[r], e[r].y, e[r].x));
-                        asm("" : "+v"(prod));
-                        sb[mfma32_row(r, lane) * 32 + c] = (half_t)prod;
-                    }
-#pragma unroll
-                    for (int ps = 0; ps < 2; ++ps) {
-                        const int row = ps * 16 + rl;
-                        const int4 v4 = *reinterpret_cast<const int4_st*>(sb + row * 32 + cl * 8);
-                        *reinterpret_cast<int4_st*>(out16 + (int64_t)(mw + i * 32 + row) * p.ldc16 + ncol0 + cl * 8) = v4;
-                    }
-                    }
-                });
-            });
-        }
-        if (vn >= ntile) break;
-        v = vn; m0 = m1; n0 = n1; sp = ls ^ 1;
-#pragma unroll
-        for (int j = 0; j < NI; ++j) pb[j] = pbn[j];
-    }
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(64 * WGM * WGN) void gemm_geglu_persist_ws_kernel(const PncGemmParams pin, const float* __restrict__ phi_g,
+                                                                               const int group_m, const int stagger_min_in,
+                                                                               const void* __restrict__ wlo16) {
+    constexpr bool WS = true;
+#include "gemm_geglu_persist_body.inc"
 }
 
 // (Round 4 measured the same GEMM as TWO independent persistent 4-wave workgroups per CU — 128 x 256 tiles, 32-channel half tiles,
 // bit-identical — so that one workgroup's GEGLU epilogue runs under the other's MFMAs, the arrangement that gave the view
 // attention 8 %: 6 % SLOWER at level 0 (410 -> 435 us), 14 % at levels 1-2; staging W once per 128 rows instead of once per 256
 // costs more than the overlap returns.  Kernel source and numbers: tools/exp/gemm_geglu_2wg_kernel.h, profiles/round4/ff1_two_workgroups_ab_r4i.txt.)
-template <int BM, int BN, int WGM, int WGN>
-int launch_geglu_persist(const PncGemmParams& p, hipStream_t st) {
+template <int BM, int BN, int WGM, int WGN, bool WS = false>
+int launch_geglu_persist(const PncGemmParams& p, hipStream_t st, const void* wlo16 = nullptr) {
     constexpr int lds = 2 * (BM + BN) * 128;               // dynamic part: the operand ring (table and staging are static)
     static_assert(lds + PHI_BYTES + WGM * WGN * 2048 <= 160 * 1024, "LDS budget of one CU");
     static std::atomic<unsigned char> attr_done[64];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    auto kern = gemm_geglu_persist_kernel<BM, BN, WGM, WGN>;
+    const void* kern;
+    if constexpr (WS) kern = reinterpret_cast<const void*>(gemm_geglu_persist_ws_kernel<BM, BN, WGM, WGN>);
+    else kern = reinterpret_cast<const void*>(gemm_geglu_persist_kernel<BM, BN, WGM, WGN>);
     if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done[dev & 63].store(1, std::memory_order_release);
     }
     int rc = PNC_OK;
@@ -1626,7 +880,12 @@ int launch_geglu_persist(const PncGemmParams& p, hipStream_t st) {
         ncu_of[dev & 63].store(ncu, std::memory_order_relaxed);
     }
     const int blocks = tiles < ncu ? tiles : ncu;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * WGM * WGN), lds, st, p, phi, group_m, pnc_get_option(PNC_OPT_GEMM_STAGGER));
+    if constexpr (WS)
+        hipLaunchKernelGGL((gemm_geglu_persist_ws_kernel<BM, BN, WGM, WGN>), dim3(blocks), dim3(64 * WGM * WGN), lds, st, p, phi, group_m,
+                           pnc_get_option(PNC_OPT_GEMM_STAGGER), wlo16);
+    else
+        hipLaunchKernelGGL((gemm_geglu_persist_kernel<BM, BN, WGM, WGN>), dim3(blocks), dim3(64 * WGM * WGN), lds, st, p, phi, group_m,
+                           pnc_get_option(PNC_OPT_GEMM_STAGGER));
     return pnc_launch_status();
 }
 // the persistent kernel serves this problem (and the switch is on)
@@ -2085,8 +1344,9 @@ int launch_plain_persist(const PncGemmParams& p, hipStream_t st) {
     return pnc_launch_status();
 }
 
-template <int AMODE, int BM, int BN, int WGM, int WGN, int STAGES, bool PIPE, unsigned EPI>
-int launch(const PncGemmParams& p, hipStream_t st, int ksplit = 1) {
+// (wlo16 != NULL: the launch of pnc_gemm_wsplit_f16 — gemm_glds_ws_kernel, same grid; instantiated only where a caller passes one)
+template <int AMODE, int BM, int BN, int WGM, int WGN, int STAGES, bool PIPE, unsigned EPI, bool WS = false>
+int launch(const PncGemmParams& p, hipStream_t st, int ksplit = 1, const void* wlo16 = nullptr) {
     constexpr int lds = STAGES * (BM + BN) * 128;
     constexpr int threads = 64 * WGM * WGN;
     constexpr bool GEGLU = (EPI & E_GEGLU) != 0;
@@ -2095,9 +1355,11 @@ int launch(const PncGemmParams& p, hipStream_t st, int ksplit = 1) {
     static std::atomic<unsigned char> attr_done[64];      // per instantiation and device; the call is idempotent
     int dev = 0;
     (void)hipGetDevice(&dev);
-    auto kern = gemm_glds_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>;
+    const void* kern;
+    if constexpr (WS) kern = reinterpret_cast<const void*>(gemm_glds_ws_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>);
+    else kern = reinterpret_cast<const void*>(gemm_glds_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>);
     if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+        (void)hipFuncSetAttribute(kern,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds + (GEGLU ? PHI_BYTES : 0));
         attr_done[dev & 63].store(1, std::memory_order_release);
     }
@@ -2123,8 +1385,13 @@ int launch(const PncGemmParams& p, hipStream_t st, int ksplit = 1) {
     int group_m = gopt > 0 ? gopt : (tiles_n > 8 ? 4 : 0);           // 1 = plain order
     if (group_m > tiles_m) group_m = tiles_m;
     if (tiles_n < 2) group_m = 0;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds + (GEGLU ? PHI_BYTES : 0), st, q, ksplit, nfull, tail_f, phi,
-                       group_m, (pnc_get_option(PNC_OPT_GEMM_STAGGER) & 0xFF) | ((pnc_get_option(PNC_OPT_GEMM_FUSE_LN) & 2) ? 0 : 0x100));
+    const int stagger = (pnc_get_option(PNC_OPT_GEMM_STAGGER) & 0xFF) | ((pnc_get_option(PNC_OPT_GEMM_FUSE_LN) & 2) ? 0 : 0x100);
+    if constexpr (WS)
+        hipLaunchKernelGGL((gemm_glds_ws_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>), dim3(blocks), dim3(threads),
+                           lds + (GEGLU ? PHI_BYTES : 0), st, q, ksplit, nfull, tail_f, phi, group_m, stagger, wlo16);
+    else
+        hipLaunchKernelGGL((gemm_glds_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>), dim3(blocks), dim3(threads),
+                           lds + (GEGLU ? PHI_BYTES : 0), st, q, ksplit, nfull, tail_f, phi, group_m, stagger);
     if (ksplit > 1) return launch_splitk_reduce(p, ksplit, st);
     return pnc_launch_status();
 }
@@ -2197,21 +1464,21 @@ static inline bool ln_whole_rows(const PncGemmParams& p, TileChoice tc) {
 }
 
 // launch the variant EPI of AMODE on the chosen tile
-template <int AMODE, unsigned EPI>
-int launch_tile(const PncGemmParams& p, hipStream_t st, TileChoice tc) {
+template <int AMODE, unsigned EPI, bool WS = false>
+int launch_tile(const PncGemmParams& p, hipStream_t st, TileChoice tc, const void* wlo16 = nullptr) {
     constexpr bool GEGLU = (EPI & E_GEGLU) != 0;
     switch (tc.tile) {
         case T_128x32:
-            if constexpr (!GEGLU && !(EPI & E_VT)) return launch<AMODE, 128, 32, 4, 1, 2, true, EPI>(p, st);
+            if constexpr (!GEGLU && !(EPI & E_VT)) return launch<AMODE, 128, 32, 4, 1, 2, true, EPI, WS>(p, st, 1, wlo16);
             return PNC_EINVAL;
         case T_256x320:
-            if constexpr (!GEGLU) return launch<AMODE, 256, 320, 4, 2, 2, false, EPI>(p, st);
+            if constexpr (!GEGLU) return launch<AMODE, 256, 320, 4, 2, 2, false, EPI, WS>(p, st, 1, wlo16);
             return PNC_EINVAL;
         case T_256x256:
-            if (tc.ksplit > 1) return launch<AMODE, 256, 256, 4, 2, 2, true, E_O32>(p, st, tc.ksplit);   // raw partials
-            return launch<AMODE, 256, 256, 4, 2, 2, true, EPI>(p, st);
-        case T_256x128: return launch<AMODE, 256, 128, 4, 2, 3, true, EPI>(p, st);
-        default: return launch<AMODE, 128, 128, 2, 2, 2, true, EPI>(p, st);
+            if (tc.ksplit > 1) return launch<AMODE, 256, 256, 4, 2, 2, true, E_O32, WS>(p, st, tc.ksplit, wlo16);   // raw partials
+            return launch<AMODE, 256, 256, 4, 2, 2, true, EPI, WS>(p, st, 1, wlo16);
+        case T_256x128: return launch<AMODE, 256, 128, 4, 2, 3, true, EPI, WS>(p, st, 1, wlo16);
+        default: return launch<AMODE, 128, 128, 2, 2, 2, true, EPI, WS>(p, st, 1, wlo16);
     }
 }
 

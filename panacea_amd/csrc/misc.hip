@@ -654,6 +654,9 @@ void pnc_tu_collect_gemm_plain(unsigned int*, hipStream_t);
 void pnc_tu_collect_gemm_conv3x3(unsigned int*, hipStream_t);
 void pnc_tu_collect_gemm_conv1d(unsigned int*, hipStream_t);
 void pnc_tu_collect_gemm_stencil_tile(unsigned int*, hipStream_t);
+void pnc_tu_collect_gemm_plain_ws(unsigned int*, hipStream_t);
+void pnc_tu_collect_gemm_conv3x3_ws(unsigned int*, hipStream_t);
+void pnc_tu_collect_gemm_conv1d_ws(unsigned int*, hipStream_t);
 void pnc_tu_collect_norm(unsigned int*, hipStream_t);
 
 extern "C" int pnc_range_monitor_collect(unsigned int* out, void* stream) {
@@ -664,6 +667,9 @@ extern "C" int pnc_range_monitor_collect(unsigned int* out, void* stream) {
     pnc_tu_collect_gemm_conv3x3(out, st);
     pnc_tu_collect_gemm_conv1d(out, st);
     pnc_tu_collect_gemm_stencil_tile(out, st);
+    pnc_tu_collect_gemm_plain_ws(out, st);
+    pnc_tu_collect_gemm_conv3x3_ws(out, st);
+    pnc_tu_collect_gemm_conv1d_ws(out, st);
     pnc_tu_collect_norm(out, st);
     pnc_tu_collect_misc(out, st);
     return pnc_launch_status();

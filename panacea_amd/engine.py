@@ -96,6 +96,7 @@ class Precision:
     # seeing exactly those, and `weights` splits no activation.  So `precise-full` is a SplitWeights and never equal to a Precision:
     # where both should answer alike, ask is_wide().
     weights = False
+    beside = False         # WeightsBeside only: the twin travels next to the launch (gemm(..., w_lo16=)) instead of in PncGemmParams.W_lo
 
     def __post_init__(self):
         att = (self.qkv, self.q_text, self.kv_text, self.attn_o, self.ctx)
@@ -112,7 +113,8 @@ class Precision:
     @property
     def name(self) -> str:
         on = [k for k, v in self.__dict__.items() if v and k not in ("lo8", "weights")]
-        return "fp16" if not on else "split(" + ",".join(on) + (")+e4m3-lo" if self.lo8 else ")") + ("+weights" if self.weights else "")
+        return ("fp16" if not on else "split(" + ",".join(on) + (")+e4m3-lo" if self.lo8 else ")") + ("+weights" if self.weights else "")
+                + ("-beside" if self.beside else ""))
 
     def lo_dtype(self, cls: str) -> torch.dtype:
         """dtype of the lo plane of operand class `cls` (= its PNC_LO_* format, panacea_amd.hip.lo_fmt)"""
@@ -123,6 +125,26 @@ class Precision:
 class SplitWeights(Precision):
     """A policy whose weights are split as well (`weights`, see Precision): every operand class split, fp16 lo planes"""
     weights: bool = True
+
+
+@dataclass(frozen=True)
+class WeightsBeside(Precision):
+    """`precise-ckpt`: the operand classes and lo-plane formats of `precise` (e4m3 lo planes, `lo8`) + split weights, for fp32
+    checkpoints whose activations stay inside `precise`'s range.  The fp16 lo twin of the weights travels BESIDE the launch
+    (pnc_gemm_wsplit_f16, `gemm(..., w_lo16=)`), which adds the A_hi * W_lo products ahead of everything `precise` runs: one more fp16
+    pass per GEMM, no split attention kernels (attention multiplies activations by activations).  `weights` is True, so the small-M
+    linears and the stacked projectors hand over their twins as under `precise-full`; `beside` tells engine.gemm which way the plane
+    goes.  The class set is exactly `precise`'s: those are the consumers the entry point serves (every other set would also want
+    measurements of its own); single-device like `precise-full`."""
+    weights = True
+    beside = True
+
+    def __post_init__(self):
+        want = {f.name: getattr(PRECISE, f.name) for f in dataclasses.fields(Precision)}
+        have = {f.name: getattr(self, f.name) for f in dataclasses.fields(Precision)}
+        if have != want:
+            raise ValueError("weights beside the launch (`precise-ckpt`) go with exactly the operand classes and e4m3 lo planes of "
+                             f"`precise`: {sorted(k for k, v in want.items() if v)}; got {sorted(k for k, v in have.items() if v)}")
 
 
 OPERAND_CLASSES = ("stream", "gn_stt", "ff_out", "stem", "gn_head", "gn_res", "gnt", "conv_mid",
@@ -151,8 +173,11 @@ PRECISE_WIDE = Precision(stream=True, gn_stt=True, ff_out=True, stem=True, gn_he
 # `precise-wide` plus split weights: the policy for fp32 checkpoints, whose weights are not fp16-representable.  Three fp16 passes
 # per GEMM instead of two, and an fp16 lo twin of every packed weight (about +4.5 GB at full size).
 PRECISE_FULL = SplitWeights(**dataclasses.asdict(PRECISE_WIDE))
+# `precise` plus split weights beside the launch: fp32 checkpoints with an ordinary activation range (|v| < 512)
+PRECISE_CKPT = WeightsBeside(**dataclasses.asdict(PRECISE))
 PRECISIONS = {"fast": FAST, "precise": PRECISE, "precise-all": PRECISE_ALL, "precise-lite": PRECISE_LITE,
-              "precise-f16lo": PRECISE_F16LO, "precise-wide": PRECISE_WIDE, "precise-full": PRECISE_FULL}
+              "precise-f16lo": PRECISE_F16LO, "precise-wide": PRECISE_WIDE, "precise-full": PRECISE_FULL,
+              "precise-ckpt": PRECISE_CKPT}
 
 
 def is_wide(p) -> bool:
@@ -160,6 +185,16 @@ def is_wide(p) -> bool:
     built like them, whatever its class or `weights` flag.  Single-device policies (no frame / view shards)."""
     p = precision(p)
     return not p.lo8 and all(getattr(p, c) for c in OPERAND_CLASSES)
+
+
+def weights_beside(p) -> bool:
+    """the policy hands the weights' lo twins over beside the launch (`precise-ckpt`).  Single-device, like the wide policies."""
+    return bool(getattr(precision(p), "beside", False))
+
+
+def single_device_only(p) -> bool:
+    """the policies that frame / view shards and ShardedCFG refuse"""
+    return is_wide(p) or weights_beside(p)
 
 
 def precision(p) -> Precision:
@@ -1040,6 +1075,8 @@ def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_l
       a.lo is e4m3   the e4m3 copy of W for the lo pass (pk_lo8), packed on first use and kept in `pk` next to the fp16 weights;
       a.lo is fp16   the fp16 lo twin of W when the policy splits the weights (Packable.packed_lo, built on first use), else nothing;
       no a.lo        nothing.
+    Under a policy that hands the twin over BESIDE the launch (`precise-ckpt`, weights_beside) the fp16 lo twin goes along as `w_lo16`
+    for every state of a.lo, next to whatever the list above says.
     `key=None`: `pk` is W itself, a stacked matrix that is no Packable's (TextKVProjector, EmbProjector), and `w_lo` its lo twin — used
     under the same conditions as a module's."""
     w = pk
@@ -1050,6 +1087,11 @@ def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_l
             w, b = w
             if kw.get("bias") is None:
                 kw["bias"] = b
+    if rt.prec.beside:
+        kw["w_lo16"] = _lo_twin(pk, key) if key is not None else w_lo
+        if kw["w_lo16"] is None:
+            raise ValueError("a stacked weight matrix needs its lo twin (w_lo=) under a policy that splits the weights")
+        w_lo = None
     if a.lo is None:
         w_lo = None
     elif a.lo.dtype == torch.uint8:
@@ -1057,7 +1099,7 @@ def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_l
         if k8 not in pk:
             pk[k8] = pk_lo8(w)
         w_lo = pk[k8]
-    elif not rt.prec.weights:
+    elif not rt.prec.weights or rt.prec.beside:
         w_lo = None
     elif key is not None:
         w_lo = _lo_twin(pk, key)

@@ -116,6 +116,7 @@ _SIGNATURES = {
     "pnc_build_digest": (C.c_char_p, []),
     "pnc_set_option": (_I, [_I, _I]),
     "pnc_gemm_f16": (_I, [C.POINTER(GemmParams), _P]),
+    "pnc_gemm_wsplit_f16": (_I, [C.POINTER(GemmParams), _P, _P]),
     "pnc_gemm_workspace_floats": (_L, [C.POINTER(GemmParams)]),
     "pnc_gemm_fuses_layernorm": (_I, [C.POINTER(GemmParams)]),
     "pnc_attn_views_f16": (_I, [C.POINTER(AttnParams), _P]),
@@ -329,7 +330,7 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
          out16t: Optional[torch.Tensor] = None, ldt: int = 0, t_rows: int = 0, t_gstride: int = 0,
          n_split: int = 0, act: int = ACT_NONE, geglu: bool = False,
          a16_lo: Optional[torch.Tensor] = None, out16_lo: Optional[torch.Tensor] = None, w_ld: int = 0,
-         w_lo: Optional[tuple] = None,
+         w_lo: Optional[tuple] = None, w_lo16: Optional[torch.Tensor] = None,
          ln_gamma: Optional[torch.Tensor] = None, ln_beta: Optional[torch.Tensor] = None,
          ln_out16: Optional[torch.Tensor] = None, ldln: int = 0, ln_eps: float = 1e-5, ln_in_library: bool = False,
          gn_part: Optional[torch.Tensor] = None):
@@ -337,7 +338,12 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
     (PncGemmParams.gn_part).  `a16_lo` / `out16_lo`: lo planes of precise (split) operands, see PncGemmParams.A_lo in the header; their dtype names the
     format (fp16, or uint8 = e4m3 bytes).  `w_lo` = (W_lo e4m3 bytes [N, K], w_lo_exp E8M0 byte of the tensor) — engine.pk_lo8 —
     is the weight side of an e4m3 lo pass; `w_lo` = an fp16 tensor in w16's layout is the lo plane of split weights (engine.wlo under
-    the `precise-full` policy, PncGemmParams.W_lo): it goes with an fp16 `a16_lo`."""
+    the `precise-full` policy, PncGemmParams.W_lo): it goes with an fp16 `a16_lo`.  `w_lo16`: the same fp16 lo plane handed over BESIDE
+    the struct (pnc_gemm_wsplit_f16, the `precise-ckpt` policy): it goes with every `a16_lo` — none, e4m3 (`w_lo` then stays the e4m3
+    pair) or fp16 (the library forwards that launch to the three-part one; `w_lo` must be None)."""
+    if w_lo16 is not None and (w_lo16.dtype != torch.float16 or w_lo16.shape != w16.shape):
+        raise PncError(f"w_lo16: the fp16 lo plane of the weights in w16's layout {tuple(w16.shape)}, got {w_lo16.dtype} "
+                       f"{tuple(w_lo16.shape)}")
     p, lib, _ws = _gemm_params(a16, w16, M=M, N=N, K=K, lda=lda, a_mode=a_mode, conv=conv, tconv=tconv, bias=bias, rowbias=rowbias,
                                rb_rows=rb_rows, rb_mod=rb_mod, res1=res1, ldr1=ldr1, res2=res2, ldr2=ldr2, out32=out32, ldc32=ldc32,
                                out16=out16, ldc16=ldc16, out16t=out16t, ldt=ldt, t_rows=t_rows, t_gstride=t_gstride, n_split=n_split,
@@ -349,7 +355,11 @@ def gemm(a16: torch.Tensor, w16: torch.Tensor, *, M: int, N: int, K: int, lda: i
         # rows span several workgroups: the library would launch its LayerNorm kernel after the GEMM.  Issue the two launches
         # from here instead (the same two kernels) so that the per-family timing of bench.py sees them separately.
         p.ln_gamma = p.ln_beta = p.ln_out16 = None
-    _check(_timed(fam, 2.0 * M * N * K, 0.0, lib.pnc_gemm_f16, C.byref(p), _stream()), "pnc_gemm_f16")
+    if w_lo16 is not None:
+        _check(_timed(fam, 2.0 * M * N * K, 0.0, lib.pnc_gemm_wsplit_f16, C.byref(p), _ptr(w_lo16, torch.float16, "w_lo16"), _stream()),
+               "pnc_gemm_wsplit_f16")
+    else:
+        _check(_timed(fam, 2.0 * M * N * K, 0.0, lib.pnc_gemm_f16, C.byref(p), _stream()), "pnc_gemm_f16")
     if trailing_ln:
         layernorm(out32, ldc32, M, N, ln_gamma, ln_beta, ln_eps, ln_out16, ldln)
 

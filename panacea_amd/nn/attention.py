@@ -491,16 +491,16 @@ class TextKVProjector:
         rows, D = rt.B * E.TEXT_PAD, rt.ctx16.hi.shape[1]
         if Dm != D:
             raise ValueError(f"context width {D} does not match the cross-attention context_dim {Dm}")
+        w_lo = None
+        if rt.prec.weights:                           # the lo twin of the stacked weights: same rows, same zero padding (n_split)
+            if getattr(self, "_pk_lo", None) is None or getattr(self, "_sig_lo", None) != sig:
+                with torch.no_grad():
+                    self._pk_lo, self._sig_lo = self.pack(lo=True)[0], sig
+            w_lo = self._pk_lo
         if rt.prec.kv_text:
             # split policy: every output column row-major with its lo plane (the split attention kernels read V row-major)
             ld = NKp + NT
             kv = rt.operand((rows, ld), "kv_text")
-            w_lo = None
-            if rt.prec.weights:                       # the lo twin of the stacked weights: same rows, same zero padding (n_split)
-                if getattr(self, "_pk_lo", None) is None or getattr(self, "_sig_lo", None) != sig:
-                    with torch.no_grad():
-                        self._pk_lo, self._sig_lo = self.pack(lo=True)[0], sig
-                w_lo = self._pk_lo
             E.gemm(rt, rt.ctx16, w, None, kv, w_lo=w_lo, M=rows, N=ld, K=D, lda=D, ldc16=ld)
             kv = kv.map(lambda t: t.view(-1))
             for a, o in zip(self.sites, offs):
@@ -508,7 +508,7 @@ class TextKVProjector:
             return
         k = rt.empty((rows, NKp), torch.float16)
         vt = rt.empty((rt.B, NT, E.TEXT_PAD), torch.float16)
-        E.gemm(rt, rt.ctx16, w, None, E.Operand(k), M=rows, N=NKp + NT, K=D, lda=D, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,
+        E.gemm(rt, rt.ctx16, w, None, E.Operand(k), w_lo=w_lo, M=rows, N=NKp + NT, K=D, lda=D, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,
                t_rows=E.TEXT_PAD, t_gstride=NT * E.TEXT_PAD, n_split=NKp)
         kf, vf = k.view(-1), vt.view(-1)
         for a, o in zip(self.sites, offs):

@@ -232,9 +232,9 @@ def _refuse_wide(model):
     """sharded evaluations run neither the 'precise-wide' operand policy nor the escalate protocol (UNetModel3D._check_unsharded_policy)"""
     from . import engine as E
     prec = getattr(model, "precision", None)
-    if getattr(model, "on_range_exceeded", None) == "escalate" or (prec is not None and E.is_wide(prec)):
-        raise ValueError("the 'precise-wide' operand policy and on_range_exceeded='escalate' do not run sharded (frame / view shards, "
-                         "ShardedCFG)")
+    if getattr(model, "on_range_exceeded", None) == "escalate" or (prec is not None and E.single_device_only(prec)):
+        raise ValueError("the 'precise-wide' operand policy (and 'precise-full', 'precise-ckpt') and on_range_exceeded='escalate' do not "
+                         "run sharded (frame / view shards, ShardedCFG)")
 
 
 def _refuse_denoiser(den):

@@ -26,6 +26,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 import emu  # noqa: E402
+import emu_ckpt  # noqa: E402
 import emu_weights  # noqa: E402
 import emu_wide  # noqa: E402
 from helpers import cond, manifest, product_network, step_inputs  # noqa: E402
@@ -33,7 +34,7 @@ from panacea_amd import engine as E, hip, parallel, synth  # noqa: E402
 from panacea_amd.nn.attention import SpatialTemporalTransformer  # noqa: E402
 from panacea_amd.nn.openaimodel import ResBlock3D  # noqa: E402
 
-OVERLAY = dict(attn_views_split=emu_wide.attn_views_split, attn_temporal_split=emu_wide.attn_temporal_split, gemm=emu_weights.gemm,
+OVERLAY = dict(attn_views_split=emu_wide.attn_views_split, attn_temporal_split=emu_wide.attn_temporal_split, gemm=emu_ckpt.gemm,
                linear_smallm=emu_weights.linear_smallm, linear_smallm_segments=emu_weights.linear_smallm_segments)
 
 
@@ -79,7 +80,7 @@ def network(w32: bool):
 def cases():
     for p in E.PRECISIONS:
         def whole(p=p):
-            w, inp = network(p in ("precise-wide", "precise-full"))
+            w, inp = network(p in ("precise-wide", "precise-full", "precise-ckpt"))
             w.diffusion_model.precision = p
             return w(inp["x"], inp["t"], cond(inp))
         yield p, whole

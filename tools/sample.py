@@ -49,8 +49,9 @@ def main():
     ap.add_argument("--discretization", choices=sorted(DISCRETIZATIONS), default="ddpm", help="the sampler's sigma schedule")
     ap.add_argument("--frames", type=int, default=8, choices=range(1, 17), metavar="1..16", help="frames per clip (num_frames)")
     ap.add_argument("--precision", choices=sorted(engine.PRECISIONS), default=None,
-                    help="operand policy of the denoiser (default: the network's own, `precise`); `precise-full` splits the weights too — "
-                         "the policy for fp32 checkpoints")
+                    help="operand policy of the denoiser (default: the network's own, `precise`); `precise-ckpt` splits the weights too — "
+                         "the policy for fp32 checkpoints with an ordinary activation range (|v| < 512); `precise-full` splits every "
+                         "operand and the weights (|v| < 65504, at 3-4x the time)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
