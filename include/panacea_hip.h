@@ -546,6 +546,27 @@ int pnc_cast_f16(const float* x, int64_t n, void* y16, void* y16_lo, int lo_fmt,
  * stayed inside the range its contract is written for. */
 int pnc_range_monitor_collect(unsigned int* out, void* stream);
 
+/* Range profile of ONE contraction operand (a diagnostic pass: UNetModel3D.profile_ranges; the denoising path never launches it).
+ * Where the monitor above answers "did a lo plane clamp, anywhere", this states where an operand sits in fp16's range.
+ *   hi  : fp16 plane, `rows` rows of `cols` elements, `ld` elements between rows
+ *   lo  : NULL, or the lo plane of the operand in lo_fmt (PNC_LO_*), same ld IN ELEMENTS
+ * Elements at column positions cols .. ld - 1 of a row are padding and are never read.
+ * rec : PNC_STATS_WORDS 64-bit words on the device.  The kernel ADDS to them (atomic add; atomic max for word 32), so one record sums
+ *       any number of launches on any streams without a host synchronisation; the caller zeroes it.
+ *   rec[0..31]  elements per fp16 binade: index = exponent field (bits >> 10) & 31 of hi.  Bin 0: zeros and subnormals; bin 31: Inf
+ *               and NaN; |v| >= 512 — where an e4m3 lo plane clamps — is bins 24..31
+ *   rec[32]     maximum of (bits & 0x7FFF) over the elements: NaN > Inf > every finite value, so a NaN cannot hide
+ *   rec[33]     lo elements at the END of their format: e4m3 (byte & 0x7F) >= 0x7E (+-448 and the NaN code), fp16 non-finite; an
+ *               upper bound of the elements that clamped (a residual of exactly 448 counts, too).  lo = NULL adds nothing
+ *   rec[34]     NaN elements of hi
+ *   rec[35]     elements counted (rows * cols)
+ * Checked before any launch: NULL hi / rec, rows < 1, cols < 1, ld < cols, lo != NULL with an unknown lo_fmt, a plane of more than
+ * 2^43 elements (a wave of the kernel counts in 32 bits before it widens) -> PNC_EINVAL;
+ * cols % 8, ld % 8, hi not 16-byte aligned, lo not aligned to 8 elements of its format, rec not 8-byte aligned -> PNC_EALIGN. */
+#define PNC_STATS_WORDS 36
+int pnc_operand_stats_f16(const void* hi, const void* lo, int lo_fmt, int64_t rows, int cols, int64_t ld,
+                          unsigned long long* rec, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * 5. First-stage decoder: row softmax of a materialised score
  *    matrix, p[m][:] = softmax(scale * s[m][:]) (fp32 in, fp32 statistics, fp16

@@ -766,6 +766,7 @@ class Runtime:
         self.emb_proj: Dict[int, torch.Tensor] = {}    # per ResBlock3D: emb_layers(emb), [F, C] fp32 (nn.openaimodel.EmbProjector)
         self.text_frozen = False                       # text_kv / guided come from StepInvariants (sampler hoisting)
         self.guided: Optional["Act"] = None            # precomputed ControlNet hint-stem output
+        self.profile: Optional["RangeProfile"] = None  # UNetModel3D.profile_ranges(): `gemm` observes every A operand; None = off
 
     def empty(self, shape, dtype, tail_rows: int = 0) -> torch.Tensor:
         """tail_rows: a [rows, C] operand allocated with that many spare rows behind it; the returned [rows, C] view remembers
@@ -789,7 +790,10 @@ class Runtime:
 
     def operand(self, shape, cls: Optional[str] = None, tail_rows: int = 0) -> Operand:
         """an uninitialised fp16 operand of class `cls` (None: never split), with its lo plane when the policy splits that class"""
-        return Operand(self.empty(shape, torch.float16, tail_rows), self.lo_plane(shape, cls, tail_rows=tail_rows) if cls else None)
+        op = Operand(self.empty(shape, torch.float16, tail_rows), self.lo_plane(shape, cls, tail_rows=tail_rows) if cls else None)
+        if self.profile is not None:
+            self.profile.note(op.hi, cls)
+        return op
 
     def set_context(self, context: torch.Tensor):
         """context: (B, n_text, D) — tiled over T inside the reference (controlmodel.py:121-122,183-184);
@@ -811,6 +815,149 @@ class Runtime:
         c = torch.zeros((B, TEXT_PAD, D), device=self.device, dtype=torch.float16)
         c[:, :n] = context.to(device=self.device, dtype=torch.float16)
         self.ctx16 = Operand(c.view(B * TEXT_PAD, D))
+        if self.profile is not None:
+            self.profile.note(c, "ctx")
+
+
+# ----------------------------------------------------------------------------------------------
+# range profile (UNetModel3D.profile_ranges): where every GEMM operand of an evaluation sits in fp16's range
+# ----------------------------------------------------------------------------------------------
+def _f16_from_bits(bits: int) -> float:
+    import struct
+    return struct.unpack("<e", struct.pack("<H", int(bits) & 0xFFFF))[0]
+
+
+class RangeProfile:
+    """Range statistics of the A operands of every `gemm` of the evaluations it observes, per operand class and per site.
+
+    Owns a device table [slots, 36] of int64 records (pnc_operand_stats_f16, include/panacea_hip.h: binade histogram, maximum,
+    lo-plane saturation and NaN counts), zeroed here, and the host map slot -> (operand class, site).  The statistics kernel ADDS to
+    a record, so a site that runs in every evaluation, on whichever stream, sums into one slot and nothing synchronises until
+    `report()`.  A site is the name of the module that owns the weights within the profiled network (its ControlNet under
+    `controlnet.`) plus the weight key; the class is the one the operand was allocated under (Runtime.operand), "unsplit" for
+    operands no policy splits.  Remembered per allocation, by storage base pointer, so views and slices resolve; every
+    Runtime.operand() overwrites what an earlier allocation at that address left and every evaluation starts from an empty map, so
+    a plane that an evaluation did not allocate itself (hoisted StepInvariants) is "unsplit".
+
+    The range monitor (UNetModel3D.lo_clamped) counts the e4m3 QUADS that clamped, process-wide; `lo_saturated` here counts the lo
+    ELEMENTS that sit at their format's last code — an upper bound of the clamped elements, per site."""
+    WORDS = _hip.STATS_WORDS
+
+    def __init__(self, device, slots: int = 4096):
+        self.table = torch.zeros((slots, self.WORDS), dtype=torch.int64, device=device)
+        self.sites: List[tuple] = []                  # slot -> (operand class, site)
+        self.evaluations = 0
+        self.limit: Optional[int] = None              # observe at most that many evaluations (UNetModel3D.profile_ranges)
+        self._slot: Dict[tuple, int] = {}
+        self._cls: Dict[int, str] = {}                # storage base pointer -> operand class
+        self._names: Dict[int, str] = {}              # id(module) -> name within the profiled network
+
+    def bind(self, network: torch.nn.Module):
+        """resolve the site names once: named_modules() of the network (its ControlNet is the child `controlnet`)"""
+        for name, m in network.named_modules():
+            self._names.setdefault(id(m), name)
+
+    def note(self, t: torch.Tensor, cls: Optional[str]):
+        """the allocation behind `t` holds an operand of class `cls` (None: an unclassed buffer — forget what lived there before)"""
+        ptr = t.untyped_storage().data_ptr()
+        if cls is None:
+            self._cls.pop(ptr, None)
+        else:
+            self._cls[ptr] = cls
+
+    def begin_evaluation(self):
+        """a new evaluation allocates its operands afresh: drop the classes of the previous one's allocations, whose addresses the
+        allocator hands out again (to buffers that never pass through Runtime.operand, too)"""
+        self._cls.clear()
+        self.evaluations += 1
+
+    def class_of(self, t: torch.Tensor) -> str:
+        return self._cls.get(t.untyped_storage().data_ptr(), "unsplit")
+
+    def _site(self, pk, key, site) -> str:
+        if key is None:
+            owner, name = site if site is not None else (None, "stacked")
+        else:
+            owner, name = getattr(pk, "owner", None), ".".join(str(k) for k in (key if isinstance(key, tuple) else (key,)))
+        mod = "" if owner is None else self._names.get(id(owner), type(owner).__name__)
+        return f"{mod}.{name}" if mod else name
+
+    def observe(self, rt: Runtime, a: Operand, pk, key, site, kw: dict):
+        """one statistics launch over the planes of `a`, on the current stream, ahead of the GEMM that reads them (`kw`: its keywords)"""
+        if rt.shard is not None or rt.vshard is not None:
+            raise ValueError("the range profile does not run frame- or view-sharded")
+        mode = kw.get("a_mode", _hip.A_PLAIN)
+        if mode == _hip.A_PLAIN:
+            rows, cols = kw["M"], kw["K"]
+            ld = kw.get("lda") or cols
+        elif mode == _hip.A_CONV3X3:
+            # the gather reads every pixel nine times: the profile covers the activation plane once
+            c = kw["conv"]
+            cols = ld = c["Cin"]
+            rows = kw["M"] // (c["Hout"] * c["Wout"]) * c["Hin"] * c["Win"]
+        else:
+            cols = ld = kw["tconv"]["C"]
+            rows = kw["M"]
+        k = (self.class_of(a.hi), self._site(pk, key, site))
+        slot = self._slot.get(k)
+        if slot is None:
+            if len(self.sites) >= self.table.shape[0]:
+                raise ValueError(f"the range profile holds {self.table.shape[0]} sites; make it with more slots")
+            slot = self._slot[k] = len(self.sites)
+            self.sites.append(k)
+        rt.be.operand_stats(a.hi, a.lo, rows, cols, ld, self.table[slot])
+
+    @staticmethod
+    def _stats(words, max_bits: int) -> dict:
+        b = [int(v) for v in words[:32]]
+        return {"elements": int(words[35]), "max_abs": _f16_from_bits(max_bits), "binades": b, "ge_512": sum(b[24:]),
+                "lo_saturated": int(words[33]), "nan": int(words[34]), "inf": b[31] - int(words[34])}
+
+    def report(self) -> dict:
+        """-> {"evaluations", "classes": {class: S}, "sites": [{"site", "class", **S}, ...]} with S = {"elements", "max_abs",
+        "binades" (32 counts), "ge_512", "lo_saturated", "nan", "inf"}; sites sorted by max_abs, largest first (NaN > Inf > finite).
+        One device-to-host copy."""
+        n = len(self.sites)
+        host = self.table[:n].cpu().tolist() if n else []
+        order = sorted(range(n), key=lambda i: (-host[i][32], self.sites[i][1], self.sites[i][0]))
+        sites = [{"site": self.sites[i][1], "class": self.sites[i][0], **self._stats(host[i], host[i][32])} for i in order]
+        sums: Dict[str, list] = {}
+        for (cls, _), w in zip(self.sites, host):
+            s = sums.setdefault(cls, [0] * self.WORDS)
+            for j in range(self.WORDS):
+                s[j] = max(s[j], w[j]) if j == 32 else s[j] + w[j]
+        return {"evaluations": self.evaluations, "classes": {c: self._stats(w, w[32]) for c, w in sorted(sums.items())}, "sites": sites}
+
+    def recommend(self, network: torch.nn.Module) -> dict:
+        """-> {"policy", "reason", "headroom_binades"}: the cheapest operand policy whose stated range (README, operand policies) holds
+        what was observed.  None when an operand is non-finite or at fp16's end: no fp16 policy holds that.  `precise` /
+        `precise-ckpt` while no class that `precise` splits reaches |v| = 512 (bins 24..31), `precise-wide` / `precise-full` beyond;
+        the second of each pair when the network's weights are not all fp16-representable: checked is `w.half().float() == w` on every
+        parameter of `network` with two or more dimensions (the Linear and conv weights every GEMM and small-M linear packs; biases and
+        norm parameters stay fp32 on the device and are not looked at), one device synchronisation in all.  `headroom_binades` = 24 - the
+        highest occupied binade over those classes: <= 0 is out of range, 1 means the operands already touch [256, 512)."""
+        rep = self.report()
+        split = [c for c in OPERAND_CLASSES if getattr(PRECISE, c) and c in rep["classes"]]
+        top = max((b for c in split for b, cnt in enumerate(rep["classes"][c]["binades"]) if cnt), default=0)
+        headroom = 24 - top
+        s = rep["sites"][0] if rep["sites"] else None          # (sorted: the worst site first)
+        if s is not None and (s["nan"] or s["inf"] or not s["max_abs"] < 65504.0):
+            what = "NaN" if s["nan"] else ("Inf" if s["inf"] else "the largest finite fp16 value")
+            return {"policy": None, "headroom_binades": headroom,
+                    "reason": f"operand class '{s['class']}' at site '{s['site']}' holds {what} (max |v| = {s['max_abs']}): "
+                              "no fp16 operand policy can carry it"}
+        with torch.no_grad():
+            off = [(p.detach().half().float() != p.detach().float()).any() for p in network.parameters() if p.dim() >= 2]
+            rounded = not (off and bool(torch.stack(off).any()))
+        wtxt = "the GEMM weights are fp16-representable" if rounded else "the GEMM weights are not fp16-representable (an fp32 checkpoint)"
+        over = [c for c in split if rep["classes"][c]["ge_512"] > 0]
+        if not over:
+            return {"policy": "precise" if rounded else "precise-ckpt", "headroom_binades": headroom,
+                    "reason": f"every operand class that `precise` splits stays below |v| = 512 ({headroom} binades of headroom); {wtxt}"}
+        worst = next(s for s in rep["sites"] if s["class"] in over and s["ge_512"] > 0)
+        return {"policy": "precise-wide" if rounded else "precise-full", "headroom_binades": headroom,
+                "reason": f"operand class(es) {', '.join(over)} reach |v| >= 512, where an e4m3 lo plane clamps (widest: site "
+                          f"'{worst['site']}', max |v| = {worst['max_abs']}); {wtxt}"}
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1068,7 +1215,7 @@ def layer_norm(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta) -> O
     return y
 
 
-def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_lo=None, **kw):
+def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_lo=None, site=None, **kw):
     """THE launch of a GEMM on an operand: a @ W^T with the epilogue `kw` (the keywords of the backend's `gemm`), fp16 output into
     `out`.  W = pk[key]; `key` may be a path into `pk` (a tuple), and an entry that is a (weight, bias) pair gives both.  What goes
     with the planes of `a` and `out` is decided here and nowhere else:
@@ -1078,7 +1225,8 @@ def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_l
     Under a policy that hands the twin over BESIDE the launch (`precise-ckpt`, weights_beside) the fp16 lo twin goes along as `w_lo16`
     for every state of a.lo, next to whatever the list above says.
     `key=None`: `pk` is W itself, a stacked matrix that is no Packable's (TextKVProjector, EmbProjector), and `w_lo` its lo twin — used
-    under the same conditions as a module's."""
+    under the same conditions as a module's.  `site` = (owning network, fixed name) names such a matrix in a range profile.
+    With a range profile on (rt.profile, UNetModel3D.profile_ranges) the planes of `a` are observed ahead of the launch, on its stream."""
     w = pk
     if key is not None:
         for k in key if isinstance(key, tuple) else (key,):
@@ -1107,6 +1255,8 @@ def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_l
         kw["out16"] = out.hi
         if out.lo is not None:
             kw["out16_lo"] = out.lo
+    if rt.profile is not None:
+        rt.profile.observe(rt, a, pk, key, site, kw)
     rt.be.gemm(a.hi, w, a16_lo=a.lo, w_lo=w_lo, **kw)
 
 

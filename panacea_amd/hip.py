@@ -148,6 +148,7 @@ _SIGNATURES = {
     "pnc_add_f32": (_I, [_P, _P, _L, _P, _P, _P, _I, _P]),
     "pnc_cast_f16": (_I, [_P, _L, _P, _P, _I, _P]),
     "pnc_range_monitor_collect": (_I, [_P, _P]),
+    "pnc_operand_stats_f16": (_I, [_P, _P, _I, _L, _I, _L, _P, _P]),
 }
 
 _lib = None
@@ -654,6 +655,21 @@ def range_monitor_collect(out_i32: torch.Tensor):
     """adds the number of e4m3 lo-plane quads that CLAMPED since the previous call to out_i32[0] (a device int32 word) and resets the
     library's counters (include/panacea_hip.h: pnc_range_monitor_collect)"""
     _check(load().pnc_range_monitor_collect(_ptr(out_i32, torch.int32, "out"), _stream()), "pnc_range_monitor_collect")
+
+
+STATS_WORDS = 36         # PNC_STATS_WORDS: 64-bit words of one record of pnc_operand_stats_f16
+
+
+def operand_stats(hi, lo, rows, cols, ld, rec):
+    """pnc_operand_stats_f16: ADDS the range statistics of the operand plane `hi` (fp16; `rows` rows of `cols` elements, `ld` elements
+    between rows) and of its lo plane `lo` (None, fp16 or uint8 = e4m3 bytes, same ld in elements) to the record `rec`, an int64
+    device tensor of at least STATS_WORDS contiguous words (binade histogram, maximum, saturation counts: include/panacea_hip.h)"""
+    if rec.dtype != torch.int64 or rec.numel() < STATS_WORDS or not rec.is_contiguous():
+        raise PncError(f"operand_stats: the record is {STATS_WORDS} contiguous int64 words, got {rec.dtype} x {rec.numel()}")
+    fmt = lo_fmt(lo)
+    nb = rows * cols * (2.0 + _lo_bytes(lo))
+    _check(_timed("operand_stats", 0.0, nb, load().pnc_operand_stats_f16, _ptr(hi, torch.float16, "hi"), _ptr(lo, LO_DTYPE[fmt], "lo"),
+                  fmt, rows, cols, ld, _ptr(rec, torch.int64, "rec"), _stream()), "pnc_operand_stats_f16")
 
 
 def cast_f16(x32, n, y16, y16_lo=None):

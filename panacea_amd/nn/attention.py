@@ -450,6 +450,7 @@ class TextKVProjector:
 
     def __init__(self, root: nn.Module):
         self.sites = [m.attn2 for m in root.modules() if isinstance(m, BasicTransformerBlock)]
+        self.net = getattr(root, "net", root)          # the network these sites belong to (names the GEMM in a range profile)
         self._pk = None
         if not E.TEXTKV_ONE_GEMM:                      # A/B (PNC_TEXTKV_ONE_GEMM=0): one projector per width, as rounds 2-4 grouped
             by_c = {}
@@ -457,7 +458,7 @@ class TextKVProjector:
                 by_c.setdefault(a.inner_dim, []).append(a)
             self.parts = [TextKVProjector.__new__(TextKVProjector) for _ in by_c]
             for p, sites in zip(self.parts, by_c.values()):
-                p.sites, p._pk, p.parts = sites, None, None
+                p.sites, p._pk, p.parts, p.net = sites, None, None, self.net
         else:
             self.parts = None
 
@@ -501,14 +502,14 @@ class TextKVProjector:
             # split policy: every output column row-major with its lo plane (the split attention kernels read V row-major)
             ld = NKp + NT
             kv = rt.operand((rows, ld), "kv_text")
-            E.gemm(rt, rt.ctx16, w, None, kv, w_lo=w_lo, M=rows, N=ld, K=D, lda=D, ldc16=ld)
+            E.gemm(rt, rt.ctx16, w, None, kv, w_lo=w_lo, site=(self.net, "text_kv"), M=rows, N=ld, K=D, lda=D, ldc16=ld)
             kv = kv.map(lambda t: t.view(-1))
             for a, o in zip(self.sites, offs):
                 rt.text_kv[id(a)] = E.TextKV(kv.map(lambda t: t[o:]), ld, kv.map(lambda t: t[NKp + o:]), ld)
             return
         k = rt.empty((rows, NKp), torch.float16)
         vt = rt.empty((rt.B, NT, E.TEXT_PAD), torch.float16)
-        E.gemm(rt, rt.ctx16, w, None, E.Operand(k), w_lo=w_lo, M=rows, N=NKp + NT, K=D, lda=D, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,
+        E.gemm(rt, rt.ctx16, w, None, E.Operand(k), w_lo=w_lo, site=(self.net, "text_kv"), M=rows, N=NKp + NT, K=D, lda=D, ldc16=NKp, out16t=vt, ldt=E.TEXT_PAD,
                t_rows=E.TEXT_PAD, t_gstride=NT * E.TEXT_PAD, n_split=NKp)
         kf, vf = k.view(-1), vt.view(-1)
         for a, o in zip(self.sites, offs):

@@ -140,7 +140,7 @@ class ControlNet3D(UNetModel3D):
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"
         with torch.no_grad():
-            rt = runtime_for(x, self.num_frames, self.frame_shard, self.view_shard)
+            rt = self._observed(runtime_for(x, self.num_frames, self.frame_shard, self.view_shard))
             rt.prec = E.precision(self.precision)
             rt.set_context(context)
             emb = self._time_embedding(rt, timesteps)
@@ -165,7 +165,7 @@ class ControlledUNetModel3D(UNetModel3D):
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"
         with torch.no_grad():
-            rt = runtime_for(x, self.num_frames, self.frame_shard, self.view_shard)
+            rt = self._observed(runtime_for(x, self.num_frames, self.frame_shard, self.view_shard))
             rt.prec = E.precision(self.precision)
             rt.set_context(context)
             emb = self._time_embedding(rt, timesteps)
@@ -190,7 +190,7 @@ class ControlledUNetModel3D(UNetModel3D):
             if hint.shape[0] not in (B * t_local, t_local):
                 raise ValueError(f"hint holds {hint.shape[0]} frames; expected {B * t_local} (every frame of the {B}-sample batch) "
                                  f"or {t_local} (one layout shared by the samples)")
-            rt = Runtime(hint.device, B, self.num_frames, sh, self.view_shard)
+            rt = self._observed(Runtime(hint.device, B, self.num_frames, sh, self.view_shard), evaluation=False)
             rt.prec = E.precision(self.precision)
             rt.set_context(context)
             self._project_text(rt)
@@ -249,7 +249,7 @@ class ControlledUNetModel3D(UNetModel3D):
 
     def _denoise_once(self, x, timesteps, context, hint, trace, side_idx, inv, fused, collect):
         with torch.no_grad():
-            rt = runtime_for(x if fused is None else fused[1], self.num_frames, self.frame_shard, self.view_shard)
+            rt = self._observed(runtime_for(x if fused is None else fused[1], self.num_frames, self.frame_shard, self.view_shard))
             rt.prec = E.precision(self.precision)
             rt.trace = trace
             if inv is not None:

@@ -14,6 +14,7 @@ the gfx950 kernels on channels-last tokens:
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
@@ -628,6 +629,51 @@ class UNetModel3D(nn.Module, Packable):
         return once(True)
 
 
+    # ---- range profile (engine.RangeProfile): opt-in statistics of every GEMM operand, per operand class and per site.  Off (the
+    # default) the runtimes carry no profile and engine.gemm launches, allocates and synchronises nothing for it.
+    @contextlib.contextmanager
+    def profile_ranges(self, slots: int = 4096, evaluations: Optional[int] = None):
+        """Context manager -> engine.RangeProfile.  Inside it every evaluation of this network and of its ControlNet — direct calls,
+        `denoise`, a sampler's steps, both side streams — adds the range statistics of the A operand of each GEMM to the profile
+        (one pnc_operand_stats_f16 launch per operand, on the stream of its GEMM); `report()` / `recommend(network)` read them.
+        `evaluations`: observe only the first that many (a sampler run then pays for the statistics in its first steps only).
+        Single-device and eager, like `escalate`: refused on a frame- or view-sharded network and while a stream is capturing."""
+        cn = self._modules.get("controlnet")
+        for net in (self, cn):
+            if net is not None and (net.frame_shard is not None or net.view_shard is not None):
+                raise ValueError("the range profile does not run frame- or view-sharded")
+        device = next(self.parameters()).device
+        if _capturing(device):
+            raise ValueError("the range profile launches a statistics kernel per operand and reads its table on the host: it cannot "
+                             "be started while a stream is capturing")
+        if self.__dict__.get("_profile") is not None:
+            raise ValueError("this network is being profiled already")
+        prof = E.RangeProfile(device, slots)
+        prof.limit = evaluations
+        prof.bind(self)
+        for net in (self, cn):
+            if net is not None:
+                net.__dict__["_profile"] = prof
+        try:
+            yield prof
+        finally:
+            for net in (self, cn):
+                if net is not None:
+                    net.__dict__.pop("_profile", None)
+
+    def _observed(self, rt: Runtime, evaluation: bool = True) -> Runtime:
+        """hand the active range profile (if any) to the runtime of an evaluation"""
+        prof = self.__dict__.get("_profile")
+        if prof is not None and (prof.limit is None or prof.evaluations < prof.limit):
+            if _capturing(rt.device):
+                raise ValueError("the range profile does not run while a stream is capturing")
+            if rt.shard is not None or rt.vshard is not None:
+                raise ValueError("the range profile does not run frame- or view-sharded")
+            rt.profile = prof
+            if evaluation:
+                prof.begin_evaluation()
+        return rt
+
     def _range_state(self) -> dict:
         st = self.__dict__.get("_range_st")
         if st is None:
@@ -830,7 +876,7 @@ class UNetModel3D(nn.Module, Packable):
         from .util import runtime_for
 
         def once(collect):
-            rt = runtime_for(x, self.num_frames, self.frame_shard, self.view_shard)
+            rt = self._observed(runtime_for(x, self.num_frames, self.frame_shard, self.view_shard))
             rt.prec = E.precision(self.precision)
             rt.set_context(context)
             emb = self._time_embedding(rt, timesteps)

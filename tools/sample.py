@@ -37,6 +37,29 @@ def denoiser_config(prediction: str) -> dict:
                        "discretization_config": {"target": P + "discretizer.LegacyDDPMDiscretization"}}}
 
 
+def print_range_profile(prof, network, path=""):
+    """the class table, the ten widest sites and the recommendation of an engine.RangeProfile; `path`: the report as JSON"""
+    rep, rec = prof.report(), prof.recommend(network)
+
+    def row(name, S):
+        top = max((b for b, n in enumerate(S["binades"]) if n), default=0)
+        return (f"{name[:58]:58s} {S['elements']:>13d} {S['max_abs']:>10.4g} {top:>4d} {S['ge_512']:>11d} {S['lo_saturated']:>11d} "
+                f"{S['nan']:>6d} {S['inf']:>6d}")
+    head = f"{'':58s} {'elements':>13s} {'max |v|':>10s} {'bin':>4s} {'>= 512':>11s} {'lo at end':>11s} {'NaN':>6s} {'Inf':>6s}"
+    print(f"operand ranges over {rep['evaluations']} evaluation(s), policy {network.precision} (bin: highest occupied fp16 binade; 24 = [512, 1024))")
+    print(head)
+    for c, S in rep["classes"].items():
+        print(row(c, S))
+    print("the ten widest sites")
+    for s in rep["sites"][:10]:
+        print(row(f"{s['class']}: {s['site']}", s))
+    print(f"recommended operand policy: {rec['policy']} (headroom {rec['headroom_binades']} binades) - {rec['reason']}")
+    if path:
+        Path(path).parent.mkdir(parents=True, exist_ok=True)
+        Path(path).write_text(json.dumps({"recommendation": rec, **rep}, indent=1))
+        print("wrote", path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=25)
@@ -52,6 +75,10 @@ def main():
                     help="operand policy of the denoiser (default: the network's own, `precise`); `precise-ckpt` splits the weights too — "
                          "the policy for fp32 checkpoints with an ordinary activation range (|v| < 512); `precise-full` splits every "
                          "operand and the weights (|v| < 65504, at 3-4x the time)")
+    ap.add_argument("--range-profile", nargs="?", const="", default=None, metavar="FILE",
+                    help="profile the operand ranges of the first two evaluations of the run under the chosen policy "
+                         "(UNetModel3D.profile_ranges): prints the class table, the ten widest sites and the recommended operand "
+                         "policy; FILE: also write the report as JSON")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
@@ -80,11 +107,16 @@ def main():
                                            "discretization_config": {"target": P + "discretizer." + DISCRETIZATIONS[a.discretization]},
                                            "guider_config": {"target": P + "guiders.VanillaCFG", "params": {"scale": a.cfg_scale}}}},
                                device=dev)
-    frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
-                                    denoiser=denoiser_config(a.prediction))
+    import contextlib
+    profiling = net.diffusion_model.profile_ranges(evaluations=2) if a.range_profile is not None else contextlib.nullcontext()
+    with profiling as prof:
+        frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
+                                        denoiser=denoiser_config(a.prediction))
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print(f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.steps} steps + decode of {T} frames {tuple(frames.shape)}: {dt:.2f} s "
           f"(range {frames.min().item():.2f} .. {frames.max().item():.2f}, finite={bool(torch.isfinite(frames).all())})")
+    if prof is not None:
+        print_range_profile(prof, net.diffusion_model, a.range_profile)
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
     checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=frames.shape[-1] // 6)
     checkpoint.save_gif(frames[:, :, ::4, ::4], str(out / "panorama_quarter.gif"))
