@@ -16,14 +16,18 @@ rank = ((sample * cfg + half) * G + frame_group) * V + view_group  (`RankLayout`
   frame: attention.py:545-559, util.py:276-283) need nothing from another rank.  The cross-frame couplings — the two
   temporal GroupNorm + conv1d sites of every ResBlock3D (openaimodel.py:505-515, 533-539) and the temporal transformer
   branch of every STT (attention.py:1106-1134) — are pointwise per pixel across frames and run in the transposed
-  sharding (all T frames of N/G pixels per rank): `engine.FrameShard.to_pixels / to_frames`, one all-to-all each.
+  sharding (all T frames of N/G pixels per rank): `FrameShard.to_pixels / to_frames`, one all-to-all each.
   Bytes per rank and step, and the overlap plan, are in DESIGN.md §9.
 * **view groups** (V = 2 | 3 | 6) — the alternative split of one half: rank v of a view group holds views
-  [v*6/V, (v+1)*6/V) of every frame, a band of W/V columns of every map (`engine.ViewShard`).  The temporal sites are then
+  [v*6/V, (v+1)*6/V) of every frame, a band of W/V columns of every map (`ViewShard`).  The temporal sites are then
   local; what crosses ranks are the one-column halos of the 3x3 convs, the spatial GroupNorm statistics (96 floats per
   frame) and the keys / values of the two neighbouring views in the cross-view attention — neighbour-to-neighbour
   messages, each pair on its own xGMI link.  More, smaller messages than the frame exchange (DESIGN.md section 9 has the
   counts); it is the layout for V ranks when T / G frames per rank would drop below the temporal kernels' tile.
+
+This module decides WHICH ranks form a group and what each rank holds (`RankLayout`, `Groups`, the guider, the latent's cuts and
+gathers).  What a rank of a frame or view group exchanges, and how, is `panacea_amd/shard.py` (`FrameShard`, `ViewShard`; also
+reachable as `engine.FrameShard` / `engine.ViewShard`).
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from .engine import FrameShard, ViewShard
+from .shard import FrameShard, ViewShard
 from .sampling import VanillaCFG
 
 

@@ -14,6 +14,13 @@ import torch.multiprocessing as mp
 
 ROOT = Path(__file__).resolve().parent.parent
 
+# (exchanges, bytes_sent) of every rank's shard, read after the eps evaluation and again after the schedule.  The figures are those of
+# the tree before the shards moved to panacea_amd/shard.py, measured with these workers: the accounting must not drift.
+FRAME_COUNTERS = {(2, 1, 2, 4, "halo"): [[(72, 13572260), (412, 81402020)]] * 2}
+VIEW_COUNTERS = {(3, 1, 3, 2): [[(189, 6627200), (493, 19685248)], [(189, 6860672), (493, 20852608)], [(189, 6627200), (493, 19685248)]]}
+# (frame exchanges, frame bytes_sent, view exchanges, view bytes_sent): cfg 2 x frames 2 x views 2, every rank alike
+GRID_COUNTERS = [[(68, 3391488, 78, 1530880), (340, 16957440, 390, 7654400)]] * 8
+
 
 def _worker(rank, world, port, out_dir):
     sys.path.insert(0, str(ROOT))
@@ -144,6 +151,7 @@ def _frames_worker(rank, world, port, out_dir, cfg, G, T, resblock="halo"):
     with E.use_backend(emu), torch.no_grad():
         eps_loc = net(loc["x"], loc["t"], cond_of(loc))
         assert shard.exchanges > 0 and shard.bytes_sent > 0
+        counters = [(shard.exchanges, shard.bytes_sent)]
         torch.save({"eps": eps_loc, "halves": halves, "fg": lo.frame_group}, Path(out_dir) / f"eps{rank}.pt")
         # --- (3) three sampler steps with the layout's guider; the latent stays sharded, gathered once at the end
         cond = {"crossattn": inp["crossattn"][1:2], "concat": inp["concat"][T:], "cond_feat": inp["cond_feat"][T:]}
@@ -164,6 +172,8 @@ def _frames_worker(rank, world, port, out_dir, cfg, G, T, resblock="halo"):
         plain = smp.sampler_step(s_in * sig[0], s_in * sig[1], denoiser, xin, c_l, u_l)
         fused = smp._fused_step(s_in * sig[0], s_in * sig[1], S.BoundDenoiser(den, net), xin, c_l, u_l)
         assert torch.equal(plain, fused), (plain - fused).abs().max().item()
+        counters.append((shard.exchanges, shard.bytes_sent))
+        torch.save(counters, Path(out_dir) / f"counters{rank}.pt")
         if rank == 0:
             parallel.apply_frame_shard(net, None)
             eps_ref = net(inp["x"], inp["t"], cond_of(inp))
@@ -193,6 +203,10 @@ def test_frame_group_sharding_reproduces_the_single_process_eps(world, cfg, G, T
             e = torch.load(Path(d) / f"eps{r}.pt")
             want = eps_ref[e["halves"]][:, e["fg"] * tl:(e["fg"] + 1) * tl].reshape(e["eps"].shape)
             worst = max(worst, (e["eps"] - want).abs().max().item())
+        counters = [torch.load(Path(d) / f"counters{r}.pt") for r in range(world)]
+        print(f"world {world} cfg {cfg} G {G} {resblock}: (exchanges, bytes_sent) per rank after eps, after the schedule: {counters}")
+        if (world, cfg, G, T, resblock) in FRAME_COUNTERS:
+            assert counters == FRAME_COUNTERS[world, cfg, G, T, resblock]
         print(f"world {world} cfg {cfg} G {G}: max |eps_sharded - eps_single| = {worst:.3e}")
         assert worst <= 1e-3
         err = (ref["traj"] - ref["traj_ref"]).abs().max().item()
@@ -341,6 +355,7 @@ def _views_worker(rank, world, port, out_dir, cfg, V, T, network):
         assert torch.equal(eps_loc, eps_two), (eps_loc - eps_two).abs().max().item()
         assert vs.exchanges - n0 <= n_two - 20, (vs.exchanges - n0, n_two)         # the tiny network: 23 GroupNorm + conv sites
         assert vs.exchanges > n0 and vs.bytes_sent > 0
+        counters = [(vs.exchanges, vs.bytes_sent)]
         torch.save({"eps": eps_loc, "halves": halves, "vg": vg, "exchanges": vs.exchanges - n0}, Path(out_dir) / f"eps{rank}.pt")
         # --- (3) two sampler steps with the layout's guider; the latent stays a band, gathered once at the end
         cond = {"crossattn": inp["crossattn"][1:2], "concat": inp["concat"][T:], "cond_feat": inp["cond_feat"][T:]}
@@ -359,6 +374,8 @@ def _views_worker(rank, world, port, out_dir, cfg, V, T, network):
         xs_h = smp(denoiser, parallel.local_views(x0, lo), ch, uh)
         assert torch.equal(xs_h, xs), (xs_h - xs).abs().max().item()
         assert vs.exchanges - n1 < 2 * (n1 - n0)        # fewer exchanges per step: the hint stem's halos are not repeated
+        counters.append((vs.exchanges, vs.bytes_sent))
+        torch.save(counters, Path(out_dir) / f"counters{rank}.pt")
         if rank == 0:
             parallel.apply_view_shard(net, None)
             eps_ref = net(inp["x"], inp["t"], cond_of(inp))
@@ -401,6 +418,10 @@ def test_view_group_sharding_reproduces_the_single_process_eps(world, cfg, V, T)
             worst, mean = max(worst, diff.max().item()), max(mean, diff.mean().item())
             edge = diff[..., [0, -1]].mean().item()                  # the columns next to a neighbour band
             assert edge <= 2.0 * diff.mean().item(), (edge, diff.mean().item())
+        counters = [torch.load(Path(d) / f"counters{r}.pt") for r in range(world)]
+        print(f"world {world} cfg {cfg} V {V}: (exchanges, bytes_sent) per rank after eps, after the schedule: {counters}")
+        if (world, cfg, V, T) in VIEW_COUNTERS:
+            assert counters == VIEW_COUNTERS[world, cfg, V, T]
         print(f"world {world} cfg {cfg} V {V}: |eps_sharded - eps_single| max {worst:.3e} mean {mean:.3e}, "
               f"{e['exchanges']} exchanges per evaluation")
         assert worst <= 2e-3 and mean <= 2.5e-4
@@ -450,6 +471,7 @@ def _grid_worker(rank, world, port, out_dir, cfg, G, V, T):
     with E.use_backend(emu), torch.no_grad():
         eps_loc = net(loc["x"], loc["t"], cond_of(loc))
         assert shard.exchanges > 0 and vs.exchanges > 0
+        counters = [(shard.exchanges, shard.bytes_sent, vs.exchanges, vs.bytes_sent)]
         torch.save({"eps": eps_loc, "halves": halves, "fg": lo.frame_group, "vg": lo.view_group,
                     "frame_exchanges": shard.exchanges, "view_exchanges": vs.exchanges}, Path(out_dir) / f"eps{rank}.pt")
         cond = {"crossattn": inp["crossattn"][1:2], "concat": inp["concat"][T:], "cond_feat": inp["cond_feat"][T:]}
@@ -471,6 +493,8 @@ def _grid_worker(rank, world, port, out_dir, cfg, G, V, T):
         plain = smp.sampler_step(s_in * sig[0], s_in * sig[1], denoiser, xin, c_l, u_l)
         fused = smp._fused_step(s_in * sig[0], s_in * sig[1], S.BoundDenoiser(den, net), xin, c_l, u_l)
         assert torch.equal(plain, fused), (plain - fused).abs().max().item()
+        counters.append((shard.exchanges, shard.bytes_sent, vs.exchanges, vs.bytes_sent))
+        torch.save(counters, Path(out_dir) / f"counters{rank}.pt")
         if rank == 0:
             parallel.apply_frame_shard(net, None)
             parallel.apply_view_shard(net, None)
@@ -501,6 +525,9 @@ def test_cfg_x_views_x_frames_grid_world8_reproduces_the_single_process_eps():
             want = eps_ref[e["halves"]][:, e["fg"] * tl:(e["fg"] + 1) * tl, ..., e["vg"] * wl:(e["vg"] + 1) * wl].reshape(e["eps"].shape)
             diff = (e["eps"] - want).abs()
             worst, mean = max(worst, diff.max().item()), max(mean, diff.mean().item())
+        counters = [torch.load(Path(d) / f"counters{r}.pt") for r in range(world)]
+        print(f"world 8: (frame exchanges, frame bytes_sent, view exchanges, view bytes_sent) per rank after eps, after the schedule: {counters}")
+        assert counters == GRID_COUNTERS
         print(f"world 8 = cfg 2 x frames 2 x views 2: |eps_sharded - eps_single| max {worst:.3e} mean {mean:.3e}; "
               f"{e['frame_exchanges']} frame + {e['view_exchanges']} view exchanges per evaluation")
         assert worst <= 2e-3 and mean <= 2.5e-4
