@@ -356,8 +356,16 @@ __device__ __forceinline__ void epi_fast(const PncGemmParams& p, f32x16 (&acc)[M
                     for (int e = 0; e < 8; ++e) v[e] = silu_f(v[e]);
                 }
                 if constexpr (GELU) {
+                    // the product is kept opaque (as epi_geglu keeps its own): hipcc otherwise fuses multiply + conversion into
+                    // v_fma_mixlo_f16 (ONE rounding of the exact product) for the lo plane's residual, next to a store that converts
+                    // the rounded fp32 product (two roundings).  Where the fp32 product is a tie of the fp16 grid the two disagree by
+                    // an fp16 ulp, and out16 + 2^-11 out16_lo missed v by that whole ulp (tests/test_gemm_edges_gpu.py)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = gelu_erf_f(v[e]);
+                    for (int e = 0; e < 8; ++e) {
+                        float g = gelu_erf_f(v[e]);
+                        asm("" : "+v"(g));
+                        v[e] = g;
+                    }
                 }
             }
             if constexpr (R2) {
