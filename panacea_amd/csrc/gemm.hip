@@ -1,19 +1,17 @@
 // gemm.hip — C-ABI entry of the MFMA GEMM family: argument validation, epilogue-variant selection, split-K reduce
 // kernel, GEGLU Phi table.  The kernels themselves are instantiated per A-gather mode in gemm_plain.hip /
-// gemm_conv3x3.hip / gemm_conv1d.hip from the template in gemm_kernel.h.
+// gemm_conv3x3.hip / gemm_conv1d.hip (and their _ws twins) from the template in gemm_kernel.h, by the dispatch of gemm_dispatch.h.
 #include "gemm_kernel.h"
 #include <math.h>
 #include <mutex>
 
 namespace pnc_gemm {
 
-int dispatch_plain(const PncGemmParams& p, unsigned epi, hipStream_t st, bool* ln_fused);
-int dispatch_conv3x3(const PncGemmParams& p, unsigned epi, hipStream_t st);
-int dispatch_conv1d(const PncGemmParams& p, unsigned epi, hipStream_t st);
-// the same with the weight part (gemm_*_ws.hip): wlo16 = the fp16 lo plane of W beside the parameter block
-int dispatch_plain_ws(const PncGemmParams& p, unsigned epi, hipStream_t st, bool* ln_fused, const void* wlo16);
-int dispatch_conv3x3_ws(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16);
-int dispatch_conv1d_ws(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16);
+// gemm_dispatch.h, instantiated in gemm_<mode>.hip (WS = false) and gemm_<mode>_ws.hip (WS = true: with the weight part, wlo16 = the fp16 lo
+// plane of W beside the parameter block; NULL without)
+template <bool WS> int dispatch_plain(const PncGemmParams& p, unsigned epi, hipStream_t st, bool* ln_fused, const void* wlo16);
+template <bool WS> int dispatch_conv3x3(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16);
+template <bool WS> int dispatch_conv1d(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16);
 
 __device__ __attribute__((aligned(16))) float g_phi_table[2 * PHI_N];
 
@@ -255,24 +253,33 @@ extern "C" int pnc_gemm_fuses_layernorm(const PncGemmParams* pp) {
     return ln_whole_rows(p, tc) ? 1 : 0;
 }
 
-extern "C" int pnc_gemm_f16(const PncGemmParams* pp, void* stream) {
-    if (!pp) return PNC_EINVAL;
-    const int rc = validate(*pp);
-    if (rc != PNC_OK) return rc;
-    PncGemmParams p = *pp;
+template <bool WS>
+static int dispatch(const PncGemmParams& p, unsigned epi, hipStream_t st, bool* ln_fused, const void* wlo16) {
+    switch (p.a_mode) {
+        case PNC_A_PLAIN: return dispatch_plain<WS>(p, epi, st, ln_fused, wlo16);
+        case PNC_A_CONV3X3: return dispatch_conv3x3<WS>(p, epi, st, wlo16);
+        default: return dispatch_conv1d<WS>(p, epi, st, wlo16);
+    }
+}
+
+// a validated launch; wlo16 != NULL: with the weight part (pnc_gemm_wsplit_f16)
+static int run_gemm(const PncGemmParams& pin, const void* wlo16, void* stream) {
+    PncGemmParams p = pin;
     normalise(p);
     const unsigned epi = epilogue_with_ln(p);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     bool ln_fused = false;
-    int rc2;
-    switch (p.a_mode) {
-        case PNC_A_PLAIN: rc2 = dispatch_plain(p, epi, st, &ln_fused); break;
-        case PNC_A_CONV3X3: rc2 = dispatch_conv3x3(p, epi, st); break;
-        default: rc2 = dispatch_conv1d(p, epi, st); break;
-    }
-    if (rc2 == PNC_OK && p.ln_out16 && !ln_fused)      // rows span several workgroups (or a generic launch): the LayerNorm kernel
-        rc2 = pnc_layernorm(p.out32, p.ldc32, p.M, p.N, p.ln_gamma, p.ln_beta, p.ln_eps, p.ln_out16, p.ldln, nullptr, stream);
-    return rc2;
+    int rc = wlo16 ? dispatch<true>(p, epi, st, &ln_fused, wlo16) : dispatch<false>(p, epi, st, &ln_fused, nullptr);
+    if (rc == PNC_OK && p.ln_out16 && !ln_fused)      // rows span several workgroups (or a generic launch): the LayerNorm kernel
+        rc = pnc_layernorm(p.out32, p.ldc32, p.M, p.N, p.ln_gamma, p.ln_beta, p.ln_eps, p.ln_out16, p.ldln, nullptr, stream);
+    return rc;
+}
+
+extern "C" int pnc_gemm_f16(const PncGemmParams* pp, void* stream) {
+    if (!pp) return PNC_EINVAL;
+    const int rc = validate(*pp);
+    if (rc != PNC_OK) return rc;
+    return run_gemm(*pp, nullptr, stream);
 }
 
 // pnc_gemm_f16 with the fp16 lo plane of the weights BESIDE the parameter block (include/panacea_hip.h)
@@ -288,20 +295,7 @@ extern "C" int pnc_gemm_wsplit_f16(const PncGemmParams* pp, const void* W_lo16, 
         q.W_lo = W_lo16; q.ldw_lo = 0;
         return pnc_gemm_f16(&q, stream);
     }
-    PncGemmParams p = *pp;
-    normalise(p);
-    const unsigned epi = epilogue_with_ln(p);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    bool ln_fused = false;
-    int rc2;
-    switch (p.a_mode) {
-        case PNC_A_PLAIN: rc2 = dispatch_plain_ws(p, epi, st, &ln_fused, W_lo16); break;
-        case PNC_A_CONV3X3: rc2 = dispatch_conv3x3_ws(p, epi, st, W_lo16); break;
-        default: rc2 = dispatch_conv1d_ws(p, epi, st, W_lo16); break;
-    }
-    if (rc2 == PNC_OK && p.ln_out16 && !ln_fused)
-        rc2 = pnc_layernorm(p.out32, p.ldc32, p.M, p.N, p.ln_gamma, p.ln_beta, p.ln_eps, p.ln_out16, p.ldln, nullptr, stream);
-    return rc2;
+    return run_gemm(*pp, W_lo16, stream);
 }
 
 PNC_DEFINE_TU_COLLECT(gemm)

@@ -820,14 +820,60 @@ static inline void tail_split(int tiles, int& nfull, int& tail_f) {
     if (tail_f > 1) nfull = tiles - r;
 }
 
-// gemm_stencil_tile.hip
+// gemm_stencil_tile.hip (WS: the weight part of pnc_gemm_wsplit_f16, wlo16 = the fp16 lo plane of W beside the parameter block; NULL without)
 int conv3x3_tile_geometry(const PncGemmParams& p, unsigned epi);
-int dispatch_conv3x3_tiles(const PncGemmParams& p, unsigned epi, int geometry, hipStream_t st);
+template <bool WS>
+int dispatch_conv3x3_tiles(const PncGemmParams& p, unsigned epi, int geometry, hipStream_t st, const void* wlo16);
 
 // gemm.hip
 int launch_splitk_reduce(const PncGemmParams& p, int ksplit, hipStream_t st);
 
 const float* phi_table_device(hipStream_t st, int* rc);
+
+// ---- what every launcher below (and gemm_stencil_tile.hip's) does the same way
+static inline int current_device() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev;
+}
+
+// CUs of the device, asked once (the persistent kernels run one workgroup per CU)
+inline int cu_count(int dev) {
+    static std::atomic<int> ncu_of[64];
+    int ncu = ncu_of[dev & 63].load(std::memory_order_relaxed);
+    if (ncu == 0) {
+        int v = 0;
+        ncu = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+        ncu_of[dev & 63].store(ncu, std::memory_order_relaxed);
+    }
+    return ncu;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of `kern`, set once per device; `done`: the caller's static flags, one array per
+// kernel instantiation (the call is idempotent, so a race costs a second call)
+template <class K>
+static inline void set_dynamic_lds_once(std::atomic<unsigned char> (&done)[64], int dev, K kern, int bytes) {
+    if (done[dev & 63].load(std::memory_order_acquire)) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done[dev & 63].store(1, std::memory_order_release);
+}
+
+// grouped tile order (see the kernel): PNC_OPT_GEMM_GROUP_M row panels per group, auto = 4 when the problem has more than 8
+// column tiles; 0 = plain order
+static inline int grouped_tile_order(int tiles_m, int tiles_n) {
+    const int gopt = pnc_get_option(PNC_OPT_GEMM_GROUP_M);
+    int group_m = gopt > 0 ? gopt : (tiles_n > 8 ? 4 : 0);
+    if (group_m > tiles_m) group_m = tiles_m;
+    if (tiles_n < 2) group_m = 0;
+    return group_m;
+}
+
+// launch a kernel (WS: its _ws twin, which takes the plane as one more argument at the end)
+template <bool WS, class K, class... Args>
+static inline void launch_kernel(K kern, dim3 grid, dim3 block, int lds, hipStream_t st, const void* wlo16, const Args&... args) {
+    if constexpr (WS) hipLaunchKernelGGL(kern, grid, block, lds, st, args..., wlo16);
+    else hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+}
 
 // PERSISTENT form of the GEGLU GEMM (FF1; PNC_OPT_GEMM_PERSIST, on by default) — the first step of DESIGN.md section 12a: one workgroup
 // per CU walks its share of the output tiles, and the FIRST K tile of the next output tile is requested before the epilogue of the
@@ -863,37 +909,20 @@ int launch_geglu_persist(const PncGemmParams& p, hipStream_t st, const void* wlo
     constexpr int lds = 2 * (BM + BN) * 128;               // dynamic part: the operand ring (table and staging are static)
     static_assert(lds + PHI_BYTES + WGM * WGN * 2048 <= 160 * 1024, "LDS budget of one CU");
     static std::atomic<unsigned char> attr_done[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const void* kern;
-    if constexpr (WS) kern = reinterpret_cast<const void*>(gemm_geglu_persist_ws_kernel<BM, BN, WGM, WGN>);
-    else kern = reinterpret_cast<const void*>(gemm_geglu_persist_kernel<BM, BN, WGM, WGN>);
-    if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_done[dev & 63].store(1, std::memory_order_release);
-    }
+    const int dev = current_device();
+    const auto kern = [] {
+        if constexpr (WS) return gemm_geglu_persist_ws_kernel<BM, BN, WGM, WGN>;
+        else return gemm_geglu_persist_kernel<BM, BN, WGM, WGN>;
+    }();
+    set_dynamic_lds_once(attr_done, dev, kern, lds);
     int rc = PNC_OK;
     const float* phi = phi_table_device(st, &rc);
     if (rc != PNC_OK) return rc;
     const int tiles_n = p.N / BN, tiles_m = p.M / BM, tiles = tiles_m * tiles_n;
-    const int gopt = pnc_get_option(PNC_OPT_GEMM_GROUP_M);
-    int group_m = gopt > 0 ? gopt : (tiles_n > 8 ? 4 : 0);
-    if (group_m > tiles_m) group_m = tiles_m;
-    if (tiles_n < 2) group_m = 0;
-    static std::atomic<int> ncu_of[64];                    // CUs per device, asked once (one persistent workgroup per CU)
-    int ncu = ncu_of[dev & 63].load(std::memory_order_relaxed);
-    if (ncu == 0) {
-        int v = 0;
-        ncu = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-        ncu_of[dev & 63].store(ncu, std::memory_order_relaxed);
-    }
+    const int group_m = grouped_tile_order(tiles_m, tiles_n);
+    const int ncu = cu_count(dev);                         // one persistent workgroup per CU
     const int blocks = tiles < ncu ? tiles : ncu;
-    if constexpr (WS)
-        hipLaunchKernelGGL((gemm_geglu_persist_ws_kernel<BM, BN, WGM, WGN>), dim3(blocks), dim3(64 * WGM * WGN), lds, st, p, phi, group_m,
-                           pnc_get_option(PNC_OPT_GEMM_STAGGER), wlo16);
-    else
-        hipLaunchKernelGGL((gemm_geglu_persist_kernel<BM, BN, WGM, WGN>), dim3(blocks), dim3(64 * WGM * WGN), lds, st, p, phi, group_m,
-                           pnc_get_option(PNC_OPT_GEMM_STAGGER));
+    launch_kernel<WS>(kern, dim3(blocks), dim3(64 * WGM * WGN), lds, st, wlo16, p, phi, group_m, pnc_get_option(PNC_OPT_GEMM_STAGGER));
     return pnc_launch_status();
 }
 // the persistent kernel serves this problem (and the switch is on)
@@ -1328,25 +1357,12 @@ template <unsigned EPI>
 int launch_plain_persist(const PncGemmParams& p, hipStream_t st) {
     constexpr int lds = 2 * (256 + 320) * 128;
     static std::atomic<unsigned char> attr_done[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
+    const int dev = current_device();
     auto kern = gemm_persist_kernel<EPI>;
-    if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_done[dev & 63].store(1, std::memory_order_release);
-    }
+    set_dynamic_lds_once(attr_done, dev, kern, lds);
     const int tiles_n = p.N / 320, tiles_m = p.M / 256, tiles = tiles_m * tiles_n;
-    const int gopt = pnc_get_option(PNC_OPT_GEMM_GROUP_M);
-    int group_m = gopt > 0 ? gopt : (tiles_n > 8 ? 4 : 0);
-    if (group_m > tiles_m) group_m = tiles_m;
-    if (tiles_n < 2) group_m = 0;
-    static std::atomic<int> ncu_of[64];
-    int ncu = ncu_of[dev & 63].load(std::memory_order_relaxed);
-    if (ncu == 0) {
-        int v = 0;
-        ncu = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-        ncu_of[dev & 63].store(ncu, std::memory_order_relaxed);
-    }
+    const int group_m = grouped_tile_order(tiles_m, tiles_n);
+    const int ncu = cu_count(dev);
     const int blocks = tiles < ncu ? tiles : ncu;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, st, p, group_m | ((pnc_get_option(PNC_OPT_GEMM_FUSE_LN) & 2) ? 0x10000 : 0));
     return pnc_launch_status();
@@ -1360,18 +1376,13 @@ int launch(const PncGemmParams& p, hipStream_t st, int ksplit = 1, const void* w
     constexpr bool GEGLU = (EPI & E_GEGLU) != 0;
     static_assert(lds + (GEGLU ? PHI_BYTES : 0) <= 160 * 1024, "LDS budget of one CU (operand ring + GEGLU table)");
     static_assert(lds >= WGM * WGN * (32 * 68 * 4 + 64 * 8), "epilogue staging (+ LayerNorm row sums) must fit the operand ring");
-    static std::atomic<unsigned char> attr_done[64];      // per instantiation and device; the call is idempotent
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const void* kern;
-    if constexpr (WS) kern = reinterpret_cast<const void*>(gemm_glds_ws_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>);
-    else kern = reinterpret_cast<const void*>(gemm_glds_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>);
-    if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(kern,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds + (GEGLU ? PHI_BYTES : 0));
-        attr_done[dev & 63].store(1, std::memory_order_release);
-    }
-    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+    static std::atomic<unsigned char> attr_done[64];      // per instantiation and device
+    const auto kern = [] {
+        if constexpr (WS) return gemm_glds_ws_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>;
+        else return gemm_glds_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>;
+    }();
+    set_dynamic_lds_once(attr_done, current_device(), kern, lds + (GEGLU ? PHI_BYTES : 0));
+    const int tiles =((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     int nfull = tiles, tail_f = 1;
     if (ksplit == 1) tail_split<BM, WGM, lds>(tiles, nfull, tail_f);
     const int blocks = ksplit > 1 ? tiles * ksplit : nfull + (tiles - nfull) * tail_f;
@@ -1387,19 +1398,9 @@ int launch(const PncGemmParams& p, hipStream_t st, int ksplit = 1, const void* w
         q.bias = nullptr; q.rowbias = nullptr; q.res1 = nullptr; q.res2 = nullptr;
         q.out16 = nullptr; q.out16_lo = nullptr; q.out16t = nullptr; q.n_split = p.N; q.act = PNC_ACT_NONE;
     }
-    // grouped tile order (see the kernel): auto = 4 row panels per group when the problem has more than 8 column tiles
-    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-    const int gopt = pnc_get_option(PNC_OPT_GEMM_GROUP_M);
-    int group_m = gopt > 0 ? gopt : (tiles_n > 8 ? 4 : 0);           // 1 = plain order
-    if (group_m > tiles_m) group_m = tiles_m;
-    if (tiles_n < 2) group_m = 0;
+    const int group_m = grouped_tile_order((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);          // (1 = plain order too)
     const int stagger = (pnc_get_option(PNC_OPT_GEMM_STAGGER) & 0xFF) | ((pnc_get_option(PNC_OPT_GEMM_FUSE_LN) & 2) ? 0 : 0x100);
-    if constexpr (WS)
-        hipLaunchKernelGGL((gemm_glds_ws_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>), dim3(blocks), dim3(threads),
-                           lds + (GEGLU ? PHI_BYTES : 0), st, q, ksplit, nfull, tail_f, phi, group_m, stagger, wlo16);
-    else
-        hipLaunchKernelGGL((gemm_glds_kernel<AMODE, BM, BN, WGM, WGN, STAGES, PIPE, EPI>), dim3(blocks), dim3(threads),
-                           lds + (GEGLU ? PHI_BYTES : 0), st, q, ksplit, nfull, tail_f, phi, group_m, stagger);
+    launch_kernel<WS>(kern, dim3(blocks), dim3(threads), lds + (GEGLU ? PHI_BYTES : 0), st, wlo16, q, ksplit, nfull, tail_f, phi, group_m, stagger);
     if (ksplit > 1) return launch_splitk_reduce(p, ksplit, st);
     return pnc_launch_status();
 }

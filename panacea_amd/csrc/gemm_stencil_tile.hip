@@ -50,38 +50,31 @@ constexpr int stencil_lds_bytes() {
     return 2 * ((HROWS + 7) / 8) * 1024 + 3 * NI * 64 * 64;
 }
 
-template <int TWS, int NI, unsigned EPI, bool WS = false>
-static int launch_stencil(const PncGemmParams& p, hipStream_t st, const void* wlo16 = nullptr) {
+template <int TWS, int NI, unsigned EPI, bool WS>
+static int launch_stencil(const PncGemmParams& p, hipStream_t st, const void* wlo16) {
     constexpr int TW = 1 << TWS, TH = 256 / TW, BN = NI * 64;
     constexpr int lds = stencil_lds_bytes<TWS, NI>();
     static std::atomic<unsigned char> attr_done[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const void* kern;
-    if constexpr (WS) kern = reinterpret_cast<const void*>(stencil_tile_ws_kernel<TWS, NI, EPI>);
-    else kern = reinterpret_cast<const void*>(stencil_tile_kernel<TWS, NI, EPI>);
-    if (!attr_done[dev & 63].load(std::memory_order_acquire)) {
-        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_done[dev & 63].store(1, std::memory_order_release);
-    }
+    const auto kern = [] {
+        if constexpr (WS) return stencil_tile_ws_kernel<TWS, NI, EPI>;
+        else return stencil_tile_kernel<TWS, NI, EPI>;
+    }();
+    set_dynamic_lds_once(attr_done, current_device(), kern, lds);
     const int tiles_m = (p.M / (p.Hout * p.Wout)) * (p.Hout / TH) * (p.Wout >> TWS), tiles_n = (p.N + BN - 1) / BN;
-    const int gopt = pnc_get_option(PNC_OPT_GEMM_GROUP_M);
-    int group_m = gopt > 0 ? gopt : (tiles_n > 8 ? 4 : 0);
-    if (group_m > tiles_m) group_m = tiles_m;
-    if (group_m == 1 || tiles_n < 2) group_m = 0;
+    int group_m = grouped_tile_order(tiles_m, tiles_n);
+    if (group_m == 1) group_m = 0;                     // (this kernel's plain order is 0 alone)
     int nfull = tiles_m * tiles_n, tail_f = 1;
     tail_split<256, 4, lds>(tiles_m * tiles_n, nfull, tail_f);            // one workgroup per CU: 256 slots per round
     const int stagger = pnc_get_option(PNC_OPT_GEMM_STAGGER) == 1 ? 1 : (((pnc_get_option(PNC_OPT_STENCIL_TILES) & 4) ? 2 : 0) | ((pnc_get_option(PNC_OPT_GEMM_FUSE_LN) & 2) ? 4 : 0));
     const dim3 grid(nfull + (tiles_m * tiles_n - nfull) * tail_f);
-    if constexpr (WS) hipLaunchKernelGGL((stencil_tile_ws_kernel<TWS, NI, EPI>), grid, dim3(512), lds, st, p, group_m, nfull, tail_f, stagger, wlo16);
-    else hipLaunchKernelGGL((stencil_tile_kernel<TWS, NI, EPI>), grid, dim3(512), lds, st, p, group_m, nfull, tail_f, stagger);
+    launch_kernel<WS>(kern, grid, dim3(512), lds, st, wlo16, p, group_m, nfull, tail_f, stagger);
     // (stagger = 1: the staggered schedule, measured 5-15 % slower than the pipeline, only on request; + 2: the pipeline with the fragment
     // addresses computed next to the reads, as in round 5; + 4: the fp32-only epilogue staged through LDS, as in round 5)
     return pnc_launch_status();
 }
 
-template <int TWS, int NI, bool WS = false>
-static int dispatch_epi(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16 = nullptr) {
+template <int TWS, int NI, bool WS>
+static int dispatch_epi(const PncGemmParams& p, unsigned epi, hipStream_t st, const void* wlo16) {
     switch (epi) {
         case E_O16: return launch_stencil<TWS, NI, E_O16, WS>(p, st, wlo16);
         case E_O32: return launch_stencil<TWS, NI, E_O32, WS>(p, st, wlo16);
@@ -123,27 +116,22 @@ int conv3x3_tile_geometry(const PncGemmParams& p, unsigned epi) {
     return (tws << 4) | ni;
 }
 
-int dispatch_conv3x3_tiles(const PncGemmParams& p, unsigned epi, int geometry, hipStream_t st) {
+// WS: the same geometries with the weight part (pnc_gemm_wsplit_f16)
+template <bool WS>
+int dispatch_conv3x3_tiles(const PncGemmParams& p, unsigned epi, int geometry, hipStream_t st, const void* wlo16) {
+    if constexpr (WS) {
+        if (p.A_lo) return PNC_EINVAL;          // the tile kernel's weight part is the two-pass form for A_lo == NULL (the `gn_res` convs)
+    }
     switch (geometry) {
-        case (4 << 4) | 5: return dispatch_epi<4, 5>(p, epi, st);
-        case (4 << 4) | 4: return dispatch_epi<4, 4>(p, epi, st);
-        case (5 << 4) | 5: return dispatch_epi<5, 5>(p, epi, st);
-        case (5 << 4) | 4: return dispatch_epi<5, 4>(p, epi, st);
+        case (4 << 4) | 5: return dispatch_epi<4, 5, WS>(p, epi, st, wlo16);
+        case (4 << 4) | 4: return dispatch_epi<4, 4, WS>(p, epi, st, wlo16);
+        case (5 << 4) | 5: return dispatch_epi<5, 5, WS>(p, epi, st, wlo16);
+        case (5 << 4) | 4: return dispatch_epi<5, 4, WS>(p, epi, st, wlo16);
         default: return PNC_EINVAL;
     }
 }
-
-// the same geometries with the weight part (pnc_gemm_wsplit_f16; the caller passes a launch whose A_lo is NULL)
-int dispatch_conv3x3_tiles_ws(const PncGemmParams& p, unsigned epi, int geometry, hipStream_t st, const void* wlo16) {
-    if (p.A_lo) return PNC_EINVAL;
-    switch (geometry) {
-        case (4 << 4) | 5: return dispatch_epi<4, 5, true>(p, epi, st, wlo16);
-        case (4 << 4) | 4: return dispatch_epi<4, 4, true>(p, epi, st, wlo16);
-        case (5 << 4) | 5: return dispatch_epi<5, 5, true>(p, epi, st, wlo16);
-        case (5 << 4) | 4: return dispatch_epi<5, 4, true>(p, epi, st, wlo16);
-        default: return PNC_EINVAL;
-    }
-}
+template int dispatch_conv3x3_tiles<false>(const PncGemmParams&, unsigned, int, hipStream_t, const void*);
+template int dispatch_conv3x3_tiles<true>(const PncGemmParams&, unsigned, int, hipStream_t, const void*);
 
 }  // namespace pnc_gemm
 

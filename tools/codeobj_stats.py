@@ -1,11 +1,18 @@
 """Per-kernel resource table of the gfx950 code objects: VGPRs, SGPRs, spills, scratch, LDS, machine-code bytes.
 
-    python tools/codeobj_stats.py [source.hip ...]        (default: every source of panacea_amd/build.py)
+    python tools/codeobj_stats.py [--digest] [source.hip ...]        (default: every source of panacea_amd/build.py)
 
 Compiles each source device-only with the build's own flags (hipcc cross-compiles without a GPU), reads the
 AMDGPU metadata notes and the symbol table with llvm-readelf.  The output committed under profiles/ is the evidence
 for "no scratch, fits the instruction cache" claims.
+
+--digest appends to each line twelve hex digits of the SHA-256 over the kernel's machine-code bytes in .text, and the source
+the kernel was compiled in.  Two trees whose tables agree line for line (after `sort`) in every column, digest included, ship the
+same device code in the same translation units: the way a host-side or schedule-neutral refactor proves itself without a GPU.
+Within a source the lines are ordered by code size, then name — not by the order in which the translation unit instantiates
+its kernels.
 """
+import hashlib
 import re
 import subprocess
 import sys
@@ -32,18 +39,23 @@ def device_elf(src: Path, tmp: Path) -> Path:
 def kernels(elf: Path):
     notes = subprocess.check_output([READELF, "--notes", str(elf)], text=True)
     syms = subprocess.check_output([READELF, "-sW", str(elf)], text=True)
-    size = {}
+    size, addr = {}, {}
     for ln in syms.splitlines():
         f = ln.split()
         if len(f) >= 8 and f[3] == "FUNC":
-            size[f[7]] = int(f[2])
+            size[f[7]], addr[f[7]] = int(f[2]), int(f[1], 16)
+    # .text: its address and file offset, for the bytes of a function
+    text = re.search(r"\]\s+\.text\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)", subprocess.check_output([READELF, "-SW", str(elf)], text=True))
+    text_addr, text_off = int(text.group(1), 16), int(text.group(2), 16)
+    image = elf.read_bytes()
     out = []
     for blk in notes.split("- .agpr_count")[1:]:
         g = lambda k: re.search(rf"\.{k}:\s+(\S+)", blk)   # noqa: E731
         name = g("name").group(1)
         out.append(dict(name=name, vgpr=int(g("vgpr_count").group(1)), sgpr=int(g("sgpr_count").group(1)),
                         spill=int(g("vgpr_spill_count").group(1)), scratch=int(g("private_segment_fixed_size").group(1)),
-                        lds=int(g("group_segment_fixed_size").group(1)), code=size.get(name, 0)))
+                        lds=int(g("group_segment_fixed_size").group(1)), code=size.get(name, 0),
+                        digest=hashlib.sha256(image[text_off + addr.get(name, text_addr) - text_addr:][:size.get(name, 0)]).hexdigest()[:12]))
     return out
 
 
@@ -56,13 +68,15 @@ def short(name: str) -> str:
 
 
 def main():
-    srcs = [Path(a) for a in sys.argv[1:]] or [B.CSRC / s for s in B.SOURCES]
+    args = [a for a in sys.argv[1:] if a != "--digest"]
+    digest = len(args) != len(sys.argv[1:])
+    srcs = [Path(a) for a in args] or [B.CSRC / s for s in B.SOURCES]
     worst = dict(spill=0, scratch=0, code=0)
     with tempfile.TemporaryDirectory() as td:
-        print(f"{'kernel':86s} {'vgpr':>5s} {'sgpr':>5s} {'spill':>5s} {'scratch':>7s} {'code B':>8s}")
+        print(f"{'kernel':86s} {'vgpr':>5s} {'sgpr':>5s} {'spill':>5s} {'scratch':>7s} {'code B':>8s}" + (f" {'sha256':>12s} source" if digest else ""))
         for s in srcs:
-            for k in sorted(kernels(device_elf(s, Path(td))), key=lambda k: -k["code"]):
-                print(f"{short(k['name'])[:86]:86s} {k['vgpr']:5d} {k['sgpr']:5d} {k['spill']:5d} {k['scratch']:7d} {k['code']:8d}")
+            for k in sorted(kernels(device_elf(s, Path(td))), key=lambda k: (-k["code"], k["name"])):
+                print(f"{short(k['name'])[:86]:86s} {k['vgpr']:5d} {k['sgpr']:5d} {k['spill']:5d} {k['scratch']:7d} {k['code']:8d}" + (f" {k['digest']} {s.stem}" if digest else ""))
                 for w in worst:
                     worst[w] = max(worst[w], k[w])
     print(f"max over all kernels: spill {worst['spill']}, scratch {worst['scratch']} B, code {worst['code']} B")
