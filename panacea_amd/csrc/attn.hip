@@ -21,7 +21,7 @@
 //    in total, so it is a bandwidth-bound VALU kernel: 8 lanes per (token, head), 16-byte loads.
 //    attn_temporal_wide_kernel: the same for 9 <= T <= 16, one wave per (pixel, head) on the 16x16 MFMA.
 #include "common.h"
-#include <stdlib.h>
+#include "attn_check.h"
 
 namespace {
 
@@ -778,23 +778,19 @@ __global__ __launch_bounds__(256) void attn_temporal_wide_kernel(
 
 constexpr int TEXT_HG = 5;          // heads per workgroup of attn_text_kernel
 
-// argument checks of pnc_attn_views_f16: PNC_OK, or the code it returns without launching
+// argument checks of pnc_attn_views_f16: PNC_OK, or the code it returns without launching.  The geometry rules shared with the split
+// entry point are attn_check.h's.
 int attn_views_check(const PncAttnParams* pp) {
     if (!pp) return PNC_EINVAL;
     const PncAttnParams& p = *pp;
     if (!p.q || !p.k || !p.vt || !p.o) return PNC_EINVAL;
-    if (p.views < 1 || p.views > 8 || p.kv_views < 1 || p.kv_views > 8) return PNC_EINVAL;
-    if (p.W % p.views || p.kvW % p.kv_views) return PNC_EINVAL;
-    const int kvWv = p.kvW / p.kv_views;   // any view width: V^T chunks fall back to a per-key gather when a view row is not 8-aligned
+    if (!pnc_attn::views_ok(p)) return PNC_EINVAL;   // any view width: V^T chunks fall back to a per-key gather when a view row is not 8-aligned
     if (p.ldq % 8 || p.ldk % 8 || p.ldo % 4) return PNC_EALIGN;
-    if (((uintptr_t)p.q | (uintptr_t)p.k) & 15) return PNC_EALIGN;
-    if ((uintptr_t)p.vt & 15) return PNC_EALIGN;
-    if ((uintptr_t)p.o & 7) return PNC_EALIGN;
-    if (p.q_per_kv < 1 || p.groups < 1 || p.heads < 1) return PNC_EINVAL;
-    if (p.kv_valid < 1 || p.kv_valid > p.kvH * kvWv) return PNC_EINVAL;
+    if ((((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.vt) & 15) || ((uintptr_t)p.o & 7)) return PNC_EALIGN;
+    if (!pnc_attn::counts_ok(p)) return PNC_EINVAL;
     if (p.causal != 0 && p.causal != 1) return PNC_EINVAL;
     for (int v = 0; v < p.views; ++v) {
-        if (p.nseg[v] < 1 || p.nseg[v] > 2) return PNC_EINVAL;
+        if (!pnc_attn::nseg_ok(p, v)) return PNC_EINVAL;
         for (int s = 0; s < p.nseg[v]; ++s) {
             const int id = p.seg[v][s];
             if (id == -1 || id == p.kv_views) {          // a halo view: its buffers must be there, laid out like the band's
@@ -831,6 +827,58 @@ bool attn_text_dispatch(const PncAttnParams& p) {
     return text_ok && (force == 43 || (force == 0 && big_enough)) && (dopt & 3) != 0 && !(dopt & 4);
 }
 
+// (waves, query blocks per wave) of the attn_views_kernel launch as 10 * waves + blocks: 41, 42, 81 or 82 — 32 * waves * blocks queries
+// per workgroup.  `force` = PNC_OPT_ATTN_VARIANT (tests / kbench): 41 and up names the variant, 1 is the size heuristic with 82 in the
+// place of 42 (whole-step A/B of the old choice).  Measured in profiles/round1/kbench_attn_variants.log, profiles/round4/attn_ab_r4a.log.
+int views_variant(const PncAttnParams& p, int Nq, int force) {
+    if (force >= 41) return force;
+    if (p.kv_valid * 2 <= 256) {                                  // at most two K/V segments per view
+        // Few keys per view (the 77 text tokens: two K/V tiles): the launch is a stream of q in / o out.  Round 3 took 4 waves x 1 block
+        // (three small workgroups per CU: 90 / 48 / 30 us at levels 0-2 vs 100 / 53 / 37 for 8 x 2); with two workgroups per CU the
+        // 4 x 2 shape (256 queries per workgroup: half the per-workgroup prologues) is faster still — 84 / 45 / 27 us vs 110 / 55 / 33
+        // on one box (tools/exp/text_attn_variants.py, profiles/round4/attn_text_variants_r4k.txt).
+        return Nq >= 256 ? 42 : 41;
+    }
+    // Large views (>= 512 queries): 4 waves x 2 blocks, TWO workgroups per CU (round 4).  Two blocks per wave: every K / V^T fragment
+    // read feeds two MFMAs (600-670 TFLOP/s at level 0 vs 470-500 for 4 x 1).  The 8 x 2 workgroup it replaces shares each K/V tile
+    // among 512 queries but its barrier re-aligns the two waves of every SIMD each tile, so their softmax (VALU) and MFMA phases
+    // coincide and add up; two independent workgroups drift apart and overlap them: level 0 intra 685 -> 638 us, cross 1221 -> 1164,
+    // level 1 intra 111 -> 100 (same box, interleaved: profiles/round4/attn_ab_r4a.log).
+    if (Nq >= 512) return force == 1 ? 82 : 42;
+    if (Nq >= 256) return 81;                                     // mid-size views: 8 x 1 (256 queries)
+    return 41;                                                    // small views: 4 x 1 (128)
+}
+
+// What attn_views_kernel takes beside p, from p and the library options: wv_shift = log2(kv view width) when that is a power of two, else
+// -1; defer_thr = PNC_OPT_ATTN_DEFER_MAX in 0 .. 14; dma_mode = PNC_OPT_ATTN_DMA & 3, dma = it is on and every V^T row is 16-byte
+// addressable (the kernel's DMA template argument); sum_lim = 2^PNC_OPT_ATTN_SUM_TRIGGER (at most 2^14), 0 when that is off.
+struct ViewsArgs { int wv_shift; float defer_thr; int dma_mode; bool dma; float sum_lim; };
+ViewsArgs views_args(const PncAttnParams& p) {
+    const int kvWv = p.kvW / p.kv_views, dma_mode = pnc_get_option(PNC_OPT_ATTN_DMA) & 3;
+    const int dopt = pnc_get_option(PNC_OPT_ATTN_DEFER_MAX), sopt = pnc_get_option(PNC_OPT_ATTN_SUM_TRIGGER);
+    const bool dma = ((kvWv & 7) == 0) && ((p.kvW & 7) == 0) && ((p.ldvt & 7) == 0) && ((p.vt_gstride & 7) == 0) && dma_mode != 0;
+    int wv_shift = -1;
+    if (kvWv > 0 && (kvWv & (kvWv - 1)) == 0) { wv_shift = 0; while ((1 << wv_shift) < kvWv) ++wv_shift; }
+    return {wv_shift, (float)(dopt < 0 ? 0 : (dopt > 14 ? 14 : dopt)), dma_mode, dma, sopt <= 0 ? 0.0f : ldexpf(1.0f, sopt > 14 ? 14 : sopt)};
+}
+
+template <int NW, int QB>
+void launch_views(const PncAttnParams& p, const ViewsArgs& a, hipStream_t st) {
+    constexpr int QTILE = 32 * NW * QB;
+    const int Nq = p.H * (p.W / p.views);
+    const dim3 grid(((Nq + QTILE - 1) / QTILE) * p.views * p.groups * p.heads), block(64 * NW);
+    hipLaunchKernelGGL((a.dma ? attn_views_kernel<NW, QB, true> : attn_views_kernel<NW, QB, false>), grid, block, 0, st, p, a.wv_shift, a.defer_thr,
+                       a.dma_mode, a.sum_lim);
+}
+
+// the two temporal kernels, four waves = four work items per block: both begin with q, k, v, o and their leading dimensions, `tail` is the rest
+template <typename... Sig, typename... Tail>
+void launch_temporal(void (*kernel)(Sig...), int64_t nwork, void* stream, const void* q, int ldq, const void* k, int ldk,
+                     const void* v, int ldv, void* o, int ldo, Tail... tail) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((nwork + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), f16p(q), ldq,
+                       f16p(k), ldk, f16p(v), ldv, f16p(o), ldo, tail...);
+}
+
 }  // namespace
 
 extern "C" int pnc_attn_uses_text_kernel(const PncAttnParams* pp) {
@@ -841,50 +889,21 @@ extern "C" int pnc_attn_views_f16(const PncAttnParams* pp, void* stream) {
     const int rc = attn_views_check(pp);
     if (rc != PNC_OK) return rc;
     const PncAttnParams& p = *pp;
-    const int kvWv = p.kvW / p.kv_views;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Nq = p.H * (p.W / p.views);
-    // variants: (waves, query blocks per wave) -> queries per workgroup.  Two blocks per wave: every K / V^T fragment read feeds
-    // two MFMAs (600-670 TFLOP/s at level 0 vs 470-500 for 4 x 1); mid-size views: 8 x 1 (256 queries); small views: 4 x 1
-    // (128).  Measured in profiles/round1/kbench_attn_variants.log, profiles/round4/attn_ab_r4a.log.
-    const int force = pnc_get_option(PNC_OPT_ATTN_VARIANT);      // tests / kbench: force one variant
-    // Few keys per view (the 77 text tokens: two K/V tiles): the launch is a stream of q in / o out.  Round 3 took 4 waves x 1 block
-    // (three small workgroups per CU: 90 / 48 / 30 us at levels 0-2 vs 100 / 53 / 37 for 8 x 2); with two workgroups per CU the
-    // 4 x 2 shape (256 queries per workgroup: half the per-workgroup prologues) is faster still — 84 / 45 / 27 us vs 110 / 55 / 33
-    // on one box (tools/exp/text_attn_variants.py, profiles/round4/attn_text_variants_r4k.txt).
-    const int kv_keys = p.kv_valid * 2;                           // at most two K/V segments per view
-    // Large views (>= 512 queries): 4 waves x 2 blocks, TWO workgroups per CU (round 4).  The 8 x 2 workgroup it replaces shares
-    // each K/V tile among 512 queries but its barrier re-aligns the two waves of every SIMD each tile, so their softmax (VALU)
-    // and MFMA phases coincide and add up; two independent workgroups drift apart and overlap them: level 0 intra 685 -> 638 us,
-    // cross 1221 -> 1164, level 1 intra 111 -> 100 (same box, interleaved: profiles/round4/attn_ab_r4a.log).  force = 1: the size
-    // heuristic with 82 in the place of 42 (whole-step A/B of the old choice).
     if (attn_text_dispatch(p)) {
         const int nhg = (p.heads + TEXT_HG - 1) / TEXT_HG;
         const dim3 grid((unsigned)((long)((Nq + 127) / 128) * nhg * p.groups));
-        hipLaunchKernelGGL((attn_text_kernel<TEXT_HG>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, nhg);
+        hipLaunchKernelGGL((attn_text_kernel<TEXT_HG>), grid, dim3(256), 0, st, p, nhg);
         return pnc_launch_status();
     }
-    const int big = force == 1 ? 82 : 42;
-    const int variant = force >= 41 ? force : (kv_keys <= 256 ? (Nq >= 256 ? 42 : 41) : (Nq >= 512 ? big : (Nq >= 256 ? 81 : 41)));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int dma_mode = pnc_get_option(PNC_OPT_ATTN_DMA) & 3;
-    const bool dma = ((kvWv & 7) == 0) && ((p.kvW & 7) == 0) && ((p.ldvt & 7) == 0) && ((p.vt_gstride & 7) == 0) && dma_mode != 0;
-    int wv_shift = -1;
-    if (kvWv > 0 && (kvWv & (kvWv - 1)) == 0) { wv_shift = 0; while ((1 << wv_shift) < kvWv) ++wv_shift; }
-    int dopt = pnc_get_option(PNC_OPT_ATTN_DEFER_MAX);
-    const float defer_thr = (float)(dopt < 0 ? 0 : (dopt > 14 ? 14 : dopt));
-    const int sopt = pnc_get_option(PNC_OPT_ATTN_SUM_TRIGGER);
-    const float sum_lim = sopt <= 0 ? 0.0f : ldexpf(1.0f, sopt > 14 ? 14 : sopt);
-#define PNC_ATTN_LAUNCH(NW_, QB_, QTILE_)                                                                         \
-    do {                                                                                                          \
-        dim3 grid(((Nq + (QTILE_) - 1) / (QTILE_)) * p.views * p.groups * p.heads);                               \
-        if (dma) hipLaunchKernelGGL((attn_views_kernel<NW_, QB_, true>), grid, dim3(64 * NW_), 0, st, p, wv_shift, defer_thr, dma_mode, sum_lim);  \
-        else hipLaunchKernelGGL((attn_views_kernel<NW_, QB_, false>), grid, dim3(64 * NW_), 0, st, p, wv_shift, defer_thr, dma_mode, sum_lim);   \
-    } while (0)
-    if (variant == 42) PNC_ATTN_LAUNCH(4, 2, 256);
-    else if (variant == 82) PNC_ATTN_LAUNCH(8, 2, 512);
-    else if (variant == 81) PNC_ATTN_LAUNCH(8, 1, 256);
-    else PNC_ATTN_LAUNCH(4, 1, 128);
-#undef PNC_ATTN_LAUNCH
+    const ViewsArgs a = views_args(p);
+    switch (views_variant(p, Nq, pnc_get_option(PNC_OPT_ATTN_VARIANT))) {
+        case 42: launch_views<4, 2>(p, a, st); break;
+        case 82: launch_views<8, 2>(p, a, st); break;
+        case 81: launch_views<8, 1>(p, a, st); break;
+        default: launch_views<4, 1>(p, a, st);
+    }
     return pnc_launch_status();
 }
 
@@ -895,24 +914,11 @@ extern "C" int pnc_attn_temporal_f16(const void* q, int ldq, const void* k, int 
     if (T < 1 || T > 16 || B < 1 || Npix < 1 || heads < 1) return PNC_EINVAL;
     if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return PNC_EALIGN;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return PNC_EALIGN;
-    if (T > 8) {                        // 9 .. 16 frames: one wave per (b, pixel, head) on the 16x16 MFMA
-        const int64_t nwork = (int64_t)B * Npix * heads;
-        if (nwork > 0x7fffffff) return PNC_EINVAL;
-        const int64_t blocks = (nwork + 3) / 4;
-        hipLaunchKernelGGL(attn_temporal_wide_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                           reinterpret_cast<hipStream_t>(stream),
-                           reinterpret_cast<const half_t*>(q), ldq, reinterpret_cast<const half_t*>(k), ldk,
-                           reinterpret_cast<const half_t*>(v), ldv, reinterpret_cast<half_t*>(o), ldo,
-                           T, Npix, heads, scale, (unsigned)nwork);
-        return pnc_launch_status();
-    }
-    const int ppw = 8 / T;
+    const bool wide = T > 8;            // 9 .. 16 frames: one wave per (b, pixel, head) on the 16x16 MFMA; up to 8: 8 / T pixels per wave
+    const int ppw = wide ? 1 : 8 / T;
     const int64_t nwork = (int64_t)B * ((Npix + ppw - 1) / ppw) * heads;
-    const int64_t blocks = (nwork + 3) / 4;
-    hipLaunchKernelGGL(attn_temporal_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const half_t*>(q), ldq, reinterpret_cast<const half_t*>(k), ldk,
-                       reinterpret_cast<const half_t*>(v), ldv, reinterpret_cast<half_t*>(o), ldo,
-                       B, T, Npix, heads, scale, ppw, nwork);
+    if (wide && nwork > 0x7fffffff) return PNC_EINVAL;
+    if (wide) launch_temporal(attn_temporal_wide_kernel, nwork, stream, q, ldq, k, ldk, v, ldv, o, ldo, T, Npix, heads, scale, (unsigned)nwork);
+    else launch_temporal(attn_temporal_kernel, nwork, stream, q, ldq, k, ldk, v, ldv, o, ldo, B, T, Npix, heads, scale, ppw, nwork);
     return pnc_launch_status();
 }

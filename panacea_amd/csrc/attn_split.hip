@@ -9,6 +9,7 @@
 // cross products accumulate in separate fp32 registers and meet once, scaled by 2^-11, in fp32.
 // Correctness first: K / Q fragments are 8-byte row loads, V^T fragments 2-byte gathers (no LDS staging, no tuning).
 #include "common.h"
+#include "attn_check.h"
 
 namespace {
 
@@ -208,8 +209,6 @@ __global__ __launch_bounds__(256) void attn_temporal_split_kernel(
     t.store(o + h * 64, o_lo + h * 64, qrow, qok, ldo, lane);
 }
 
-bool aligned8(const void* a) { return ((uintptr_t)a & 7) == 0; }
-
 }  // namespace
 
 extern "C" int pnc_attn_views_split_f16(const PncAttnSplitParams* sp, void* stream) {
@@ -218,25 +217,20 @@ extern "C" int pnc_attn_views_split_f16(const PncAttnSplitParams* sp, void* stre
     const PncAttnParams& p = sp->a;
     if (!p.q || !p.k || !p.vt || !p.o || !sp->q_lo || !sp->k_lo || !sp->v_lo || !sp->o_lo) return PNC_EINVAL;
     if (p.causal != 0 || p.k_halo[0] || p.k_halo[1] || p.vt_halo[0] || p.vt_halo[1]) return PNC_EINVAL;
-    if (p.views < 1 || p.views > 8 || p.kv_views < 1 || p.kv_views > 8) return PNC_EINVAL;
-    if (p.W % p.views || p.kvW % p.kv_views) return PNC_EINVAL;
-    if (p.q_per_kv < 1 || p.groups < 1 || p.heads < 1 || p.H < 1 || p.kvH < 1) return PNC_EINVAL;
-    const int kvWv = p.kvW / p.kv_views;
-    if (p.kv_valid < 1 || p.kv_valid > p.kvH * kvWv) return PNC_EINVAL;
-    if (p.kv_rows_per_group < p.kvH * p.kvW) return PNC_EINVAL;
+    if (!pnc_attn::views_ok(p) || !pnc_attn::counts_ok(p)) return PNC_EINVAL;           // the rules shared with pnc_attn_views_f16
+    if (p.H < 1 || p.kvH < 1 || p.kv_rows_per_group < p.kvH * p.kvW) return PNC_EINVAL;
     for (int v = 0; v < p.views; ++v) {
-        if (p.nseg[v] < 1 || p.nseg[v] > 2) return PNC_EINVAL;
+        if (!pnc_attn::nseg_ok(p, v)) return PNC_EINVAL;
         for (int s = 0; s < p.nseg[v]; ++s)
             if (p.seg[v][s] < 0 || p.seg[v][s] >= p.kv_views) return PNC_EINVAL;
     }
     if (p.ldq % 4 || p.ldk % 4 || p.ldvt % 4 || p.ldo % 4) return PNC_EALIGN;
-    if (!aligned8(p.q) || !aligned8(p.k) || !aligned8(p.vt) || !aligned8(p.o) || !aligned8(sp->q_lo) || !aligned8(sp->k_lo) ||
-        !aligned8(sp->v_lo) || !aligned8(sp->o_lo))
-        return PNC_EALIGN;
+    if (((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.vt | (uintptr_t)p.o | (uintptr_t)sp->q_lo | (uintptr_t)sp->k_lo | (uintptr_t)sp->v_lo |
+         (uintptr_t)sp->o_lo) & 7) return PNC_EALIGN;
     ViewsGeom G{};
     G.groups = p.groups; G.heads = p.heads; G.H = p.H; G.W = p.W; G.views = p.views; G.Wv = p.W / p.views;
     G.Nq = p.H * G.Wv; G.nqt = (G.Nq + 15) / 16;
-    G.kvW = p.kvW; G.kvWv = kvWv; G.kv_rows = p.kv_rows_per_group; G.q_per_kv = p.q_per_kv; G.kv_valid = p.kv_valid;
+    G.kvW = p.kvW; G.kvWv = p.kvW / p.kv_views; G.kv_rows = p.kv_rows_per_group; G.q_per_kv = p.q_per_kv; G.kv_valid = p.kv_valid;
     for (int v = 0; v < 8; ++v) {
         G.nseg[v] = p.nseg[v];
         G.seg[v][0] = p.seg[v][0];
@@ -245,10 +239,8 @@ extern "C" int pnc_attn_views_split_f16(const PncAttnSplitParams* sp, void* stre
     const int64_t ntiles = (int64_t)p.groups * p.views * G.nqt * p.heads;
     const int64_t blocks = (ntiles + 3) / 4;
     hipLaunchKernelGGL(attn_views_split_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const half_t*>(p.q), reinterpret_cast<const half_t*>(sp->q_lo), p.ldq,
-                       reinterpret_cast<const half_t*>(p.k), reinterpret_cast<const half_t*>(sp->k_lo), p.ldk,
-                       reinterpret_cast<const half_t*>(p.vt), reinterpret_cast<const half_t*>(sp->v_lo), p.ldvt,
-                       reinterpret_cast<half_t*>(p.o), reinterpret_cast<half_t*>(sp->o_lo), p.ldo, G, p.scale, ntiles);
+                       f16p(p.q), f16p(sp->q_lo), p.ldq, f16p(p.k), f16p(sp->k_lo), p.ldk, f16p(p.vt), f16p(sp->v_lo), p.ldvt,
+                       f16p(p.o), f16p(sp->o_lo), p.ldo, G, p.scale, ntiles);
     return pnc_launch_status();
 }
 
@@ -258,15 +250,12 @@ extern "C" int pnc_attn_temporal_split_f16(const void* q, const void* q_lo, int 
     if (!q || !k || !v || !o || !q_lo || !k_lo || !v_lo || !o_lo) return PNC_EINVAL;
     if (T < 1 || T > 16 || B < 1 || Npix < 1 || heads < 1) return PNC_EINVAL;
     if (ldq % 4 || ldk % 4 || ldv % 4 || ldo % 4) return PNC_EALIGN;
-    if (!aligned8(q) || !aligned8(k) || !aligned8(v) || !aligned8(o) || !aligned8(q_lo) || !aligned8(k_lo) || !aligned8(v_lo) ||
-        !aligned8(o_lo))
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)q_lo | (uintptr_t)k_lo | (uintptr_t)v_lo | (uintptr_t)o_lo) & 7)
         return PNC_EALIGN;
     const int64_t ntiles = (int64_t)B * Npix * heads;
     const int64_t blocks = (ntiles + 3) / 4;
     hipLaunchKernelGGL(attn_temporal_split_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(q_lo), ldq,
-                       reinterpret_cast<const half_t*>(k), reinterpret_cast<const half_t*>(k_lo), ldk,
-                       reinterpret_cast<const half_t*>(v), reinterpret_cast<const half_t*>(v_lo), ldv,
-                       reinterpret_cast<half_t*>(o), reinterpret_cast<half_t*>(o_lo), ldo, T, Npix, heads, scale, ntiles);
+                       f16p(q), f16p(q_lo), ldq, f16p(k), f16p(k_lo), ldk, f16p(v), f16p(v_lo), ldv, f16p(o), f16p(o_lo), ldo,
+                       T, Npix, heads, scale, ntiles);
     return pnc_launch_status();
 }

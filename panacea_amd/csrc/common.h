@@ -10,6 +10,9 @@ typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// host: the fp16 view of a void pointer of the C-ABI
+static inline const half_t* f16p(const void* p) { return reinterpret_cast<const half_t*>(p); }
+static inline half_t* f16p(void* p) { return reinterpret_cast<half_t*>(p); }
 
 #define PNC_WAVE 64
 

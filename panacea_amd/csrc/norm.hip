@@ -2,6 +2,7 @@
 // fp32 residual stream in (channels-last tokens), fp16 MFMA operand out, statistics in fp32
 // (chunk-local sums combined with Chan's parallel-variance formula).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -587,20 +588,55 @@ __global__ __launch_bounds__(256) void concat_add_stats_kernel(const float* __re
     }
 }
 
-}  // namespace
-
 constexpr int GN_MAXC = 4 * 64 * 12;       // J <= 12 float4 vectors per lane
 
-#define PNC_GN_DISPATCH(KERNEL, ...)                                                                           \
-    do {                                                                                                       \
-        const int J = (C / 4 + 63) / 64;                                                                       \
-        if (J <= 1) hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__);                                                \
-        else if (J == 2) hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__);                                           \
-        else if (J == 3) hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__);                                           \
-        else if (J <= 5) hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__);                                           \
-        else if (J <= 8) hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__);                                           \
-        else hipLaunchKernelGGL(KERNEL<12>, __VA_ARGS__);                                                      \
-    } while (0)
+// The row kernels (gn_stats / gn_apply / layernorm / concat_add_stats) are instantiated at J = 1, 2, 3, 5, 8, 12 float4 vectors per
+// lane: `launch` is called with std::integral_constant<int, rung> of the smallest rung that holds J.  CAP = 3 ends the ladder there
+// (concat_add_stats, whose channel slices keep J <= 3).
+template <int N> using int_c = std::integral_constant<int, N>;
+template <int CAP = 12, typename Launch>
+void dispatch_j(int J, Launch&& launch) {
+    if (J <= 1) launch(int_c<1>{});
+    else if (J == 2) launch(int_c<2>{});
+    else if (J == 3 || CAP == 3) launch(int_c<3>{});
+    else if constexpr (CAP > 3) {
+        if (J <= 5) launch(int_c<5>{});
+        else if (J <= 8) launch(int_c<8>{});
+        else launch(int_c<12>{});
+    }
+}
+int vectors_per_lane(int C) { return (C / 4 + 63) / 64; }
+
+// launch geometry of gn_temporal_kernel, every mode: PB pixels per block, <= 512 work items of 4 channels per block
+struct GnTemporalGeom { int PB; unsigned blocks; size_t lds; };
+GnTemporalGeom gn_temporal_geom(int B, int Npix, int C) {
+    int PB = 512 / (C / 4); if (PB < 1) PB = 1; if (PB > 16) PB = 16;
+    return {PB, (unsigned)(((int64_t)B * Npix + PB - 1) / PB), ((size_t)PB * (C / 2) * 2 + (size_t)PB * GROUPS * 2) * sizeof(float)};
+}
+
+// The alignment rules of both temporal entry points (their last check), then gn_temporal_kernel<T, MODE> for the T = 1 .. 16 local
+// frames of a pixel (256 threads up to 8 frames, 512 from 9 on) -> the status of the launch
+template <int MODE>
+int launch_gn_temporal(int T, void* stream, const float* x, int B, int Npix, int C, const float* gamma, const float* beta, float eps,
+                       void* y16, void* y16_lo, int lo_fmt, float* stats, int T_total, int t_pad) {
+    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return PNC_EALIGN;
+    if (((uintptr_t)y16 | (uintptr_t)y16_lo | (uintptr_t)stats) & 7) return PNC_EALIGN;
+    const GnTemporalGeom g = gn_temporal_geom(B, Npix, C);
+    auto launch = [&](auto frames) {
+        constexpr int TT = decltype(frames)::value;
+        hipLaunchKernelGGL((gn_temporal_kernel<TT, MODE>), dim3(g.blocks), dim3(TT <= 8 ? 256 : 512), g.lds, reinterpret_cast<hipStream_t>(stream),
+                           x, B, Npix, C, gamma, beta, eps, f16p(y16), y16_lo, lo_fmt, g.PB, stats, T_total, t_pad);
+    };
+    switch (T) {
+        case 1: launch(int_c<1>{}); break; case 2: launch(int_c<2>{}); break; case 3: launch(int_c<3>{}); break; case 4: launch(int_c<4>{}); break;
+        case 5: launch(int_c<5>{}); break; case 6: launch(int_c<6>{}); break; case 7: launch(int_c<7>{}); break; case 8: launch(int_c<8>{}); break;
+        case 9: launch(int_c<9>{}); break; case 10: launch(int_c<10>{}); break; case 11: launch(int_c<11>{}); break; case 12: launch(int_c<12>{}); break;
+        case 13: launch(int_c<13>{}); break; case 14: launch(int_c<14>{}); break; case 15: launch(int_c<15>{}); break; case 16: launch(int_c<16>{}); break;
+    }
+    return pnc_launch_status();
+}
+
+}  // namespace
 
 extern "C" int pnc_groupnorm_stats(const float* x, int ldx, int F, int Npix, int C,
                                    int pix_per_chunk, float* partial, void* stream) {
@@ -610,7 +646,9 @@ extern "C" int pnc_groupnorm_stats(const float* x, int ldx, int F, int Npix, int
     const int nchunk = (Npix + pix_per_chunk - 1) / pix_per_chunk;
     const size_t lds = ((size_t)4 * C + GROUPS) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    PNC_GN_DISPATCH(gn_stats_kernel, dim3(nchunk, F), dim3(256), lds, st, x, ldx, Npix, C, pix_per_chunk, partial);
+    dispatch_j(vectors_per_lane(C), [&](auto j) {
+        hipLaunchKernelGGL(gn_stats_kernel<decltype(j)::value>, dim3(nchunk, F), dim3(256), lds, st, x, ldx, Npix, C, pix_per_chunk, partial);
+    });
     return pnc_launch_status();
 }
 
@@ -625,16 +663,14 @@ extern "C" int pnc_concat_add_stats(const float* a, int C1, const float* s, cons
     const int nchunk = (Npix + pix_per_chunk - 1) / pix_per_chunk;
     // channel slices of whole groups, at most 3 float4 vectors per lane: S = 1, 2, 4 or 8
     int S = 1;
-    while (S < 8 && (C / S / 4 + 63) / 64 > 3 && (C / (2 * S)) % 4 == 0) S *= 2;        // slices of whole groups AND whole float4 vectors
-    if ((C / S / 4 + 63) / 64 > 3) return PNC_EINVAL;
-    const int J = (C / S / 4 + 63) / 64;
+    while (S < 8 && vectors_per_lane(C / S) > 3 && (C / (2 * S)) % 4 == 0) S *= 2;        // slices of whole groups AND whole float4 vectors
+    if (vectors_per_lane(C / S) > 3) return PNC_EINVAL;
     const size_t lds = ((size_t)4 * (C / S) + GROUPS) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    half_t* o16 = reinterpret_cast<half_t*>(out16);
-    const dim3 grid(nchunk, F, S);
-    if (J <= 1) hipLaunchKernelGGL(concat_add_stats_kernel<1>, grid, dim3(256), lds, st, a, C1, s, c, C2, Npix, pix_per_chunk, out32, o16, out16_lo, lo_fmt, partial);
-    else if (J == 2) hipLaunchKernelGGL(concat_add_stats_kernel<2>, grid, dim3(256), lds, st, a, C1, s, c, C2, Npix, pix_per_chunk, out32, o16, out16_lo, lo_fmt, partial);
-    else hipLaunchKernelGGL(concat_add_stats_kernel<3>, grid, dim3(256), lds, st, a, C1, s, c, C2, Npix, pix_per_chunk, out32, o16, out16_lo, lo_fmt, partial);
+    dispatch_j<3>(vectors_per_lane(C / S), [&](auto j) {
+        hipLaunchKernelGGL(concat_add_stats_kernel<decltype(j)::value>, dim3(nchunk, F, S), dim3(256), lds, st, a, C1, s, c, C2, Npix, pix_per_chunk,
+                           out32, f16p(out16), out16_lo, lo_fmt, partial);
+    });
     return pnc_launch_status();
 }
 
@@ -649,9 +685,10 @@ extern "C" int pnc_groupnorm_apply(const float* x, int ldx, int F, int Npix, int
     const int nchunk = (Npix + pix_per_chunk - 1) / pix_per_chunk;
     const size_t lds = ((size_t)(2 * C > 24 * GROUPS ? 2 * C : 24 * GROUPS) + 2 * GROUPS) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    half_t* y = reinterpret_cast<half_t*>(y16);
-    PNC_GN_DISPATCH(gn_apply_kernel, dim3(nchunk, F), dim3(256), lds, st, x, ldx, Npix, C, pix_per_chunk, partial,
-                    gamma, beta, eps, silu, y, ldy, y16_lo, lo_fmt, n_records > 0 ? n_records : nchunk);
+    dispatch_j(vectors_per_lane(C), [&](auto j) {
+        hipLaunchKernelGGL(gn_apply_kernel<decltype(j)::value>, dim3(nchunk, F), dim3(256), lds, st, x, ldx, Npix, C, pix_per_chunk, partial,
+                           gamma, beta, eps, silu, f16p(y16), ldy, y16_lo, lo_fmt, n_records > 0 ? n_records : nchunk);
+    });
     return pnc_launch_status();
 }
 
@@ -667,23 +704,7 @@ extern "C" int pnc_groupnorm_temporal_silu(const float* x, int B, int T, int Npi
     if (!x || !gamma || !beta || !y16 || B < 1 || Npix < 1) return PNC_EINVAL;
     if (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3) return PNC_EINVAL;
     if (C % 64 || C > 2048 || T < 1 || T > 16) return PNC_EINVAL;    // <= 512 four-channel items per pixel
-    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return PNC_EALIGN;
-    if (((uintptr_t)y16 | (uintptr_t)y16_lo) & 7) return PNC_EALIGN;
-    const int CP = C / 2;
-    int PB = 512 / (C / 4); if (PB < 1) PB = 1; if (PB > 16) PB = 16;       // <= 512 work items of 4 channels per block
-    const int64_t total = (int64_t)B * Npix;
-    const unsigned blocks = (unsigned)((total + PB - 1) / PB);
-    const size_t lds = ((size_t)PB * CP * 2 + (size_t)PB * GROUPS * 2) * sizeof(float);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    half_t* y = reinterpret_cast<half_t*>(y16);
-#define PNC_GNT(TT) case TT: hipLaunchKernelGGL((gn_temporal_kernel<TT, 0>), dim3(blocks), dim3(TT <= 8 ? 256 : 512), lds, st, \
-                                               x, B, Npix, C, gamma, beta, eps, y, y16_lo, lo_fmt, PB, (float*)nullptr, TT, 0); break;
-    switch (T) {
-        PNC_GNT(1) PNC_GNT(2) PNC_GNT(3) PNC_GNT(4) PNC_GNT(5) PNC_GNT(6) PNC_GNT(7) PNC_GNT(8)
-        PNC_GNT(9) PNC_GNT(10) PNC_GNT(11) PNC_GNT(12) PNC_GNT(13) PNC_GNT(14) PNC_GNT(15) PNC_GNT(16)
-    }
-#undef PNC_GNT
-    return pnc_launch_status();
+    return launch_gn_temporal<0>(T, stream, x, B, Npix, C, gamma, beta, eps, y16, y16_lo, lo_fmt, nullptr, T, 0);
 }
 
 extern "C" int pnc_groupnorm_temporal_part(const float* x, int B, int T, int Npix, int C,
@@ -693,27 +714,7 @@ extern "C" int pnc_groupnorm_temporal_part(const float* x, int B, int T, int Npi
     if (!x || !stats || B < 1 || Npix < 1 || (mode != 1 && mode != 2)) return PNC_EINVAL;
     if (C % 64 || C > 2048 || T < 1 || T > 16 || T_total < T || (t_pad != 0 && t_pad != 1)) return PNC_EINVAL;
     if (mode == 2 && (!gamma || !beta || !y16 || (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3))) return PNC_EINVAL;
-    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return PNC_EALIGN;
-    if (((uintptr_t)y16 | (uintptr_t)y16_lo | (uintptr_t)stats) & 7) return PNC_EALIGN;
-    const int CP = C / 2;
-    int PB = 512 / (C / 4); if (PB < 1) PB = 1; if (PB > 16) PB = 16;
-    const int64_t total = (int64_t)B * Npix;
-    const unsigned blocks = (unsigned)((total + PB - 1) / PB);
-    const size_t lds = ((size_t)PB * CP * 2 + (size_t)PB * GROUPS * 2) * sizeof(float);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    half_t* y = reinterpret_cast<half_t*>(y16);
-#define PNC_GNTP(TT) case TT:                                                                                              \
-        if (mode == 1) hipLaunchKernelGGL((gn_temporal_kernel<TT, 1>), dim3(blocks), dim3(TT <= 8 ? 256 : 512), lds, st, x, B, Npix, C, gamma, beta, \
-                                          eps, y, y16_lo, lo_fmt, PB, stats, T_total, t_pad);                              \
-        else hipLaunchKernelGGL((gn_temporal_kernel<TT, 2>), dim3(blocks), dim3(TT <= 8 ? 256 : 512), lds, st, x, B, Npix, C, gamma, beta, eps, y, \
-                                y16_lo, lo_fmt, PB, stats, T_total, t_pad);                                                \
-        break;
-    switch (T) {
-        PNC_GNTP(1) PNC_GNTP(2) PNC_GNTP(3) PNC_GNTP(4) PNC_GNTP(5) PNC_GNTP(6) PNC_GNTP(7) PNC_GNTP(8)
-        PNC_GNTP(9) PNC_GNTP(10) PNC_GNTP(11) PNC_GNTP(12) PNC_GNTP(13) PNC_GNTP(14) PNC_GNTP(15) PNC_GNTP(16)
-    }
-#undef PNC_GNTP
-    return pnc_launch_status();
+    return (mode == 1 ? launch_gn_temporal<1> : launch_gn_temporal<2>)(T, stream, x, B, Npix, C, gamma, beta, eps, y16, y16_lo, lo_fmt, stats, T_total, t_pad);
 }
 
 extern "C" int pnc_layernorm(const float* x, int ldx, int M, int C,
@@ -725,12 +726,10 @@ extern "C" int pnc_layernorm(const float* x, int ldx, int M, int C,
     if (((uintptr_t)y16 | (uintptr_t)y16_lo) & 7) return PNC_EALIGN;
     const unsigned blocks = (unsigned)(((int64_t)M + 4 * LN_R - 1) / (4 * LN_R));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    half_t* y = reinterpret_cast<half_t*>(y16);
-    const int J = (C / 4 + 63) / 64;
-#define PNC_LN(JJ) hipLaunchKernelGGL(layernorm_kernel<JJ>, dim3(blocks), dim3(256), 0, st, x, ldx, M, C, gamma, beta, eps, y, ldy, reinterpret_cast<half_t*>(y16_lo))
-    if (J <= 1) PNC_LN(1); else if (J == 2) PNC_LN(2); else if (J == 3) PNC_LN(3); else if (J <= 5) PNC_LN(5);
-    else if (J <= 8) PNC_LN(8); else PNC_LN(12);
-#undef PNC_LN
+    dispatch_j(vectors_per_lane(C), [&](auto j) {
+        hipLaunchKernelGGL(layernorm_kernel<decltype(j)::value>, dim3(blocks), dim3(256), 0, st, x, ldx, M, C, gamma, beta, eps,
+                           f16p(y16), ldy, f16p(y16_lo));
+    });
     return pnc_launch_status();
 }
 

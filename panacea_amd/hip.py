@@ -421,8 +421,10 @@ def _gemm_params(a16, w16, *, M, N, K, lda=0, a_mode=A_PLAIN, conv=None, tconv=N
     return p, lib, ws
 
 
-def _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
-                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal):
+def _attn_struct(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
+                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal=False, k_halo=None, vt_halo=None, into=None):
+    """The filled PncAttnParams of `attn_views` / `attn_uses_text_kernel` / `attn_views_split` (`into`: its AttnSplitParams.a)"""
+    p = AttnParams() if into is None else into
     p.q, p.ldq, p.k, p.ldk = _ptr(q), ldq, _ptr(k), ldk
     p.vt, p.ldvt, p.vt_gstride, p.o, p.ldo = _ptr(vt), ldvt, vt_gstride, _ptr(o), ldo
     p.groups, p.heads, p.H, p.W, p.views = groups, heads, H, W, views
@@ -433,18 +435,18 @@ def _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads,
         for j, u in enumerate(s):
             p.seg[v][j] = u
     p.scale, p.causal = scale, int(causal)
+    if k_halo is not None:
+        for i in range(2):
+            p.k_halo[i], p.vt_halo[i] = _ptr(k_halo[i]), _ptr(vt_halo[i])
+    return p
 
 
 def attn_views(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H, W, views,
                kvH, kvW, kv_views, kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal=False, k_halo=None, vt_halo=None):
     """`k_halo` / `vt_halo`: pairs (left, right) of buffers with the geometry of k / vt whose view column 0 holds a neighbour rank's
     view — kv view id -1 / kv_views in `segs` (PncAttnParams.k_halo)"""
-    p = AttnParams()
-    if k_halo is not None:
-        for i in range(2):
-            p.k_halo[i], p.vt_halo[i] = _ptr(k_halo[i]), _ptr(vt_halo[i])
-    _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
-                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal)
+    p = _attn_struct(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views, kv_rows_per_group,
+                     q_per_kv, kv_valid, segs, scale, causal, k_halo, vt_halo)
     nq = H * (W // views)
     nkeys = sum(len(sv) for sv in segs) * kv_valid
     _check(_timed("attn_views", 4.0 * groups * heads * nq * nkeys * 64, 0.0, load().pnc_attn_views_f16,
@@ -455,12 +457,8 @@ def attn_uses_text_kernel(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, group
                           kvH, kvW, kv_views, kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal=False, k_halo=None, vt_halo=None) -> bool:
     """pnc_attn_uses_text_kernel: would `attn_views` with these arguments, under the current options, launch the single-pass few-key
     kernel?  Answered by the library's own dispatch predicate; nothing is launched."""
-    p = AttnParams()
-    if k_halo is not None:
-        for i in range(2):
-            p.k_halo[i], p.vt_halo[i] = _ptr(k_halo[i]), _ptr(vt_halo[i])
-    _attn_params(p, q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views,
-                 kv_rows_per_group, q_per_kv, kv_valid, segs, scale, causal)
+    p = _attn_struct(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views, kv_rows_per_group,
+                     q_per_kv, kv_valid, segs, scale, causal, k_halo, vt_halo)
     return bool(load().pnc_attn_uses_text_kernel(C.byref(p)))
 
 
@@ -471,8 +469,8 @@ def attn_views_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, 
     f16 = torch.float16
     sp = AttnSplitParams()
     sp.struct_bytes = C.sizeof(AttnSplitParams)
-    _attn_params(sp.a, q, ldq, k, ldk, v, ldv, 0, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views, kv_rows_per_group,
-                 q_per_kv, kv_valid, segs, scale, False)
+    _attn_struct(q, ldq, k, ldk, v, ldv, 0, o, ldo, groups, heads, H, W, views, kvH, kvW, kv_views, kv_rows_per_group, q_per_kv,
+                 kv_valid, segs, scale, into=sp.a)
     sp.q_lo, sp.k_lo = _ptr(q_lo, f16, "q_lo"), _ptr(k_lo, f16, "k_lo")
     sp.v_lo, sp.o_lo = _ptr(v_lo, f16, "v_lo"), _ptr(o_lo, f16, "o_lo")
     nq = H * (W // views)

@@ -32,6 +32,17 @@ SPATIAL = [(2, 129, 64, 128), (2, 300, 320, 128), (1, 77, 1280, 16), (1, 1100, 3
 CONCAT = [(2, 100, 320, 320, True, 64), (1, 70, 1280, 640, False, 16), (1, 65, 1280, 1280, True, 64)]        # F, Npix, C1, C2, ctrl, ppc
 TEMPORAL = [(2, 1, 77, 64), (1, 3, 33, 320), (2, 8, 21, 1280), (1, 9, 19, 320), (1, 16, 5, 2048)]                # B, T, Npix, C
 LAYERNORM = [(7, 64), (513, 320), (33, 1280), (5, 3072)]                                                         # M, C
+# The rungs of the host dispatch the shapes above do not reach.  The row kernels are instantiated for J = 1, 2, 3, 5, 8, 12 float4
+# vectors per lane and a row of C channels needs ceil(C / 256): C = 1024 / 1536 / 2048 / 2304 need 4 / 6 / 8 / 9 and run on 5 / 8 / 8 /
+# 12 (GroupNorm: C = 640 needs 3).  The temporal kernel is instantiated per frame count, 1 .. 16, in three modes.  A wrong rung drops
+# or repeats channels (frames): these are the smallest shapes that show it.  Data, references and bounds are their neighbours'.
+LADDER = {"layernorm": [(5, C) for C in (1024, 1536, 2048, 2304)],                                               # M, C
+          "spatial": [(1, 70, C, 16) for C in (640, 1024, 1536, 2304)],                                          # F, Npix, C, ppc
+          "temporal": [(1, T, 5, 64) for T in range(1, 17)]}                                                     # B, T, Npix, C
+# pnc_groupnorm_temporal_part walks the temporal shapes at LADDER_PART_R only: modes 1 and 2 exchange raw moments (sum x, sum x^2), a
+# form that the bounds here separate from the kernels' own from r = 8 on (tests/test_norm_ref64.py, temporal_raw).  r = 0.5 is what
+# the rest of the suite draws for it, and the rung does not depend on r.
+LADDER_PART_R = 0.5
 
 
 def _gen(seed):

@@ -136,6 +136,45 @@ def test_layernorm_offsets(M, C, r):
         _check_output(f"layernorm {M}x{C} lo={lo} r={r:g}", y, ylo, lo, y64, xhat, gamma, r, "layernorm_kernel")
 
 
+# ------------------------------------------------------------------------------------------ every rung of the host dispatch
+# cases.LADDER: the J rungs and frame counts the shapes above leave out; the same references and bounds
+@pytest.mark.parametrize("r", cases.R)
+@pytest.mark.parametrize("F,Npix,C,ppc", cases.LADDER["spatial"])
+def test_ladder_groupnorm_spatial(F, Npix, C, ppc, r):
+    test_groupnorm_spatial_offsets(F, Npix, C, ppc, r)
+
+
+@pytest.mark.parametrize("r", cases.R)
+@pytest.mark.parametrize("M,C", cases.LADDER["layernorm"])
+def test_ladder_layernorm(M, C, r):
+    test_layernorm_offsets(M, C, r)
+
+
+@pytest.mark.parametrize("r", cases.R)
+@pytest.mark.parametrize("B,T,Npix,C", cases.LADDER["temporal"])
+def test_ladder_groupnorm_temporal(B, T, Npix, C, r):
+    test_groupnorm_temporal_offsets(B, T, Npix, C, r)
+
+
+@pytest.mark.parametrize("B,T,Npix,C", cases.LADDER["temporal"])
+def test_ladder_groupnorm_temporal_part(B, T, Npix, C):
+    """pnc_groupnorm_temporal_part, mode 1 then mode 2 with every frame local (T_total = T): the output of
+    pnc_groupnorm_temporal_silu, under the same bound"""
+    r = cases.LADDER_PART_R
+    x = cases.temporal(B, T, Npix, C, r)
+    gamma, beta = cases.affine(C)
+    y64, xhat = ref64.groupnorm_temporal_silu(x, B, T, Npix, C, gamma, beta, cases.EPS)
+    xd, gd, bd = x.to(DEV), gamma.to(DEV), beta.to(DEV)
+    stats = torch.full((B * Npix * 64,), float("nan"), device=DEV)
+    hip.groupnorm_temporal_part(xd, B, T, Npix, C, gd, bd, cases.EPS, stats, 1, T)
+    for lo in (None, "f16", "e4m3"):
+        y = torch.full((B * T * Npix, C), float("nan"), device=DEV, dtype=torch.float16)
+        ylo = _lo_plane(lo, B * T * Npix, C)
+        hip.groupnorm_temporal_part(xd, B, T, Npix, C, gd, bd, cases.EPS, stats, 2, T, y, ylo)
+        torch.cuda.synchronize()
+        _check_output(f"temporal part {B}x{T}x{Npix}x{C} lo={lo} r={r:g}", y, ylo, lo, y64, xhat, gamma, r, "gn_temporal_kernel modes 1, 2")
+
+
 # ------------------------------------------------------------------------------------------ channels with gamma = 0
 def test_zero_gamma_channels():
     """cases.affine keeps |gamma| >= 0.5; here every 8th channel has gamma = 0: the allowance vanishes there, the output is beta (or

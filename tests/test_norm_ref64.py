@@ -21,7 +21,7 @@ f32 = np.float32
 
 
 # ------------------------------------------------------------------------------------------ (a) the reference against torch
-@pytest.mark.parametrize("F,Npix,C,ppc", cases.SPATIAL)
+@pytest.mark.parametrize("F,Npix,C,ppc", cases.SPATIAL + cases.LADDER["spatial"])
 def test_ref64_spatial_vs_torch(F, Npix, C, ppc):
     x = cases.spatial(F, Npix, C, 8.0)
     gamma, beta = cases.affine(C)
@@ -42,7 +42,7 @@ def test_ref64_spatial_vs_torch(F, Npix, C, ppc):
     assert torch.equal(ref64.groupnorm(wide, C + 8, F, Npix, C, gamma, beta, cases.EPS, 1)[0], ref64.groupnorm(x, C, F, Npix, C, gamma, beta, cases.EPS, 1)[0])
 
 
-@pytest.mark.parametrize("B,T,Npix,C", cases.TEMPORAL)
+@pytest.mark.parametrize("B,T,Npix,C", cases.TEMPORAL + cases.LADDER["temporal"])
 def test_ref64_temporal_vs_torch(B, T, Npix, C):
     x = cases.temporal(B, T, Npix, C, 8.0)
     gamma, beta = cases.affine(C)
@@ -55,7 +55,7 @@ def test_ref64_temporal_vs_torch(B, T, Npix, C):
     assert torch.equal(yp[:, 1:T + 1], y) and torch.equal(xp[:, 1:T + 1], xhat)
 
 
-@pytest.mark.parametrize("M,C", cases.LAYERNORM)
+@pytest.mark.parametrize("M,C", cases.LAYERNORM + cases.LADDER["layernorm"])
 def test_ref64_layernorm_vs_torch(M, C):
     x = cases.row_sets(M, C, 8.0)
     gamma, beta = cases.affine(C)
@@ -99,7 +99,33 @@ def _half(tag, got, y64, xhat, gamma, r, lo=None):
 
 @pytest.mark.parametrize("r", cases.R)
 def test_emulation_within_half_of_the_bounds(r):
-    for F, Npix, C, ppc in cases.SPATIAL:
+    _emulation_within_half(r, cases.SPATIAL, cases.CONCAT, cases.TEMPORAL, cases.LAYERNORM)
+
+
+@pytest.mark.parametrize("r", cases.R)
+def test_emulation_within_half_of_the_bounds_on_the_ladder(r):
+    """cases.LADDER, the shapes tests/test_norm_offsets_gpu.py adds for the rungs of the host dispatch: the same walk"""
+    _emulation_within_half(r, cases.LADDER["spatial"], [], cases.LADDER["temporal"], cases.LADDER["layernorm"])
+
+
+def test_emulated_temporal_parts_within_half_of_the_bounds_on_the_ladder():
+    """pnc_groupnorm_temporal_part mode 1 then 2 with every frame local, the way the GPU test calls the kernel (at cases.LADDER_PART_R)"""
+    r = cases.LADDER_PART_R
+    for B, T, Npix, C in cases.LADDER["temporal"]:
+        x = cases.temporal(B, T, Npix, C, r)
+        gamma, beta = cases.affine(C)
+        y64, xhat = ref64.groupnorm_temporal_silu(x, B, T, Npix, C, gamma, beta, cases.EPS)
+        stats = torch.zeros(B * Npix * 64)
+        emu.groupnorm_temporal_part(x, B, T, Npix, C, gamma, beta, cases.EPS, stats, 1, T)
+        for lo in (None, "f16", "e4m3"):
+            y16 = torch.zeros(B * T * Npix, C, dtype=torch.float16)
+            ylo = None if lo is None else torch.zeros(B * T * Npix, C, dtype=cases.LO_DTYPE[lo])
+            emu.groupnorm_temporal_part(x, B, T, Npix, C, gamma, beta, cases.EPS, stats, 2, T, y16, ylo)
+            _half(f"temporal part {B}x{T}x{Npix}x{C} lo={lo}", cases.joined(y16, ylo).view(B, T, Npix, C), y64, xhat, gamma, r, lo)
+
+
+def _emulation_within_half(r, spatial, concat, temporal, layernorm):
+    for F, Npix, C, ppc in spatial:
         x = cases.spatial(F, Npix, C, r)
         gamma, beta = cases.affine(C)
         nchunk = -(-Npix // ppc)
@@ -119,7 +145,7 @@ def test_emulation_within_half_of_the_bounds(r):
                 ylo = None if lo is None else torch.zeros(F * Npix, C, dtype=cases.LO_DTYPE[lo])
                 emu.groupnorm_apply(x, C, F, Npix, C, ppc, part, gamma, beta, cases.EPS, silu, y16, C, ylo)
                 _half(f"spatial {F}x{Npix}x{C} silu={silu} lo={lo}", cases.joined(y16, ylo), y64, xhat, gamma, r, lo)
-    for F, Npix, C1, C2, ctrl, ppc in cases.CONCAT:
+    for F, Npix, C1, C2, ctrl, ppc in concat:
         a, s, c = cases.concat(F, Npix, C1, C2, ctrl, r)
         C, M, nchunk = C1 + C2, F * Npix, -(-Npix // ppc)
         o32, part = torch.zeros(M, C), torch.zeros(F * nchunk * 96)
@@ -130,7 +156,7 @@ def test_emulation_within_half_of_the_bounds(r):
         v64 = P64[..., 2] / P64[..., 0]
         st = cases.stats_excess(P[..., 1], P[..., 2] / P[..., 0], P64[..., 1], v64, cases.realised_r(P64[..., 1], v64).nan_to_num(0.0))
         assert st[1] <= 0.5 and st[3] <= 0.5, st
-    for B, T, Npix, C in cases.TEMPORAL:
+    for B, T, Npix, C in temporal:
         x = cases.temporal(B, T, Npix, C, r)
         gamma, beta = cases.affine(C)
         y64, xhat = ref64.groupnorm_temporal_silu(x, B, T, Npix, C, gamma, beta, cases.EPS)
@@ -139,7 +165,7 @@ def test_emulation_within_half_of_the_bounds(r):
             ylo = None if lo is None else torch.zeros(B * T * Npix, C, dtype=cases.LO_DTYPE[lo])
             emu.groupnorm_temporal_silu(x, B, T, Npix, C, gamma, beta, cases.EPS, y16, ylo)
             _half(f"temporal {B}x{T}x{Npix}x{C} lo={lo}", cases.joined(y16, ylo).view(B, T, Npix, C), y64, xhat, gamma, r, lo)
-    for M, C in cases.LAYERNORM:
+    for M, C in layernorm:
         x = cases.row_sets(M, C, r)
         gamma, beta = cases.affine(C)
         y64, xhat = ref64.layernorm(x, C, M, C, gamma, beta, cases.EPS)

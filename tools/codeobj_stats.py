@@ -7,13 +7,19 @@ AMDGPU metadata notes and the symbol table with llvm-readelf.  The output commit
 for "no scratch, fits the instruction cache" claims.
 
 --digest appends to each line twelve hex digits of the SHA-256 over the kernel's machine-code bytes in .text, and the source
-the kernel was compiled in.  Two trees whose tables agree line for line (after `sort`) in every column, digest included, ship the
+the kernel was compiled in.  The hash is of the INSTRUCTIONS, not of where the linker put them: a kernel reaches its globals and
+its callees pc-relative (s_getpc_b64, then s_add_u32 / s_addc_u32 with a 32-bit literal that is the distance from here to there),
+and that distance moves when anything else in the translation unit does.  Those literals are zeroed before hashing
+(placement_free), so one source line gives one digest in every translation unit that compiles it.  Tables written before this
+masking (profiles/*_codeobj.txt up to gemm_dispatch_codeobj.txt) differ from today's in the kernels that hold such a sequence; run
+the tool on both trees to compare.  Two trees whose tables agree line for line (after `sort`) in every column, digest included, ship the
 same device code in the same translation units: the way a host-side or schedule-neutral refactor proves itself without a GPU.
 Within a source the lines are ordered by code size, then name — not by the order in which the translation unit instantiates
 its kernels.
 """
 import hashlib
 import re
+import struct
 import subprocess
 import sys
 import tempfile
@@ -36,6 +42,21 @@ def device_elf(src: Path, tmp: Path) -> Path:
     return elf
 
 
+def placement_free(code: bytes) -> bytes:
+    """`code` with the literals of the s_add_u32 / s_addc_u32 that follow an s_getpc_b64 set to zero.  gfx9 encodings, one dword
+    each: SOP1 s_getpc_b64 = 0xBE80_1C00 | sdst << 16; SOP2 = 0b10 op[29:23] sdst[22:16] ssrc1[15:8] ssrc0[7:0] with op 0 = s_add_u32,
+    4 = s_addc_u32, and a source of 0xFF means that the next dword is the literal."""
+    w = list(struct.unpack(f"<{len(code) // 4}I", code[:len(code) & ~3]))
+    for i, d in enumerate(w):
+        if d & 0xFF80FFFF != 0xBE801C00:
+            continue
+        j = i + 1
+        while j + 1 < len(w) and w[j] & 0xFF800000 in (0x80000000, 0x82000000) and 0xFF in (w[j] & 0xFF, w[j] >> 8 & 0xFF):
+            w[j + 1] = 0
+            j += 2
+    return struct.pack(f"<{len(w)}I", *w) + code[len(code) & ~3:]
+
+
 def kernels(elf: Path):
     notes = subprocess.check_output([READELF, "--notes", str(elf)], text=True)
     syms = subprocess.check_output([READELF, "-sW", str(elf)], text=True)
@@ -55,7 +76,7 @@ def kernels(elf: Path):
         out.append(dict(name=name, vgpr=int(g("vgpr_count").group(1)), sgpr=int(g("sgpr_count").group(1)),
                         spill=int(g("vgpr_spill_count").group(1)), scratch=int(g("private_segment_fixed_size").group(1)),
                         lds=int(g("group_segment_fixed_size").group(1)), code=size.get(name, 0),
-                        digest=hashlib.sha256(image[text_off + addr.get(name, text_addr) - text_addr:][:size.get(name, 0)]).hexdigest()[:12]))
+                        digest=hashlib.sha256(placement_free(image[text_off + addr.get(name, text_addr) - text_addr:][:size.get(name, 0)])).hexdigest()[:12]))
     return out
 
 
