@@ -1,5 +1,7 @@
-"""Plain-torch emulation of every entry point of panacea_amd.hip (same names, same arguments,
-results written into the caller's output tensors).
+"""Plain-torch emulation of every wrapper of panacea_amd.hip that the product calls on its backend: same names, same parameters
+(names, order, keyword-only split, defaults — tests/test_emu_surface.py holds the two signatures together), results written into
+the caller's output tensors.  One module is the whole backend: `engine.use_backend(emu)` and nothing else.  The sections follow
+the order of hip.py: GEMM, attention, norms, small-M linears, embeddings and layout, sampler exits, elementwise, statistics.
 
 TEST INFRASTRUCTURE ONLY.  Two uses:
   * `-m gpu` kernel tests: HIP kernel vs this emulation on the same device tensors;
@@ -9,13 +11,13 @@ The product never imports it: `panacea_amd.hip` has no fallback and raises witho
 """
 from __future__ import annotations
 
-import math
-
+import numpy as np
 import torch
 import torch.nn.functional as TF
 
 A_PLAIN, A_CONV3X3, A_CONV1D_T = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
+SAMPLER_HEUN1, SAMPLER_HEUN2, SAMPLER_EULER_A, SAMPLER_DPM2S_1, SAMPLER_DPM2S_2, SAMPLER_DPM2M, SAMPLER_LMS = range(7)   # PNC_SAMPLER_*
 
 
 class PncError(RuntimeError):
@@ -45,13 +47,6 @@ def _lo(v: torch.Tensor, hi: torch.Tensor, like: torch.Tensor = None) -> torch.T
 
 
 _LO_CLAMPED = 0      # e4m3 lo-plane quads that clamped since the last range_monitor_collect (the kernels' per-quad count)
-
-
-def range_monitor_collect(out_i32: torch.Tensor):
-    """pnc_range_monitor_collect: adds the clamped-quad count since the previous call to out_i32[0] and resets it"""
-    global _LO_CLAMPED
-    out_i32[0] += _LO_CLAMPED
-    _LO_CLAMPED = 0
 
 
 def _lo_value(lo: torch.Tensor) -> torch.Tensor:
@@ -149,14 +144,37 @@ def _contract(a16, Wm, M, N, K, lda, a_mode, conv, tconv):
     return acc
 
 
-def gemm(a16, w16, *, M, N, K, lda=0, a_mode=A_PLAIN, conv=None, tconv=None, bias=None, rowbias=None,
-         rb_rows=0, rb_mod=0, res1=None, ldr1=0, res2=None, ldr2=0, out32=None, ldc32=0, out16=None,
-         ldc16=0, out16t=None, ldt=0, t_rows=0, t_gstride=0, n_split=0, act=ACT_NONE, geglu=False,
-         a16_lo=None, out16_lo=None, w_ld=0, ln_gamma=None, ln_beta=None, ln_out16=None, ldln=0, ln_eps=1e-5,
-         ln_in_library=False, w_lo=None, gn_part=None):
-    assert (not STRICT_DTYPES) or (a16.dtype == torch.float16 and w16.dtype == torch.float16)
+# ---- GEMM (pnc_gemm_f16 / pnc_gemm_wsplit_f16; the kernels are held to float64 by tests/test_gemm_edges_gpu.py) ----------------
+# Split operands: A W ~= A_hi W_hi + 2^-11 (A_lo W_hi + A_hi W_lo), the 2^-22 A_lo W_lo term dropped.  An fp16 A_lo is joined to
+# A_hi in fp32 ahead of the contraction; an e4m3 A_lo runs its own pass against the e4m3 copy of the weights (`w_lo` = the (bytes,
+# exponent) pair of engine.pk_lo8).  The fp16 lo plane of the WEIGHTS arrives as `w_lo` (PncGemmParams.W_lo, `precise-full`: next
+# to an fp16 A_lo only) or as `w_lo16` (beside the parameter block, pnc_gemm_wsplit_f16, `precise-ckpt`: next to every A_lo — none,
+# e4m3, or fp16, which the library forwards to the three-part launch).  The sum is linear in W, so 2^-11 A_hi W_lo is one more
+# contraction added to the fp32 accumulator ahead of the epilogue.
+def gemm(a16, w16, *, M, N, K, lda=0, a_mode=A_PLAIN, conv=None, tconv=None, bias=None, rowbias=None, rb_rows=0, rb_mod=0,
+         res1=None, ldr1=0, res2=None, ldr2=0, out32=None, ldc32=0, out16=None, ldc16=0, out16t=None, ldt=0, t_rows=0,
+         t_gstride=0, n_split=0, act=ACT_NONE, geglu=False, a16_lo=None, out16_lo=None, w_ld=0, w_lo=None, w_lo16=None,
+         ln_gamma=None, ln_beta=None, ln_out16=None, ldln=0, ln_eps=1e-5, ln_in_library=False, gn_part=None):
+    f16 = torch.float16
+    if w_lo16 is not None:
+        if w_lo16.dtype != f16 or w_lo16.shape != w16.shape:
+            raise PncError("w_lo16: the fp16 lo plane of the weights in w16's layout")
+        if a16_lo is not None and a16_lo.dtype == f16:
+            if w_lo is not None:
+                raise PncError("an fp16 A_lo is forwarded with W_lo = W_lo16: W_lo must be NULL (PNC_EINVAL)")
+            w_lo, w_lo16 = w_lo16, None
+    if isinstance(w_lo, torch.Tensor):                  # else None, or the (bytes, exponent) pair of an e4m3 lo pass
+        if a16_lo is None:
+            raise PncError("W_lo without A_lo (PNC_EINVAL)")
+        if a16_lo.dtype != f16 or w_lo.dtype != f16:
+            raise PncError("split weights go with fp16 lo planes")
+        w_lo, w_lo16 = None, w_lo
+    assert (not STRICT_DTYPES) or (a16.dtype == f16 and w16.dtype == f16)
     assert K % 8 == 0
     Wm = _mat(w16, N, K, w_ld or K).float()
+    acc_w = None                                        # 2^-11 A_hi W_lo, from the hi plane of A
+    if w_lo16 is not None:
+        acc_w = _contract(a16, _mat(w_lo16, N, K, w_ld or K).float(), M, N, K, lda, a_mode, conv, tconv) / LO_SCALE
     acc_lo = None
     if a16_lo is not None and a16_lo.dtype == torch.uint8:
         # e4m3 lo plane: its pass runs against the e4m3 copy of the weights (engine.pk_lo8), products weighted 2^-11
@@ -174,6 +192,8 @@ def gemm(a16, w16, *, M, N, K, lda=0, a_mode=A_PLAIN, conv=None, tconv=None, bia
         acc = acc + acc_lo
     if ACC_HOOK is not None:     # numerics experiments (tools/exp/error_budget.py): e.g. the weight side of an MX lo pass
         acc = ACC_HOOK(acc, a16, Wm, dict(M=M, N=N, K=K, lda=lda, a_mode=a_mode, conv=conv, tconv=tconv))
+    if acc_w is not None:
+        acc = acc + acc_w
     v = acc
     if bias is not None:
         v = v + bias.reshape(-1)[:N].float()
@@ -221,6 +241,7 @@ def gemm(a16, w16, *, M, N, K, lda=0, a_mode=A_PLAIN, conv=None, tconv=None, bia
         dst.copy_(r16(v[:, ns:], 'gemm.out16t').view(G, t_rows, N - ns).permute(0, 2, 1))
 
 
+# ---- attention (pnc_attn_views_f16, pnc_softmax_rows_f16, pnc_attn_temporal_f16) ------------------------------------------------
 PERM16 = (0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15)
 
 
@@ -275,6 +296,110 @@ def attn_views(q, ldq, k, ldk, vt, ldvt, vt_gstride, o, ldo, *, groups, heads, H
         O[:, :, v * Wv:(v + 1) * Wv] = r16(ov, 'attn_views')
 
 
+# ---- split-operand attention (pnc_attn_views_split_f16, pnc_attn_temporal_split_f16; CPU tensors only) -------------------------
+# The kernels' arithmetic in fp32 — S = Qh.Kh + 2^-11 (Qh.Kl + Ql.Kh), fp32 softmax, P split into an fp16 pair,
+# O = Ph.Vh + 2^-11 (Ph.Vl + Pl.Vh) — written as hi + fp16 lo planes.  The `_exact` forms: float64 attention of the operand values
+# hi + lo * 2^-11 (no term dropped), returned with the query rows instead of written; tests/test_precise_wide_gpu.py holds the HIP
+# kernels to them on the MI355X.
+def _rows_views(groups, H, W, views):
+    """row index [groups, views, H * W / views] of every query (the resident layout: row = (g * H + y) * W + x)"""
+    Wv = W // views
+    g = torch.arange(groups).view(-1, 1, 1)
+    v = torch.arange(views).view(1, -1, 1)
+    i = torch.arange(H * Wv).view(1, 1, -1)
+    return g * H * W + (i // Wv) * W + v * Wv + i % Wv
+
+
+def _kv_rows(kg, u, kvW, kvWv, kv_rows, kv_valid):
+    j = torch.arange(kv_valid)
+    return kg * kv_rows + (j // kvWv) * kvW + u * kvWv + j % kvWv
+
+
+def _attend(qh, ql, kh, kl, vh, vl, scale, exact):
+    """[..., nq, 64] queries, [..., nk, 64] keys / values (hi, lo) -> [..., nq, 64] output (float64 when exact, else fp32)"""
+    S = 1.0 / LO_SCALE
+    if exact:
+        d = torch.float64
+        q, k, v = (a.to(d) + b.to(d) * S for a, b in ((qh, ql), (kh, kl), (vh, vl)))
+        return torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1) @ v
+    qh, ql, kh, kl, vh, vl = (t.float() for t in (qh, ql, kh, kl, vh, vl))
+    s = qh @ kh.transpose(-1, -2) + (qh @ kl.transpose(-1, -2) + ql @ kh.transpose(-1, -2)) * S
+    p = torch.softmax(s * scale, dim=-1)
+    ph = p.half().float()
+    pl = ((p - ph) * LO_SCALE).half().float()
+    return ph @ vh + (ph @ vl + pl @ vh) * S
+
+
+def _write_split(o, o_lo, rows, ldo, Cc, val):
+    """val [..., heads, nq, 64] at the query rows `rows` [..., nq]"""
+    val = val.float()
+    heads = val.shape[-3]
+    flat = val.movedim(-3, -2).reshape(-1, heads * 64)          # [..., nq, heads*64]
+    r = rows.reshape(-1)
+    hi = r16(flat, "attn_split")
+    _mat(o, int(r.max()) + 1, Cc, ldo)[r] = hi
+    _mat(o_lo, int(r.max()) + 1, Cc, ldo)[r] = _lo(flat, hi)
+
+
+def _views_split(exact, q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, *, groups, heads, H, W, views, kvH, kvW, kv_views, kv_rows_per_group,
+                 q_per_kv, kv_valid, segs, scale):
+    """-> ([g, heads, nq, 64] per view, query rows [g, views, nq])"""
+    Cc = heads * 64
+    kvWv = kvW // kv_views
+    n_kvg = (groups + q_per_kv - 1) // q_per_kv
+    qrows = _rows_views(groups, H, W, views)
+    nrows_q, nrows_kv = groups * H * W, n_kvg * kv_rows_per_group
+
+    def heads_of(t, ld, rows, n):
+        return _mat(t, n, Cc, ld)[rows].view(*rows.shape, heads, 64).movedim(-2, -3)     # [..., heads, n, 64]
+    out = []
+    for vw in range(views):
+        qr = qrows[:, vw]
+        qh, ql = heads_of(q, ldq, qr, nrows_q), heads_of(q_lo, ldq, qr, nrows_q)
+        kr = torch.stack([torch.cat([_kv_rows(g // q_per_kv, u, kvW, kvWv, kv_rows_per_group, kv_valid) for u in segs[vw]])
+                          for g in range(groups)])                       # [g, nk]
+        kh, kl = heads_of(k, ldk, kr, nrows_kv), heads_of(k_lo, ldk, kr, nrows_kv)
+        vh, vl = heads_of(v, ldv, kr, nrows_kv), heads_of(v_lo, ldv, kr, nrows_kv)
+        out.append(_attend(qh, ql, kh, kl, vh, vl, scale, exact))
+    return out, qrows
+
+
+def attn_views_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, groups, heads, H, W, views, kvH, kvW, kv_views,
+                     kv_rows_per_group, q_per_kv, kv_valid, segs, scale):
+    out, qrows = _views_split(False, q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, groups=groups, heads=heads, H=H, W=W, views=views,
+                              kvH=kvH, kvW=kvW, kv_views=kv_views, kv_rows_per_group=kv_rows_per_group, q_per_kv=q_per_kv,
+                              kv_valid=kv_valid, segs=segs, scale=scale)
+    for vw in range(views):
+        _write_split(o, o_lo, qrows[:, vw], ldo, heads * 64, out[vw])
+
+
+def attn_views_split_exact(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, **geo):
+    """-> (float64 [g, views, heads, nq, 64], query rows [g, views, nq]); `geo`: the keywords of attn_views_split"""
+    out, qrows = _views_split(True, q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, **geo)
+    return torch.stack(out, 1), qrows
+
+
+def _temporal_split(exact, q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, *, B, T, Npix, heads, scale):
+    """-> ([B, Npix, heads, T, 64], rows [B, Npix, T])"""
+    Cc, M = heads * 64, B * T * Npix
+    rows = (torch.arange(B).view(-1, 1, 1) * T * Npix + torch.arange(Npix).view(1, -1, 1)
+            + torch.arange(T).view(1, 1, -1) * Npix)
+
+    def g(t, ld):
+        return _mat(t, M, Cc, ld)[rows].view(B, Npix, T, heads, 64).movedim(-2, -3)
+    return _attend(g(q, ldq), g(q_lo, ldq), g(k, ldk), g(k_lo, ldk), g(v, ldv), g(v_lo, ldv), scale, exact), rows
+
+
+def attn_temporal_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, B, T, Npix, heads, scale):
+    val, rows = _temporal_split(False, q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, B=B, T=T, Npix=Npix, heads=heads, scale=scale)
+    _write_split(o, o_lo, rows, ldo, heads * 64, val)
+
+
+def attn_temporal_split_exact(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, *, B, T, Npix, heads, scale):
+    """-> (float64 [B, Npix, heads, T, 64], rows [B, Npix, T])"""
+    return _temporal_split(True, q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, B=B, T=T, Npix=Npix, heads=heads, scale=scale)
+
+
 def softmax_rows(s32, lds, M, N, scale, p16, ldp, causal=False, n_valid=0):
     sc = _mat(s32, M, N, lds).float() * scale
     col, row = torch.arange(N, device=sc.device)[None, :], torch.arange(M, device=sc.device)[:, None]
@@ -297,6 +422,7 @@ def attn_temporal(q, ldq, k, ldk, v, ldv, o, ldo, *, B, T, Npix, heads, scale):
     _mat(o, M, Cc, ldo).copy_(r16(ov.permute(0, 3, 1, 2, 4).reshape(M, Cc), 'attn_temporal'))
 
 
+# ---- norms (pnc_groupnorm_*, pnc_layernorm) ------------------------------------------------------------------------------------
 def groupnorm_stats(x32, ldx, F, Npix, Cch, ppc, partial):
     nchunk = (Npix + ppc - 1) // ppc
     X = _mat(x32, F * Npix, Cch, ldx).view(F, Npix, 32, Cch // 32)
@@ -379,36 +505,40 @@ def layernorm(x32, ldx, M, Cch, gamma, beta, eps, y16, ldy, y16_lo=None):
         _mat(y16_lo, M, Cch, ldy).copy_(_lo(y, h, y16_lo))
 
 
-def linear_smallm(a32, lda, w16, bias, out32, ldo, M, N, K, silu_in=False, silu_out=False):
+# ---- small-M linears (pnc_linear_smallm[_split], pnc_linear_smallm_segments[_split]) --------------------------------------------
+# `w_lo`: the fp16 lo plane of split weights; the kernels join w = W + 2^-11 W_lo in fp32, so does `_join`.
+def _smallm(a32, lda, w16, w_lo, bias, M, N, K, silu_in, silu_out):
     A = _mat(a32, M, K, lda)
     if silu_in:
         A = TF.silu(A)
-    y = A @ w16.reshape(-1)[: N * K].view(N, K).float().t()
+    y = A @ _join(w16, w_lo).reshape(-1)[: N * K].view(N, K).t()
     if bias is not None:
         y = y + bias.reshape(-1)[:N]
-    if silu_out:
-        y = TF.silu(y)
-    _mat(out32, M, N, ldo).copy_(y)
+    return TF.silu(y) if silu_out else y
 
 
-def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_start, silu_in=False, silu_out=False):
-    A = _mat(a32, M, K, lda)
-    if silu_in:
-        A = TF.silu(A)
-    y = A @ w16.reshape(-1)[: N * K].view(N, K).float().t()
-    if bias is not None:
-        y = y + bias.reshape(-1)[:N]
-    if silu_out:
-        y = TF.silu(y)
+def linear_smallm(a32, lda, w16, bias, out32, ldo, M, N, K, silu_in=False, silu_out=False, w_lo=None):
+    _mat(out32, M, N, ldo).copy_(_smallm(a32, lda, w16, w_lo, bias, M, N, K, silu_in, silu_out))
+
+
+def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_start, silu_in=False, silu_out=False, w_lo=None):
+    y = _smallm(a32, lda, w16, w_lo, bias, M, N, K, silu_in, silu_out)
     flat = out32.reshape(-1)
     for s0, s1 in zip(seg_start[:-1], seg_start[1:]):
         flat[s0 * Mtot:s1 * Mtot].view(Mtot, s1 - s0)[m0:m0 + M].copy_(y[:, s0:s1])
 
 
+# ---- embeddings and layout -----------------------------------------------------------------------------------------------------
 def timestep_embedding(t_i64, F, dim, freqs, out32):
     args = t_i64.reshape(-1)[:F, None].float() * freqs.reshape(-1)[None, : dim // 2]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     out32.reshape(-1)[: F * dim].view(F, dim)[:, : 2 * (dim // 2)].copy_(emb)
+
+
+def timestep_embedding_f32(t_f32, F, dim, freqs, out32):
+    """float timesteps (a continuous c_noise) as given: the int64 emulation's arithmetic after its `.float()`"""
+    assert t_f32.dtype == torch.float32
+    timestep_embedding(t_f32, F, dim, freqs, out32)
 
 
 def nchw_to_tokens_f16(a32, C1, b32, C2, F, Npix, Cpad, out16, out16_lo=None, a_scale=None, a_frames=0):
@@ -426,17 +556,70 @@ def nchw_to_tokens_f16(a32, C1, b32, C2, F, Npix, Cpad, out16, out16_lo=None, a_
         out16_lo.reshape(-1)[: F * Npix * Cpad].view(F, Npix, Cpad).copy_(_lo(v, h))
 
 
-def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next):
-    """the reference's op sequence (denoiser.py:22-28, guiders.py:25-29, sampling.py:96-133) on channels-last eps"""
+# ---- sampler exits (pnc_cfg_euler_step[_skip], pnc_cfg_sampler_step[_skip]) -----------------------------------------------------
+# The reference's torch ops in the reference's order (denoiser.py:22-28, guiders.py:25-29, sampling.py:85-365) on channels-last eps
+# tokens.  The HIP kernels are held to the same trajectories on the MI355X (tests/test_samplers_gpu.py, tests/test_denoisers_gpu.py).
+def _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip):
+    """(X [T, C, Npix], guided D).  `c_skip` None: the eps path, D_h = E_h * c_out + X; else D_h = E_h * c_out + X * c_skip
+    (denoiser.py:28) with both products and the sum rounded on their own.  Then CFG."""
     E = _mat(eps_tok, (2 if cfg else 1) * T * Npix, Cch, ld).view(-1, T, Npix, Cch).permute(0, 1, 3, 2)   # [halves, T, C, Npix]
     X = x.reshape(T, Cch, Npix)
+    if c_skip is None:
+        D = E * c_out.reshape(T, 1, 1) + X
+    else:
+        D = E * c_out.reshape(T, 1, 1) + X * c_skip.reshape(T, 1, 1)
+    return X, (D[0] + scale * (D[1] - D[0]) if cfg else D[0])
+
+
+def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip=None):
+    X, D = _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip)
     sg = sigma.reshape(T, 1, 1)
-    D = E * c_out.reshape(T, 1, 1) + X
-    Dn = D[0] + scale * (D[1] - D[0]) if cfg else D[0]
-    d = (X - Dn) / sg
+    d = (X - D) / sg
     x_next.reshape(T, Cch, Npix).copy_(X + (sigma_next.reshape(T, 1, 1) - sg) * d)
 
 
+def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux=None, x0=None, aux=None, hist=(),
+                     noise=None, s_noise=1.0, c_skip=None):
+    """`v` = the mode's per-frame [T] vectors in header order, `hist` = previous LMS d planes newest first"""
+    X, D = _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip)
+    v = [t.reshape(T, 1, 1) for t in v]
+    plane = lambda t: t.reshape(T, Cch, Npix)                       # noqa: E731
+    if mode == SAMPLER_HEUN1:
+        d = (X - D) / v[0]
+        y = X + (v[1] - v[0]) * d
+        plane(out_aux).copy_(d)
+    elif mode == SAMPLER_HEUN2:
+        d_new = (X - D) / v[1]
+        d_prime = (plane(aux) + d_new) / 2.0
+        y = torch.where(v[1] > 0.0, plane(x0) + d_prime * (v[1] - v[0]), X)
+    elif mode in (SAMPLER_EULER_A, SAMPLER_DPM2S_1):
+        xe = X + (v[1] - v[0]) * ((X - D) / v[0])
+        if mode == SAMPLER_DPM2S_1:
+            y = v[2] * X - v[3] * D
+            plane(out_aux).copy_(xe)
+        else:
+            y = torch.where(v[3] > 0.0, xe + plane(noise) * s_noise * v[2], xe)
+    elif mode == SAMPLER_DPM2S_2:
+        xs = torch.where(v[2] > 0.0, v[0] * plane(x0) - v[1] * D, plane(aux))
+        y = torch.where(v[4] > 0.0, xs + plane(noise) * s_noise * v[3], xs)
+    elif mode == SAMPLER_DPM2M:
+        y = v[0] * X - v[1] * D
+        if aux is not None:
+            y = torch.where(v[4] > 0.0, v[0] * X - v[1] * (v[2] * D - v[3] * plane(aux)), y)
+        plane(out_aux).copy_(D)
+    elif mode == SAMPLER_LMS:
+        d = (X - D) / v[0]
+        acc = 0 + v[1] * d
+        for k, h in enumerate(hist):
+            acc = acc + v[2 + k] * plane(h)
+        y = X + acc
+        plane(out_aux).copy_(d)
+    else:
+        raise ValueError(f"mode {mode}")
+    plane(out).copy_(y)
+
+
+# ---- elementwise ---------------------------------------------------------------------------------------------------------------
 def tokens_to_nchw_f32(x32, ld, F, Npix, Cch, out32):
     X = _mat(x32, F * Npix, Cch, ld).view(F, Npix, Cch)
     out32.reshape(-1)[: F * Cch * Npix].view(F, Cch, Npix).copy_(X.permute(0, 2, 1))
@@ -471,6 +654,69 @@ def add_f32(x32, a32, n, y32, y16, y16_lo=None):
             y16_lo.reshape(-1)[:n].copy_(_lo(y, h, y16_lo))
     if y32 is not None and (a32 is not None or y32.data_ptr() != x32.data_ptr()):
         y32.reshape(-1)[:n].copy_(y)
+
+
+def range_monitor_collect(out_i32: torch.Tensor):
+    """pnc_range_monitor_collect: adds the clamped-quad count since the previous call to out_i32[0] and resets it"""
+    global _LO_CLAMPED
+    out_i32[0] += _LO_CLAMPED
+    _LO_CLAMPED = 0
+
+
+# ---- operand range profile (pnc_operand_stats_f16), written from the header text with numpy ------------------------------------
+# The GPU tests (tests/test_range_profile_gpu.py) compare the kernel's records with `record()` word for word (integers: exact).
+#   rec[0..31]  elements per fp16 binade, index = (bits >> 10) & 31 of the hi plane
+#   rec[32]     max of (bits & 0x7FFF)
+#   rec[33]     lo elements at the end of their format: e4m3 (byte & 0x7F) >= 0x7E, fp16 non-finite; nothing without a lo plane
+#   rec[34]     NaN elements of hi
+#   rec[35]     elements counted
+# Columns cols .. ld - 1 of a row are padding and never read.
+STATS_WORDS = 36
+
+
+def _plane(t: torch.Tensor, rows: int, cols: int, ld: int, np_dtype) -> np.ndarray:
+    """the [rows, cols] elements of the plane whose element 0 is t's first one (row stride ld), reinterpreted as np_dtype"""
+    flat = torch.as_strided(t, ((rows - 1) * ld + cols,), (1,)) if t.numel() else t.reshape(-1)
+    a = flat.detach().cpu().contiguous().numpy().view(np_dtype)
+    return np.lib.stride_tricks.as_strided(a, (rows, cols), (ld * a.itemsize, a.itemsize))
+
+
+def record(hi: torch.Tensor, lo, rows: int, cols: int, ld: int) -> np.ndarray:
+    """the 36 words one launch ADDS (word 32: the value the launch maxes in), as int64"""
+    if hi.dtype != torch.float16 or rows < 1 or cols < 1 or ld < cols:
+        raise ValueError("PNC_EINVAL")
+    if cols % 8 or ld % 8:
+        raise ValueError("PNC_EALIGN")
+    bits = _plane(hi, rows, cols, ld, np.uint16).astype(np.int64)
+    a = bits & 0x7FFF
+    rec = np.zeros(STATS_WORDS, dtype=np.int64)
+    rec[:32] = np.bincount((a >> 10).reshape(-1), minlength=32)
+    rec[32] = a.max()
+    rec[34] = int((a > 0x7C00).sum())
+    rec[35] = rows * cols
+    if lo is not None:
+        if lo.dtype == torch.uint8:
+            b = _plane(lo, rows, cols, ld, np.uint8).astype(np.int64)
+            rec[33] = int(((b & 0x7F) >= 0x7E).sum())
+        elif lo.dtype == torch.float16:
+            b = _plane(lo, rows, cols, ld, np.uint16).astype(np.int64)
+            rec[33] = int(((b & 0x7C00) == 0x7C00).sum())
+        else:
+            raise ValueError("PNC_EINVAL")
+    return rec
+
+
+def accumulate(rec: torch.Tensor, add: np.ndarray):
+    """what the kernel's atomics do to a record"""
+    r = rec.reshape(-1)
+    new = r[:STATS_WORDS].cpu().numpy() + add
+    new[32] = max(int(r[32]), int(add[32]))
+    r[:STATS_WORDS] = torch.from_numpy(new).to(r.device)
+
+
+def operand_stats(hi, lo, rows, cols, ld, rec):
+    assert rec.dtype == torch.int64 and rec.numel() >= STATS_WORDS and rec.is_contiguous()
+    accumulate(rec, record(hi, lo, rows, cols, ld))
 
 
 def cast_f16(x32, n, y16, y16_lo=None):

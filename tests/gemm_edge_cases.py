@@ -1,6 +1,6 @@
 """Operand builders of the GEMM edge cases (tests/test_gemm_edges_gpu.py on the MI355X, tests/test_gemm_ref64.py on the CPU).
 
-A case is one launch: the keywords shared by hip.gemm, emu.gemm (with tests/emu_weights.py / tests/emu_ckpt.py for split weights) and
+A case is one launch: the keywords shared by hip.gemm, emu.gemm and
 gemm_ref64.gemm.  Every plane — A, A_lo, W, W_lo, bias, rowbias, res1, res2 and every output — is a 16-byte-aligned VIEW inside a
 larger allocation whose every other element is poison: NaN for fp16 / fp32, 0xFF (the e4m3 NaN code) for e4m3 bytes.  MARGIN = 256
 poisoned elements sit in front of the view and behind it, every leading-dimension gap (lda > K, w_ld > K, ldr > N, ldc > N, ldt >

@@ -1,7 +1,7 @@
 """Denoiser parameterisations (v-prediction, EDM, continuous c_noise) on the CPU: the mirrors of panacea_amd.sampling against
 the reference's own Denoiser / DiscreteDenoiser / VScaling / EDMScaling / EDMDiscretization (tests/golden/denoisers*.npz,
 tools/gen_golden_denoisers.py), plain on torch and fused on the emulation of the general-skip exit kernels
-(tests/emu_denoisers.py)."""
+(tests/emu.py)."""
 import ctypes
 import subprocess
 
@@ -10,7 +10,6 @@ import pytest
 import torch
 
 import emu
-import emu_denoisers
 from denoiser_cases import CASES, EDM_SCHEDULES, P, SAMPLERS, SCALINGS, TINY_SAMPLERS, make, sampler_config
 from sampler_cases import FakeTokenNetwork, fake_inputs, fake_network, golden, inject_noise
 from panacea_amd import engine as E, hip, sampling as S
@@ -22,8 +21,7 @@ NEW_SYMBOLS = ("pnc_timestep_embedding_f32", "pnc_cfg_euler_step_skip", "pnc_cfg
 
 
 @pytest.fixture
-def emu_backend(monkeypatch):
-    emu_denoisers.attach(monkeypatch)
+def emu_backend():
     with E.use_backend(emu):
         yield
 

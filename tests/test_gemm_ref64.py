@@ -12,7 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-import emu_ckpt
+import emu
 import gemm_edge_cases as cases
 import gemm_ref64 as ref64
 
@@ -136,7 +136,7 @@ _EMU_WORST = {}
 def test_emulation_stays_inside_the_bound(case, data):
     r = reference(case, data)
     kw, allocs = case.launch(data)
-    emu_ckpt.gemm(**kw)
+    emu.gemm(**kw)
     worst = cases.check_outputs(case, data, r, ref64.bound, kw, allocs)
     print(f"{case.name} [{data}] emu err / bound: " + ", ".join(f"{n} {v:.3g}" for n, v in worst.items()))
     fam = _EMU_WORST.setdefault(case.family, {})

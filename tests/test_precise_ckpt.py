@@ -1,5 +1,5 @@
 """The `precise-ckpt` operand policy (`precise`'s operand classes and e4m3 lo planes + split weights beside the launch,
-pnc_gemm_wsplit_f16) on CPU: the host logic against the emulated C-ABI (tests/emu.py + tests/emu_weights.py + tests/emu_ckpt.py) and
+pnc_gemm_wsplit_f16) on CPU: the host logic against the emulated C-ABI (tests/emu.py) and
 tests/golden/tiny_w32.npz — the reference's own fp32 forward of the `tiny` network on weights that are NOT fp16-representable."""
 import dataclasses
 
@@ -7,9 +7,6 @@ import pytest
 import torch
 
 import emu
-import emu_ckpt
-import emu_weights
-import emu_wide
 from helpers import cond, golden, manifest, product_network, step_inputs
 from panacea_amd import engine as E, synth
 
@@ -17,12 +14,7 @@ OTHER_POLICIES = ("fast", "precise", "precise-all", "precise-lite", "precise-f16
 
 
 @pytest.fixture
-def ckpt_emu(monkeypatch):
-    monkeypatch.setattr(emu, "attn_views_split", emu_wide.attn_views_split, raising=False)       # (precise-wide / -full in the same runs)
-    monkeypatch.setattr(emu, "attn_temporal_split", emu_wide.attn_temporal_split, raising=False)
-    monkeypatch.setattr(emu, "gemm", emu_ckpt.gemm)
-    monkeypatch.setattr(emu, "linear_smallm", emu_weights.linear_smallm)
-    monkeypatch.setattr(emu, "linear_smallm_segments", emu_weights.linear_smallm_segments)
+def ckpt_emu():
     with E.use_backend(emu):
         yield
 

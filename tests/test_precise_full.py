@@ -1,5 +1,5 @@
 """The `precise-full` operand policy (precise-wide + split weights, PncGemmParams.W_lo) on CPU: the host logic against the emulated
-C-ABI (tests/emu.py + tests/emu_wide.py + tests/emu_weights.py), the oracle and tests/golden/tiny_w32.npz — the reference's own fp32
+C-ABI (tests/emu.py), the oracle and tests/golden/tiny_w32.npz — the reference's own fp32
 forward of the `tiny` network on weights that are NOT fp16-representable (tools/gen_golden_w32.py)."""
 import dataclasses
 
@@ -8,8 +8,6 @@ import pytest
 import torch
 
 import emu
-import emu_weights
-import emu_wide
 from helpers import cond, golden, manifest, oracle_cfg, product_network, step_inputs
 from panacea_amd import engine as E, synth
 
@@ -17,12 +15,7 @@ OLD_POLICIES = ("fast", "precise", "precise-all", "precise-lite", "precise-f16lo
 
 
 @pytest.fixture
-def full_emu(monkeypatch):
-    monkeypatch.setattr(emu, "attn_views_split", emu_wide.attn_views_split, raising=False)
-    monkeypatch.setattr(emu, "attn_temporal_split", emu_wide.attn_temporal_split, raising=False)
-    monkeypatch.setattr(emu, "gemm", emu_weights.gemm)
-    monkeypatch.setattr(emu, "linear_smallm", emu_weights.linear_smallm)
-    monkeypatch.setattr(emu, "linear_smallm_segments", emu_weights.linear_smallm_segments)
+def full_emu():
     with E.use_backend(emu):
         yield
 

@@ -1,12 +1,11 @@
 """The `precise-wide` operand policy and on_range_exceeded = "escalate" on CPU: the host logic against the emulated C-ABI
-(tests/emu.py + the split attention of tests/emu_wide.py) and the reference oracle."""
+(tests/emu.py) and the reference oracle."""
 import dataclasses
 
 import pytest
 import torch
 
 import emu
-import emu_wide
 from helpers import cond, manifest, oracle_cfg, product_network, step_inputs
 from panacea_amd import engine as E, synth
 
@@ -14,9 +13,7 @@ CLASSES = [f.name for f in dataclasses.fields(E.Precision) if f.name != "lo8"]
 
 
 @pytest.fixture
-def wide_emu(monkeypatch):
-    monkeypatch.setattr(emu, "attn_views_split", emu_wide.attn_views_split, raising=False)
-    monkeypatch.setattr(emu, "attn_temporal_split", emu_wide.attn_temporal_split, raising=False)
+def wide_emu():
     with E.use_backend(emu):
         yield
 

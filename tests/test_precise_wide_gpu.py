@@ -4,7 +4,7 @@ policy / the "escalate" mode at full size on the golden weight sets."""
 import pytest
 import torch
 
-import emu_wide
+import emu
 from panacea_amd import hip
 from panacea_amd.nn.attention import INTER_SEGS, INTRA_SEGS
 
@@ -59,8 +59,8 @@ def _views_case(groups, heads, H, W, views, segs, kv=None, q_per_kv=1, seed=0):
     o, olo = torch.full((M, C), float("nan"), device=DEV, dtype=torch.float16), torch.empty((M, C), device=DEV, dtype=torch.float16)
     hip.attn_views_split(qh, ql, C, kh, kl, C, vh, vl, C, o, olo, C, **geo)
     torch.cuda.synchronize()
-    ref, rows = emu_wide.attn_views_split(*(t.cpu() for t in (qh, ql)), C, *(t.cpu() for t in (kh, kl)), C,
-                                          *(t.cpu() for t in (vh, vl)), C, None, None, C, exact=True, **geo)
+    ref, rows = emu.attn_views_split_exact(*(t.cpu() for t in (qh, ql)), C, *(t.cpu() for t in (kh, kl)), C,
+                                           *(t.cpu() for t in (vh, vl)), C, **geo)
     ref = ref.movedim(-3, -2).reshape(-1, C)                # [g * views * nq, C] in the order of rows
     r = rows.reshape(-1).to(DEV)
     got = o[r].double().cpu() + olo[r].double().cpu() * S
@@ -107,9 +107,8 @@ def test_temporal_split_kernel_vs_float64(B, T, Npix, heads):
     o16 = torch.empty((M, C), device=DEV, dtype=torch.float16)
     hip.attn_temporal(qh, C, kh, C, vh, C, o16, C, B=B, T=T, Npix=Npix, heads=heads, scale=0.125)
     torch.cuda.synchronize()
-    ref, rows = emu_wide.attn_temporal_split(*(t.cpu() for t in (qh, ql)), C, *(t.cpu() for t in (kh, kl)), C,
-                                             *(t.cpu() for t in (vh, vl)), C, None, None, C, B=B, T=T, Npix=Npix, heads=heads,
-                                             scale=0.125, exact=True)
+    ref, rows = emu.attn_temporal_split_exact(*(t.cpu() for t in (qh, ql)), C, *(t.cpu() for t in (kh, kl)), C,
+                                              *(t.cpu() for t in (vh, vl)), C, B=B, T=T, Npix=Npix, heads=heads, scale=0.125)
     ref = ref.movedim(-3, -2).reshape(-1, C)
     r = rows.reshape(-1).to(DEV)
     err = _rel(o[r].double().cpu() + olo[r].double().cpu() * S, ref)
@@ -120,7 +119,7 @@ def test_temporal_split_kernel_vs_float64(B, T, Npix, heads):
 
 
 def test_split_kernels_match_the_emulation():
-    """the fp32 form of tests/emu_wide.py (what the CPU tests run) against the kernel: the same arithmetic up to fp32 ordering"""
+    """the fp32 form of tests/emu.py (what the CPU tests run) against the kernel: the same arithmetic up to fp32 ordering"""
     g = torch.Generator().manual_seed(11)
     heads, C, groups, H, W = 2, 128, 2, 4, 48
     M = groups * H * W
@@ -131,7 +130,7 @@ def test_split_kernels_match_the_emulation():
     for dev in (DEV, torch.device("cpu")):
         o, olo = torch.zeros((M, C), device=dev, dtype=torch.float16), torch.zeros((M, C), device=dev, dtype=torch.float16)
         (qh, ql), (kh, kl), (vh, vl) = [(a.to(dev), b.to(dev)) for a, b in ops]
-        (hip.attn_views_split if dev.type == "cuda" else emu_wide.attn_views_split)(qh, ql, C, kh, kl, C, vh, vl, C, o, olo, C, **geo)
+        (hip.attn_views_split if dev.type == "cuda" else emu.attn_views_split)(qh, ql, C, kh, kl, C, vh, vl, C, o, olo, C, **geo)
         outs.append(o.double().cpu() + olo.double().cpu() * S)
     assert _rel(outs[0], outs[1]) < SPLIT_BOUND
 

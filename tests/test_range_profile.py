@@ -1,9 +1,9 @@
 """The operand range profile (UNetModel3D.profile_ranges -> engine.RangeProfile) on the CPU: the host logic over the emulated C-ABI
-(tests/emu.py + tests/emu_stats.py) on the `tiny` network.  Counts are integers: every comparison is exact.
+(tests/emu.py) on the `tiny` network.  Counts are integers: every comparison is exact.
 
 The independent side of the comparisons is a wrapper around emu.gemm that keeps a copy of the A operand of every launch of one
 evaluation, resolves the launch's site from the WEIGHT pointer (the packed dicts of the network's modules, walked after the run) and
-computes the statistics with torch integer ops — neither engine.RangeProfile's site naming nor tests/emu_stats.py's numpy."""
+computes the statistics with torch integer ops — neither engine.RangeProfile's site naming nor emu.record's numpy."""
 import contextlib
 import ctypes
 import math
@@ -13,28 +13,20 @@ import pytest
 import torch
 
 import emu
-import emu_stats
 from helpers import cond, golden, manifest, product_network, step_inputs
 from panacea_amd import engine as E, hip, synth
 
 
 @contextlib.contextmanager
-def stats_emu(operand_stats=emu_stats.operand_stats, gemm=None):
-    """the emu backend with pnc_operand_stats_f16 attached (and, optionally, another `gemm`)"""
-    had = hasattr(emu, "operand_stats")
-    old = (getattr(emu, "operand_stats", None), emu.gemm)
-    emu.operand_stats = operand_stats
-    if gemm is not None:
-        emu.gemm = gemm
+def stats_emu(operand_stats=None, gemm=None):
+    """the emu backend, optionally with a spy in the place of `operand_stats` and / or `gemm`"""
+    old = (emu.operand_stats, emu.gemm)
+    emu.operand_stats, emu.gemm = operand_stats or old[0], gemm or old[1]
     try:
         with E.use_backend(emu), torch.no_grad():
             yield
     finally:
-        emu.gemm = old[1]
-        if had:
-            emu.operand_stats = old[0]
-        else:
-            del emu.operand_stats
+        emu.operand_stats, emu.gemm = old
 
 
 def _never(*a, **k):
@@ -230,12 +222,10 @@ def test_recommends_precise_on_fp16_weights(precise_run):
     assert rec["policy"] == "precise" and rec["headroom_binades"] >= 1
 
 
-def test_recommends_precise_ckpt_on_unrounded_weights(monkeypatch):
+def test_recommends_precise_ckpt_on_unrounded_weights():
     """the weights behind tests/golden/tiny_w32.npz: the synthetic set of the fixture's `salt` without its fp16 rounding
     (tools/gen_golden_w32.py).  That these ARE the fixture's weights is checked on its eps: the recommended policy, run on them through
     the emulation of its entry points, holds its own 1e-3 contract against the reference's fp32 forward stored there."""
-    import emu_ckpt
-    import emu_weights
     gold = golden("tiny_w32")
     w, _, kw = product_network("tiny")
     m = w.diffusion_model
@@ -247,10 +237,8 @@ def test_recommends_precise_ckpt_on_unrounded_weights(monkeypatch):
     rec = prof.recommend(m)
     print(rec)
     assert rec["policy"] == "precise-ckpt" and rec["headroom_binades"] >= 1
-    monkeypatch.setattr(emu, "linear_smallm", emu_weights.linear_smallm)
-    monkeypatch.setattr(emu, "linear_smallm_segments", emu_weights.linear_smallm_segments)
     m.precision = rec["policy"]
-    with stats_emu(gemm=emu_ckpt.gemm):
+    with stats_emu():
         eps = w(inp["x"], inp["t"], cond(inp))
     err = (eps - torch.from_numpy(gold["eps"])).abs().max().item()
     print("eps max-abs vs tiny_w32 under the recommended policy:", err)
@@ -364,9 +352,11 @@ def test_evaluation_limit_and_hoisted_invariants(precise_run):
     x = torch.cat([inp["x"], inp["concat"]], dim=1)
     calls = []
 
+    real = emu.operand_stats
+
     def counting(*a):
         calls.append(1)
-        return emu_stats.operand_stats(*a)
+        return real(*a)
     with stats_emu(operand_stats=counting), m.profile_ranges(evaluations=1) as prof:
         inv = m.prepare(inp["crossattn"], inp["cond_feat"])
         n_prepare = len(calls)

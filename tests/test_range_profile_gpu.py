@@ -1,5 +1,5 @@
 """pnc_operand_stats_f16 and the operand range profile on the MI355X.  Every figure is an integer count: the kernel's records are
-compared with numpy's (tests/emu_stats.py, written from the header text) word for word, no tolerance.
+compared with numpy's (tests/emu.py, written from the header text) word for word, no tolerance.
 
 Kernel shapes: the smallest at which the kernel can go wrong — one chunk, less than a wave, ragged multiples of the 8-element chunk,
 a leading dimension wider than the row (NaN-filled padding in both planes), and 4099 x 72 = 36 891 chunks: more than one workgroup,
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-import emu_stats
+import emu
 from helpers import cond, manifest, product_network, step_inputs
 from panacea_amd import engine as E, hip, synth
 
@@ -64,7 +64,7 @@ def test_every_fp16_bit_pattern_once():
     g = torch.Generator().manual_seed(0)
     bits = torch.arange(65536, dtype=torch.int32)[torch.randperm(65536, generator=g)]
     hi = torch.from_numpy(bits.numpy().astype(np.uint16).view(np.int16)).view(torch.float16).view(1024, 64)
-    want = emu_stats.record(hi, None, 1024, 64, 64)
+    want = emu.record(hi, None, 1024, 64, 64)
     assert (want[:32] == 2048).all() and want[32] == 0x7FFF and want[34] == 2046 and want[33] == 0 and want[35] == 65536
     got = launch(hi.to(DEV), None, 1024, 64, 64).cpu().numpy()
     assert np.array_equal(got, want), (got, want)
@@ -76,7 +76,7 @@ def test_shapes_and_poisoned_padding(shape, kind):
     rows, cols, ld = shape
     hi = spread_values(rows, cols, seed=rows)
     lo = lo_plane(kind, rows, cols, seed=rows)
-    want = emu_stats.record(hi, lo, rows, cols, cols)
+    want = emu.record(hi, lo, rows, cols, cols)
     assert want[:32].sum() == rows * cols == want[35]
     recs = []
     for poison in (False, True):
@@ -90,7 +90,7 @@ def test_shapes_and_poisoned_padding(shape, kind):
 def test_lo_planes_with_known_counts():
     rows, cols = 37, 320
     hi = spread_values(rows, cols, seed=5)
-    base = emu_stats.record(hi, None, rows, cols, cols)
+    base = emu.record(hi, None, rows, cols, cols)
     assert np.array_equal(launch(hi.to(DEV), None, rows, cols, cols).cpu().numpy(), base) and base[33] == 0
     # e4m3: 0x7E / 0xFE (+-448), 0x7F / 0xFF (the NaN code) count; 0x7D (416) does not
     lo8 = torch.full((rows * cols,), 0x38, dtype=torch.uint8)
@@ -116,7 +116,7 @@ def test_accumulation_into_one_record_of_a_table():
     a = (torch.randn(33, 64, generator=torch.Generator().manual_seed(1)) * 3).to(torch.float16)            # max in binade ~16
     b = (torch.randn(3, 64, generator=torch.Generator().manual_seed(2)) * 3000).to(torch.float16)          # a larger maximum
     lo_b = torch.full((3, 64), 0x7E, dtype=torch.uint8)
-    ra, rb = emu_stats.record(a, None, 33, 64, 64), emu_stats.record(b, lo_b, 3, 64, 64)
+    ra, rb = emu.record(a, None, 33, 64, 64), emu.record(b, lo_b, 3, 64, 64)
     assert rb[32] > ra[32]
     launch(b.to(DEV), lo_b.to(DEV), 3, 64, 64, table[1])
     launch(a.to(DEV), None, 33, 64, 64, table[1])               # the smaller maximum second: word 32 must keep the larger one
@@ -132,7 +132,7 @@ def _ctx_record(inp):
     c = inp["crossattn"].cpu()
     pad = torch.zeros((c.shape[0], E.TEXT_PAD, c.shape[2]), dtype=torch.float16)
     pad[:, :c.shape[1]] = c.to(torch.float16)
-    return emu_stats.record(pad.view(-1, c.shape[2]), None, c.shape[0] * E.TEXT_PAD, c.shape[2], c.shape[2])
+    return emu.record(pad.view(-1, c.shape[2]), None, c.shape[0] * E.TEXT_PAD, c.shape[2], c.shape[2])
 
 
 def _words(S):

@@ -1,5 +1,5 @@
 """Heun / ancestral / DPM++ / LMS sampler mirrors and their exit kernel pnc_cfg_sampler_step (CPU: the emulation of
-tests/emu_samplers.py) against the reference's own sampler classes (tests/golden/samplers*.npz, tools/gen_golden_samplers.py)."""
+tests/emu.py) against the reference's own sampler classes (tests/golden/samplers*.npz, tools/gen_golden_samplers.py)."""
 import ctypes
 import subprocess
 
@@ -8,7 +8,6 @@ import pytest
 import torch
 
 import emu
-import emu_samplers
 from sampler_cases import CASES, FakeTokenNetwork, fake_inputs, fake_network, golden, inject_noise, make
 from panacea_amd import engine as E, hip, sampling as S
 
@@ -18,8 +17,7 @@ TOL = float(GT["tol_rel"])
 
 
 @pytest.fixture
-def emu_backend(monkeypatch):
-    monkeypatch.setattr(emu, "cfg_sampler_step", emu_samplers.cfg_sampler_step, raising=False)
+def emu_backend():
     with E.use_backend(emu):
         yield
 

@@ -11,7 +11,7 @@ EDMDiscretization mirrors and the general-skip exit kernels (needs the reference
                                          the noise drawn
   tests/golden/denoisers_tiny_net.npz  every case for 4 steps of Euler and DPM++ 2M around the reference's tiny Panacea network:
                                        the latent after every step.  Before writing, the classes `panacea_amd.dropin.install()`
-                                       puts in the network's place, on the emulated kernels (tests/emu.py + tests/emu_denoisers.py),
+                                       puts in the network's place, on the emulated kernels (tests/emu.py),
                                        must stay within tol_rel of max|x| at every step; tol_rel is the bound
                                        tests/golden/samplers_tiny_net.npz carries for this network, copied.
 
@@ -86,7 +86,6 @@ def _cpu(cfg):
 
 def tiny_trajectories(ns):
     import emu
-    import emu_denoisers
     from panacea_amd import dropin, engine as E
     kw = configs.get("tiny")
     net, wrapper = ref_import.build_reference_network(ns, kw)
@@ -107,7 +106,6 @@ def tiny_trajectories(ns):
     assert type(mirror).__module__.startswith("panacea_amd"), "the drop-in did not take"
     mirror.load_state_dict(sd, strict=True)
     mwrap = wr.OpenAIWrapperControlLDM3D(mirror)
-    emu.timestep_embedding_f32 = emu_denoisers.timestep_embedding_f32
     tol = np.load(GOLDEN / "samplers_tiny_net.npz")["tol_rel"]          # the bound this network already carries under `precise`
     out = {"x0": x0.numpy(), "steps": np.int32(TINY_STEPS), "cfg_scale": np.float32(CFG_SCALE), "tol_rel": np.float32(tol)}
     for case, s in runs:

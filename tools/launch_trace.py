@@ -1,17 +1,24 @@
-"""Launch trace of the host logic on CPU: which backend wrappers the `tiny` network calls, in what order, with which arguments.
+"""Launch trace of the host logic on CPU: which backend wrappers the `tiny` network and the samplers call, in what order, with which
+arguments.
 
     python tools/launch_trace.py [--dump DIR] [case ...]
 
-The backend is a recording proxy over the torch emulation of the C-ABI (tests/emu.py with the split attention of tests/emu_wide.py and
-the split weights of tests/emu_weights.py attached).  Per call it records the wrapper name and every argument under the name it
-has in panacea_amd/hip.py, defaults filled in (an omitted optional argument and an explicit None are the same launch): scalars and
-keywords as they are, tensors as shape, dtype and storage offset (never addresses: allocation order may change) — so `w_lo` shows
-as None, an fp16 tensor or a (bytes, exponent) pair.  Per case it prints the launch count, a digest of the trace and a digest of the output bytes; two trees
-that print the same table enqueue the same launches on the same bits.  `--dump DIR` writes the full traces for diffing.
+The backend is a recording proxy over the torch emulation of the C-ABI (tests/emu.py, the whole backend in one module).  Per call it
+records the wrapper name and every argument under its parameter name — the emulation's signature, which tests/test_emu_surface.py
+holds equal to panacea_amd/hip.py's — defaults filled in (an omitted optional argument and an explicit None are the same launch):
+scalars and keywords as they are, tensors as shape, dtype and storage offset (never addresses: allocation order may change) — so
+`w_lo` shows as None, an fp16 tensor or a (bytes, exponent) pair.  Per case it prints the launch count, a digest of the trace and a
+digest of the output bytes; two trees that print the same table enqueue the same launches on the same bits.  `--dump DIR` writes the
+full traces for diffing.
 
-Cases: every entry of engine.PRECISIONS on the wrapper network (`precise-wide` / `precise-full` on weights that are not
+Network cases: every entry of engine.PRECISIONS on the wrapper network (`precise-wide` / `precise-full` on weights that are not
 fp16-representable, so that a dropped weight plane changes the bits too); `precise` under the loop-back view shard and both loop-back
 frame shards; SpatialTemporalTransformer.forward and ResBlock3D.forward on their own under `precise` and `precise-full`.
+
+Sampler cases (`sampler/...`): the fused device loop of every sampler, 3 steps at CFG scale 2 around the closed-form network of
+tests/sampler_cases.py, which here also embeds the c_noise it is handed through the backend; LinearMultistepSampler at order 3 (its
+history is read), noise from a seeded generator, EulerEDMSampler and DPMPP2MSampler once more under VScaling with a float c_noise
+(`c_skip`, pnc_timestep_embedding_f32), and EulerEDMSampler without a guider.  Their output digest is the final latent.
 """
 import hashlib
 import inspect
@@ -26,16 +33,12 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 import emu  # noqa: E402
-import emu_ckpt  # noqa: E402
-import emu_weights  # noqa: E402
-import emu_wide  # noqa: E402
 from helpers import cond, manifest, product_network, step_inputs  # noqa: E402
-from panacea_amd import engine as E, hip, parallel, synth  # noqa: E402
+from sampler_cases import FakeTokenNetwork, fake_inputs  # noqa: E402
+from panacea_amd import engine as E, parallel, sampling as S, synth  # noqa: E402
 from panacea_amd.nn.attention import SpatialTemporalTransformer  # noqa: E402
 from panacea_amd.nn.openaimodel import ResBlock3D  # noqa: E402
-
-OVERLAY = dict(attn_views_split=emu_wide.attn_views_split, attn_temporal_split=emu_wide.attn_temporal_split, gemm=emu_ckpt.gemm,
-               linear_smallm=emu_weights.linear_smallm, linear_smallm_segments=emu_weights.linear_smallm_segments)
+from panacea_amd.nn.util import timestep_embedding  # noqa: E402
 
 
 def describe(v):
@@ -49,18 +52,18 @@ def describe(v):
 
 
 class Recorder(types.ModuleType):
-    """tests/emu.py + OVERLAY as a backend for engine.use_backend; every call of a wrapper appends one line to `lines`"""
+    """tests/emu.py as a backend for engine.use_backend; every call of a wrapper appends one line to `lines`"""
 
     def __init__(self):
         super().__init__("launch_trace_backend")
         self.lines = []
 
     def __getattr__(self, name):
-        fn = OVERLAY.get(name) or getattr(emu, name)
+        fn = getattr(emu, name)
         if not callable(fn) or isinstance(fn, type):
             return fn
 
-        sig = inspect.signature(getattr(hip, name))      # the product wrapper's signature: an omitted optional argument = its default
+        sig = inspect.signature(fn)      # = the product wrapper's signature: an omitted optional argument = its default
 
         def call(*a, **k):
             bound = sig.bind(*a, **k)
@@ -108,6 +111,43 @@ def cases():
                 ctx = inp["crossattn"]
                 return mod(x, ctx[:, None].expand(B, T, *ctx.shape[1:]).reshape(B * T, *ctx.shape[1:]))
             yield f"{cls.__name__}/{p}", alone
+    yield from sampler_cases()
+
+
+class EmbeddingNetwork(FakeTokenNetwork):
+    """the closed-form stand-in network, with the product's embedding of the c_noise it is handed (a backend launch: int64 table
+    indices or floats) folded into its eps tokens"""
+
+    def denoise_tokens(self, x, c_in, c_noise, ctx, concat, cond_feat, invariants=None):
+        eps = super().denoise_tokens(x, c_in, c_noise, ctx, concat, cond_feat, invariants)
+        eps.f32 += 1e-3 * timestep_embedding(c_noise, 64).mean(dim=1).repeat_interleave(eps.N)[:, None]
+        return eps
+
+
+def sampler_cases():
+    v_float = lambda: S.DiscreteDenoiser(quantize_c_noise=False, scaling=S.VScaling())      # noqa: E731
+    runs = [(cls, S.DiscreteDenoiser, 2.0, cls) for cls in ("EulerEDMSampler", "HeunEDMSampler", "EulerAncestralSampler",
+                                                             "DPMPP2SAncestralSampler", "DPMPP2MSampler", "LinearMultistepSampler")]
+    runs += [(cls, v_float, 2.0, cls + "/v-float") for cls in ("EulerEDMSampler", "DPMPP2MSampler")]
+    runs.append(("EulerEDMSampler", S.DiscreteDenoiser, None, "EulerEDMSampler/no-guider"))
+    for cls, denoiser, scale, tag in runs:
+        def fused(cls=cls, denoiser=denoiser, scale=scale):
+            kw = {"order": 3} if cls == "LinearMultistepSampler" else {}
+            smp = getattr(S, cls)(3, guider=None if scale is None else S.VanillaCFG(scale), device="cpu", **kw)
+            g = torch.Generator().manual_seed(11)
+            smp.noise_sampler = lambda x: torch.randn(x.shape, generator=g)
+            bd = S.BoundDenoiser(denoiser(), EmbeddingNetwork())
+            x0, c, uc = fake_inputs()
+            assert smp._fusable_network(bd, c)
+            sig, sig_f = smp.sigmas(), smp.host_sigmas()
+            x = x0 * torch.sqrt(1.0 + sig[0] ** 2.0)
+            state = smp._state(x)
+            for form, sv, draw in smp._steps(sig, sig_f, x.new_ones([x.shape[0]])):       # the device loop, as on the GPU
+                if draw:
+                    sv["noise"] = smp.noise_sampler(x)
+                x = smp._device_step(form, sv, x, bd, c, uc, state)
+            return x
+        yield "sampler/" + tag, fused
 
 
 def main(argv):
