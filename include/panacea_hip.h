@@ -456,7 +456,9 @@ int pnc_nchw_to_tokens_f16(const float* a, int C1, const float* a_scale, int a_f
  *                                                    c_skip = 1 (denoiser.py:22-28, denoiser_scaling.py:16-22)
  *   D      = D_u + scale * (D_c - D_u)               VanillaCFG (guiders.py:25-29); cfg = 0: D = D_c, one half only
  *   x_next = x + (sigma_next - sigma) * ((x - D) / sigma)      EulerEDMSampler.sampler_step (sampling.py:96-133)
- * eps_tok [(cfg ? 2 : 1) * T * Npix][ld] fp32, uncond frames first; x, x_next NCHW [T][C][Npix]; c_out, sigma, sigma_next [T]. */
+ * eps_tok [(cfg ? 2 : 1) * T * Npix][ld] fp32, uncond frames first; x, x_next NCHW [T][C][Npix]; c_out, sigma, sigma_next [T].
+ * This is the HEUN1 update of pnc_cfg_sampler_step below with v = {sigma, sigma_next}, out = x_next and no out_aux, and it runs as
+ * exactly that: the same kernel, so the same bits as HEUN1's `out`. */
 int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
                        const float* x, const float* c_out, const float* sigma, const float* sigma_next, float* x_next,
                        void* stream);
@@ -510,7 +512,9 @@ int pnc_cfg_sampler_step(const PncSamplerStepParams* p, void* stream);
  * EDMScaling (denoiser_scaling.py:4-13, 25-31) under Denoiser / DiscreteDenoiser (denoiser.py:22-28):
  *   D_h = eps_h * c_out + x * c_skip                 two products, each rounded on its own, then the sum (denoiser.py:28)
  * c_skip [T] fp32 on the device; everything after D_h (CFG combine, the sampler's update, every operand and mode) is that of
- * pnc_cfg_euler_step / pnc_cfg_sampler_step — one device function, so c_skip = 1 gives their bits.  A NULL c_skip is
+ * pnc_cfg_euler_step / pnc_cfg_sampler_step.  All four entries run ONE kernel, compiled with and without the skip term, whose D
+ * comes from one device function: c_skip = 1 gives the bits of the entries above (x * 1 is exact), and pnc_cfg_euler_step_skip is
+ * HEUN1 of pnc_cfg_sampler_step_skip as pnc_cfg_euler_step is of pnc_cfg_sampler_step.  A NULL c_skip is
  * PNC_EINVAL (it is never read as 1: the eps path is the two entries above); PNC_EABI as pnc_cfg_sampler_step. */
 int pnc_cfg_euler_step_skip(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
                             const float* x, const float* c_skip, const float* c_out, const float* sigma,

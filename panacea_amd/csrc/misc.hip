@@ -236,47 +236,33 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ x, c
 
 // Exit of a sampler step: eps tokens of the CFG batch -> next latent, one pass.  The arithmetic
 // follows the reference's sequence of fp32 roundings (no contraction into FMAs), so a trajectory matches the reference's
-// sampler to the last few ulps.  SKIP: the general-skip form (x * c_skip[t] rounded on its own, then the sum: denoiser.py:28) of
-// VScaling / EDMScaling; SKIP = false is the eps path (c_skip = 1, x enters the sum as it is) and reads no c_skip.
+// sampler to the last few ulps.  Every product and sum is rounded on its own, like the reference's separate elementwise kernels:
+// the operators are written out under `fp contract(off)` (HIP's __fmul_rn / __fadd_rn are plain inline operators compiled under
+// the default contract(fast), so they DO fuse into FMAs).  The pragma is lexical — each function states its own; the kernel's does
+// not reach into a function inlined into it.
+//
+// The guided denoised D of one element, the ONE copy every exit entry point runs.  SKIP: the general-skip form (x * c_skip[t]
+// rounded on its own, then the sum: denoiser.py:28) of VScaling / EDMScaling; SKIP = false is the eps path (c_skip = 1, x enters
+// the sum as it is) and never looks at cs.  eu, ec: the element's eps of the uncond / cond half (guiders.py:36; eu is unused
+// without cfg).
 template <bool SKIP>
-__global__ __launch_bounds__(256) void cfg_euler_step_kernel(const float* __restrict__ eps, int ld, int T, int Npix, int C,
-                                                             int cfg, float scale, const float* __restrict__ x,
-                                                             const float* __restrict__ c_out,
-                                                             const float* __restrict__ sigma,
-                                                             const float* __restrict__ sigma_next,
-                                                             float* __restrict__ xn, const float* __restrict__ c_skip) {
-    // every product and sum below is rounded on its own, like the reference's separate elementwise kernels.  The operators
-    // are written out under `fp contract(off)` (HIP's __fmul_rn / __fadd_rn are plain inline operators compiled under the
-    // default contract(fast), so they DO fuse into FMAs)
+__device__ __forceinline__ float guided_denoised(float xv, float eu, float ec, float co, float cs, int cfg, float scale) {
 #pragma clang fp contract(off)
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)T * Npix) return;
-    const int64_t t = i / Npix, pix = i - t * Npix;
-    const float sg = sigma[t], dt = sigma_next[t] - sg, co = c_out[t];
-    const float cs = SKIP ? c_skip[t] : 1.0f;
-    const float* eu = eps + i * ld;                               // uncond half first (guiders.py:36)
-    const float* ec = eps + ((int64_t)(cfg ? T : 0) * Npix + i) * ld;
-    for (int c = 0; c < C; ++c) {
-        const int64_t o = (t * C + c) * Npix + pix;
-        const float xv = x[o];
-        const float xs = SKIP ? xv * cs : xv;                            // x * c_skip   (eps path: c_skip = 1)
-        const float pc = ec[c] * co;
-        const float dc = pc + xs;                                        // eps * c_out + x * c_skip
-        float d = dc;
-        if (cfg) {
-            const float pu = eu[c] * co;
-            const float du = pu + xs;
-            const float g = scale * (dc - du);
-            d = du + g;                                                  // x_u + scale * (x_c - x_u)
-        }
-        const float dir = (xv - d) / sg;                                 // (x - denoised) / sigma
-        const float stp = dt * dir;
-        xn[o] = xv + stp;                                                // x + (sigma_next - sigma) * d
+    const float xs = SKIP ? xv * cs : xv;                                // x * c_skip   (eps path: c_skip = 1)
+    const float pc = ec * co;
+    float D = pc + xs;                                                   // eps * c_out + x * c_skip
+    if (cfg) {
+        const float pu = eu * co;
+        const float du = pu + xs;
+        const float g = scale * (D - du);
+        D = du + g;                                                      // x_u + scale * (x_c - x_u)
     }
+    return D;
 }
 
-// Exit of a step of the other samplers (include/panacea_hip.h: pnc_cfg_sampler_step).  Same denoised as above, then the
-// mode's update, every operation rounded on its own in the reference's order.  SKIP as above.
+// The exit kernel of every sampler (include/panacea_hip.h: pnc_cfg_sampler_step): the denoised above, then the mode's update,
+// every operation rounded on its own in the reference's order.  SKIP as above.  The Euler exit (pnc_cfg_euler_step) is HEUN1
+// without out_aux: x + (sigma_next - sigma) * ((x - D) / sigma) is what HEUN1 writes to `out`.
 template <bool SKIP>
 __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerStepParams p, const float* __restrict__ c_skip) {
 #pragma clang fp contract(off)
@@ -292,15 +278,7 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
     for (int c = 0; c < p.C; ++c) {
         const int64_t o = (t * p.C + c) * p.Npix + pix;
         const float xv = p.x[o];
-        const float xs = SKIP ? xv * cs : xv;
-        const float pc = ec[c] * co;
-        float D = pc + xs;
-        if (p.cfg) {
-            const float pu = eu[c] * co;
-            const float du = pu + xs;
-            const float g = p.scale * (D - du);
-            D = du + g;
-        }
+        const float D = guided_denoised<SKIP>(xv, eu[c], ec[c], co, cs, p.cfg, p.scale);
         float y;
         switch (p.mode) {
         case PNC_SAMPLER_HEUN1: {
@@ -308,7 +286,7 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
             const float dt = v1 - v0;
             const float stp = dt * d;
             y = xv + stp;
-            p.out_aux[o] = d;
+            if (p.out_aux) p.out_aux[o] = d;                             // (launch-uniform) NULL: the Euler exit keeps no d
             break;
         }
         case PNC_SAMPLER_HEUN2: {
@@ -380,46 +358,27 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
     }
 }
 
-}  // namespace
+inline hipStream_t hip_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
 
-static int cfg_euler_step_launch(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale, const float* x,
-                                 const float* c_out, const float* sigma, const float* sigma_next, float* x_next,
-                                 const float* c_skip, bool skip, void* stream) {
-    if (!eps_tok || !x || !c_out || !sigma || !sigma_next || !x_next || T < 1 || Npix < 1 || C < 1 || ld < C) return PNC_EINVAL;
-    if (skip && !c_skip) return PNC_EINVAL;                          // never "c_skip = 1": the eps path is pnc_cfg_euler_step
-    const int64_t n = (int64_t)T * Npix;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (skip)
-        hipLaunchKernelGGL(cfg_euler_step_kernel<true>, grid, block, 0, st, eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma,
-                           sigma_next, x_next, c_skip);
-    else
-        hipLaunchKernelGGL(cfg_euler_step_kernel<false>, grid, block, 0, st, eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma,
-                           sigma_next, x_next, static_cast<const float*>(nullptr));
+// every launch of this file: 256-thread workgroups over n threads' worth of work (a thread per item: n items; a wave per item:
+// 64 n; a workgroup per item: 256 n) on the caller's stream
+template <typename... Sig, typename... Args>
+int launch_1d(void (*kernel)(Sig...), int64_t n, void* stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hip_stream(stream), args...);
     return pnc_launch_status();
 }
 
-extern "C" int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
-                                  const float* x, const float* c_out, const float* sigma, const float* sigma_next,
-                                  float* x_next, void* stream) {
-    return cfg_euler_step_launch(eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next, nullptr, false, stream);
-}
-
-extern "C" int pnc_cfg_euler_step_skip(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
-                                       const float* x, const float* c_skip, const float* c_out, const float* sigma,
-                                       const float* sigma_next, float* x_next, void* stream) {
-    return cfg_euler_step_launch(eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip, true, stream);
-}
-
-static int cfg_sampler_step_launch(const PncSamplerStepParams* pp, const float* c_skip, bool skip, void* stream) {
+// The one launch of the four exit entry points.  `euler_exit`: HEUN1 may come without out_aux — how the two Euler entries reach
+// the kernel, not a mode of the public struct entries.
+int cfg_sampler_step_launch(const PncSamplerStepParams* pp, const float* c_skip, bool skip, bool euler_exit, void* stream) {
     if (!pp || pp->struct_bytes != (int32_t)sizeof(PncSamplerStepParams)) return PNC_EABI;
     const PncSamplerStepParams& p = *pp;
     if (!p.eps_tok || !p.x || !p.c_out || !p.out || p.T < 1 || p.Npix < 1 || p.C < 1 || p.ld < p.C) return PNC_EINVAL;
-    if (skip && !c_skip) return PNC_EINVAL;                          // never "c_skip = 1": the eps path is pnc_cfg_sampler_step
+    if (skip && !c_skip) return PNC_EINVAL;                          // never "c_skip = 1": the eps path is the entry without _skip
     int nv = 0;                                                      // per-frame vectors the mode reads
     bool ok = true;
     switch (p.mode) {
-    case PNC_SAMPLER_HEUN1: nv = 2; ok = p.out_aux; break;
+    case PNC_SAMPLER_HEUN1: nv = 2; ok = p.out_aux || euler_exit; break;
     case PNC_SAMPLER_HEUN2: nv = 2; ok = p.x0 && p.aux; break;
     case PNC_SAMPLER_EULER_A: nv = 4; ok = p.noise; break;
     case PNC_SAMPLER_DPM2S_1: nv = 4; ok = p.out_aux; break;
@@ -434,22 +393,42 @@ static int cfg_sampler_step_launch(const PncSamplerStepParams* pp, const float* 
     }
     for (int k = 0; ok && k < nv; ++k) ok = p.v[k] != nullptr;
     if (!ok) return PNC_EINVAL;
-    const int64_t n = (int64_t)p.T * p.Npix;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (skip)
-        hipLaunchKernelGGL(cfg_sampler_step_kernel<true>, grid, block, 0, st, p, c_skip);
-    else
-        hipLaunchKernelGGL(cfg_sampler_step_kernel<false>, grid, block, 0, st, p, static_cast<const float*>(nullptr));
-    return pnc_launch_status();
+    return launch_1d(skip ? cfg_sampler_step_kernel<true> : cfg_sampler_step_kernel<false>, (int64_t)p.T * p.Npix, stream, p,
+                     c_skip);
+}
+
+// the Euler exit: HEUN1 with v = {sigma, sigma_next} into x_next, no d kept
+int cfg_euler_step_launch(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale, const float* x,
+                          const float* c_out, const float* sigma, const float* sigma_next, float* x_next, const float* c_skip,
+                          bool skip, void* stream) {
+    PncSamplerStepParams p = {};
+    p.struct_bytes = (int32_t)sizeof(PncSamplerStepParams);
+    p.mode = PNC_SAMPLER_HEUN1;
+    p.eps_tok = eps_tok, p.ld = ld, p.T = T, p.Npix = Npix, p.C = C, p.cfg = cfg, p.scale = scale;
+    p.x = x, p.c_out = c_out, p.v[0] = sigma, p.v[1] = sigma_next, p.out = x_next;
+    return cfg_sampler_step_launch(&p, c_skip, skip, true, stream);
+}
+
+}  // namespace
+
+extern "C" int pnc_cfg_euler_step(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
+                                  const float* x, const float* c_out, const float* sigma, const float* sigma_next,
+                                  float* x_next, void* stream) {
+    return cfg_euler_step_launch(eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next, nullptr, false, stream);
+}
+
+extern "C" int pnc_cfg_euler_step_skip(const float* eps_tok, int ld, int T, int Npix, int C, int cfg, float scale,
+                                       const float* x, const float* c_skip, const float* c_out, const float* sigma,
+                                       const float* sigma_next, float* x_next, void* stream) {
+    return cfg_euler_step_launch(eps_tok, ld, T, Npix, C, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip, true, stream);
 }
 
 extern "C" int pnc_cfg_sampler_step(const PncSamplerStepParams* pp, void* stream) {
-    return cfg_sampler_step_launch(pp, nullptr, false, stream);
+    return cfg_sampler_step_launch(pp, nullptr, false, false, stream);
 }
 
 extern "C" int pnc_cfg_sampler_step_skip(const PncSamplerStepParams* pp, const float* c_skip, void* stream) {
-    return cfg_sampler_step_launch(pp, c_skip, true, stream);
+    return cfg_sampler_step_launch(pp, c_skip, true, false, stream);
 }
 
 extern "C" const char* pnc_version(void) { return "panacea_hip 0.4.0 gfx950"; }
@@ -477,10 +456,8 @@ extern "C" int pnc_linear_smallm_split(const float* a, int lda, const void* W, c
     if (!a || !W || !out || M < 1 || M > SM_MAXM || N < 1 || K < 8) return PNC_EINVAL;
     if (K % 8 || lda % 4) return PNC_EINVAL;
     if (((uintptr_t)a | (uintptr_t)W | (uintptr_t)W_lo) & 15) return PNC_EALIGN;
-    hipLaunchKernelGGL(linear_smallm_kernel, dim3((N + 3) / 4), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), a, lda, reinterpret_cast<const half_t*>(W),
-                       reinterpret_cast<const half_t*>(W_lo), bias, out, ldo, M, N, K, silu_in, silu_out);
-    return pnc_launch_status();
+    return launch_1d(linear_smallm_kernel, (int64_t)N * 64, stream, a, lda, f16p(W), f16p(W_lo), bias, out, ldo, M, N, K, silu_in,
+                     silu_out);                                  // a wave per column
 }
 
 extern "C" int pnc_linear_smallm(const float* a, int lda, const void* W, const float* bias,
@@ -508,29 +485,24 @@ extern "C" int pnc_linear_smallm_segments_split(const float* a, int lda, const v
         if (seg_start[i] % SEG_NC || (i > 0 && seg_start[i] <= seg_start[i - 1])) return PNC_EINVAL;
         segs.start[i] = seg_start[i];
     }
-    const int waves = N / SEG_NC;
-    hipLaunchKernelGGL(linear_smallm_seg_kernel, dim3((waves + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, lda,
-                       reinterpret_cast<const half_t*>(W), reinterpret_cast<const half_t*>(W_lo), bias, out, M, m0, Mtot, N, K, silu_in,
-                       silu_out, segs);
-    return pnc_launch_status();
+    return launch_1d(linear_smallm_seg_kernel, (int64_t)(N / SEG_NC) * 64, stream, a, lda, f16p(W), f16p(W_lo), bias, out, M, m0, Mtot,
+                     N, K, silu_in, silu_out, segs);             // a wave per SEG_NC columns
+}
+
+template <typename TS>
+static int timestep_embedding(const TS* t, int F, int dim, const float* freqs, float* out, void* stream) {
+    if (!t || !out || !freqs || F < 1 || dim < 2) return PNC_EINVAL;
+    return launch_1d(timestep_embedding_kernel<TS>, F * (dim / 2), stream, t, F, dim, freqs, out);
 }
 
 extern "C" int pnc_timestep_embedding(const int64_t* t, int F, int dim, const float* freqs,
                                       float* out, void* stream) {
-    if (!t || !out || !freqs || F < 1 || dim < 2) return PNC_EINVAL;
-    const int n = F * (dim / 2);
-    hipLaunchKernelGGL(timestep_embedding_kernel<int64_t>, dim3((n + 255) / 256), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), t, F, dim, freqs, out);
-    return pnc_launch_status();
+    return timestep_embedding(t, F, dim, freqs, out, stream);
 }
 
 extern "C" int pnc_timestep_embedding_f32(const float* t, int F, int dim, const float* freqs,
                                           float* out, void* stream) {
-    if (!t || !out || !freqs || F < 1 || dim < 2) return PNC_EINVAL;
-    const int n = F * (dim / 2);
-    hipLaunchKernelGGL(timestep_embedding_kernel<float>, dim3((n + 255) / 256), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), t, F, dim, freqs, out);
-    return pnc_launch_status();
+    return timestep_embedding(t, F, dim, freqs, out, stream);
 }
 
 extern "C" int pnc_nchw_to_tokens_f16(const float* a, int C1, const float* a_scale, int a_frames, const float* b, int C2,
@@ -539,20 +511,14 @@ extern "C" int pnc_nchw_to_tokens_f16(const float* a, int C1, const float* a_sca
     if (a_frames < 1 || a_frames > F) return PNC_EINVAL;
     if (Cpad % 8 || Cpad < C1 + C2) return PNC_EINVAL;
     if (((uintptr_t)out16 | (uintptr_t)out16_lo) & 15) return PNC_EALIGN;
-    const int64_t n = (int64_t)F * Npix;
-    hipLaunchKernelGGL(nchw_to_tokens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), a, C1, a_scale, a_frames, b, C2, F, Npix, Cpad,
-                       reinterpret_cast<half_t*>(out16), reinterpret_cast<half_t*>(out16_lo));
-    return pnc_launch_status();
+    return launch_1d(nchw_to_tokens_kernel, (int64_t)F * Npix, stream, a, C1, a_scale, a_frames, b, C2, F, Npix, Cpad, f16p(out16),
+                     f16p(out16_lo));
 }
 
 extern "C" int pnc_tokens_to_nchw_f32(const float* x, int ld, int F, int Npix, int C,
                                       float* out, void* stream) {
     if (!x || !out || F < 1 || Npix < 1 || C < 1 || ld < C) return PNC_EINVAL;
-    const int64_t n = (int64_t)F * Npix;
-    hipLaunchKernelGGL(tokens_to_nchw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), x, ld, F, Npix, C, out);
-    return pnc_launch_status();
+    return launch_1d(tokens_to_nchw_kernel, (int64_t)F * Npix, stream, x, ld, F, Npix, C, out);
 }
 
 extern "C" int pnc_concat_add(const float* a, int C1, const float* s, const float* c, int C2,
@@ -560,22 +526,14 @@ extern "C" int pnc_concat_add(const float* a, int C1, const float* s, const floa
     if (!a || !s || M < 1 || C1 % 4 || C2 % 4 || C1 < 4 || C2 < 4) return PNC_EINVAL;
     if (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3) return PNC_EINVAL;
     if ((!out32 && !out16) || (out16_lo && !out16)) return PNC_EINVAL;
-    const int64_t n = M * ((C1 + C2) / 4);
-    hipLaunchKernelGGL(concat_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), a, C1, s, c, C2, M, out32,
-                       reinterpret_cast<half_t*>(out16), out16_lo, lo_fmt);
-    return pnc_launch_status();
+    return launch_1d(concat_add_kernel, M * ((C1 + C2) / 4), stream, a, C1, s, c, C2, M, out32, f16p(out16), out16_lo, lo_fmt);
 }
 
 extern "C" int pnc_add_f32(const float* x, const float* a, int64_t n, float* y32, void* y16, void* y16_lo, int lo_fmt,
                            void* stream) {
     if (!x || n < 4 || n % 4 || (!y32 && !y16) || (y16_lo && !y16)) return PNC_EINVAL;
     if (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3) return PNC_EINVAL;
-    const int64_t n4 = n / 4;
-    hipLaunchKernelGGL(add_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), x, a, n4, y32, reinterpret_cast<half_t*>(y16),
-                       y16_lo, lo_fmt);
-    return pnc_launch_status();
+    return launch_1d(add_kernel, n / 4, stream, x, a, n / 4, y32, f16p(y16), y16_lo, lo_fmt);
 }
 
 // row softmax: one 256-thread block per row, the row lives in registers (<= 16 x float4 per thread), one HBM read
@@ -639,38 +597,26 @@ extern "C" int pnc_softmax_rows_f16(const float* s, int64_t lds, int M, int N, f
     if (n_valid <= 0) n_valid = N;
     if ((lds & 3) || (ldp & 3) || lds < N || ldp < N) return PNC_EINVAL;
     if (((uintptr_t)s & 15) || ((uintptr_t)p16 & 7)) return PNC_EALIGN;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)M), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), s, lds, N,
-                       scale, causal, n_valid, reinterpret_cast<half_t*>(p16), ldp);
-    return pnc_launch_status();
+    return launch_1d(softmax_rows_kernel, (int64_t)M * 256, stream, s, lds, N, scale, causal, n_valid, f16p(p16), ldp);   // a workgroup per row
 }
 
 extern "C" int pnc_cast_f16(const float* x, int64_t n, void* y16, void* y16_lo, int lo_fmt, void* stream) {
     return pnc_add_f32(x, nullptr, n, nullptr, y16, y16_lo, lo_fmt, stream);
 }
 
+// The translation units that pack e4m3 lo planes, each with a PNC_DEFINE_TU_COLLECT(name) of its own (common.h): the one list
+// their accessors are declared and called from
+#define PNC_TU_COLLECTS(X)                                                                                                       \
+    X(gemm) X(gemm_plain) X(gemm_conv3x3) X(gemm_conv1d) X(gemm_stencil_tile) X(gemm_plain_ws) X(gemm_conv3x3_ws) X(gemm_conv1d_ws) \
+    X(norm) X(misc)
+#define PNC_TU_DECLARE(name) void pnc_tu_collect_##name(unsigned int*, hipStream_t);
+#define PNC_TU_CALL(name) pnc_tu_collect_##name(out, st);
+PNC_TU_COLLECTS(PNC_TU_DECLARE)
 PNC_DEFINE_TU_COLLECT(misc)
-void pnc_tu_collect_gemm(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_plain(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_conv3x3(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_conv1d(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_stencil_tile(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_plain_ws(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_conv3x3_ws(unsigned int*, hipStream_t);
-void pnc_tu_collect_gemm_conv1d_ws(unsigned int*, hipStream_t);
-void pnc_tu_collect_norm(unsigned int*, hipStream_t);
 
 extern "C" int pnc_range_monitor_collect(unsigned int* out, void* stream) {
     if (!out) return PNC_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    pnc_tu_collect_gemm(out, st);
-    pnc_tu_collect_gemm_plain(out, st);
-    pnc_tu_collect_gemm_conv3x3(out, st);
-    pnc_tu_collect_gemm_conv1d(out, st);
-    pnc_tu_collect_gemm_stencil_tile(out, st);
-    pnc_tu_collect_gemm_plain_ws(out, st);
-    pnc_tu_collect_gemm_conv3x3_ws(out, st);
-    pnc_tu_collect_gemm_conv1d_ws(out, st);
-    pnc_tu_collect_norm(out, st);
-    pnc_tu_collect_misc(out, st);
+    hipStream_t st = hip_stream(stream);
+    PNC_TU_COLLECTS(PNC_TU_CALL)
     return pnc_launch_status();
 }

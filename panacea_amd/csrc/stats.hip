@@ -126,13 +126,8 @@ extern "C" int pnc_operand_stats_f16(const void* hi, const void* lo, int lo_fmt,
     const int64_t S = (int64_t)blocks * ST_THREADS;
     const int64_t sr = S / cpr;
     const int sc = (int)(S - sr * cpr);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const half_t* h = reinterpret_cast<const half_t*>(hi);
-    if (!lo)
-        hipLaunchKernelGGL(operand_stats_kernel<0>, dim3(blocks), dim3(ST_THREADS), 0, st, h, lo, rows, cpr, ld, sr, sc, rec);
-    else if (lo_fmt == PNC_LO_F16)
-        hipLaunchKernelGGL(operand_stats_kernel<1>, dim3(blocks), dim3(ST_THREADS), 0, st, h, lo, rows, cpr, ld, sr, sc, rec);
-    else
-        hipLaunchKernelGGL(operand_stats_kernel<2>, dim3(blocks), dim3(ST_THREADS), 0, st, h, lo, rows, cpr, ld, sr, sc, rec);
+    const auto kernel = !lo ? operand_stats_kernel<0> : lo_fmt == PNC_LO_F16 ? operand_stats_kernel<1> : operand_stats_kernel<2>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(ST_THREADS), 0, reinterpret_cast<hipStream_t>(stream), f16p(hi), lo, rows, cpr, ld, sr,
+                       sc, rec);
     return pnc_launch_status();
 }

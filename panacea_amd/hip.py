@@ -297,6 +297,12 @@ def _check(rc: int, what: str):
         raise PncError(f"{what} failed: {kind}")
 
 
+def _sibling(entry: str, suffix: str, extra, what: str, dtype):
+    """(entry point, inserted arguments) of a wrapper that serves an entry and its `suffix` sibling, which takes one more pointer:
+    the sibling and that pointer when the operand `extra` is given, the entry and nothing otherwise"""
+    return (entry, ()) if extra is None else (entry + suffix, (_ptr(extra, dtype, what),))
+
+
 def _stream() -> int:
     """the CURRENT torch stream of the CURRENT device: every wrapper launches there, and `_ptr` refuses operands that
     live on another device (a launch on device A's stream with device B's pointers reads garbage without an error)"""
@@ -543,13 +549,9 @@ def layernorm(x32, ldx, M, Cch, gamma, beta, eps, y16, ldy, y16_lo=None):
 
 def linear_smallm(a32, lda, w16, bias, out32, ldo, M, N, K, silu_in=False, silu_out=False, w_lo=None):
     """`w_lo`: the fp16 lo plane of split weights (pnc_linear_smallm_split)"""
-    if w_lo is not None:
-        _check(_timed("linear_smallm", 2.0 * M * N * K, 4.0 * N * K, load().pnc_linear_smallm_split, _ptr(a32), lda, _ptr(w16),
-                      _ptr(w_lo, torch.float16, "w_lo"), _ptr(bias), _ptr(out32), ldo, M, N, K, int(silu_in), int(silu_out),
-                      _stream()), "pnc_linear_smallm_split")
-        return
-    _check(_timed("linear_smallm", 2.0 * M * N * K, 2.0 * N * K, load().pnc_linear_smallm, _ptr(a32), lda, _ptr(w16),
-                  _ptr(bias), _ptr(out32), ldo, M, N, K, int(silu_in), int(silu_out), _stream()), "pnc_linear_smallm")
+    name, lo = _sibling("pnc_linear_smallm", "_split", w_lo, "w_lo", torch.float16)
+    _check(_timed("linear_smallm", 2.0 * M * N * K, (2.0 + 2.0 * len(lo)) * N * K, getattr(load(), name), _ptr(a32), lda, _ptr(w16), *lo,
+                  _ptr(bias), _ptr(out32), ldo, M, N, K, int(silu_in), int(silu_out), _stream()), name)
 
 
 def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_start, silu_in=False, silu_out=False, w_lo=None):
@@ -557,15 +559,10 @@ def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_st
     to back (include/panacea_hip.h); `seg_start` = the sites' first columns + [N], a host sequence; `w_lo`: the fp16 lo plane of
     split weights (pnc_linear_smallm_segments_split)"""
     segs = (C.c_int32 * len(seg_start))(*seg_start)
-    if w_lo is not None:
-        _check(_timed("linear_smallm", 2.0 * M * N * K, 4.0 * N * K, load().pnc_linear_smallm_segments_split, _ptr(a32), lda,
-                      _ptr(w16), _ptr(w_lo, torch.float16, "w_lo"), _ptr(bias), _ptr(out32), M, m0, Mtot, N, K,
-                      C.cast(segs, C.c_void_p), len(seg_start) - 1, int(silu_in), int(silu_out), _stream()),
-               "pnc_linear_smallm_segments_split")
-        return
-    _check(_timed("linear_smallm", 2.0 * M * N * K, 2.0 * N * K, load().pnc_linear_smallm_segments, _ptr(a32), lda, _ptr(w16),
+    name, lo = _sibling("pnc_linear_smallm_segments", "_split", w_lo, "w_lo", torch.float16)
+    _check(_timed("linear_smallm", 2.0 * M * N * K, (2.0 + 2.0 * len(lo)) * N * K, getattr(load(), name), _ptr(a32), lda, _ptr(w16), *lo,
                   _ptr(bias), _ptr(out32), M, m0, Mtot, N, K, C.cast(segs, C.c_void_p), len(seg_start) - 1, int(silu_in),
-                  int(silu_out), _stream()), "pnc_linear_smallm_segments")
+                  int(silu_out), _stream()), name)
 
 
 def timestep_embedding(t_i64, F, dim, freqs, out32):
@@ -587,14 +584,9 @@ def nchw_to_tokens_f16(a32, C1, b32, C2, F, Npix, Cpad, out16, out16_lo=None, a_
 
 def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip=None):
     """`c_skip`: a [T] fp32 vector selects pnc_cfg_euler_step_skip (D = eps * c_out + x * c_skip); None = the eps path"""
-    if c_skip is not None:
-        _check(_timed("elementwise", 0.0, T * Npix * Cch * (16.0 if cfg else 12.0), load().pnc_cfg_euler_step_skip, _ptr(eps_tok),
-                      ld, T, Npix, Cch, int(cfg), float(scale), _ptr(x), _ptr(c_skip, torch.float32, "c_skip"), _ptr(c_out),
-                      _ptr(sigma), _ptr(sigma_next), _ptr(x_next), _stream()), "pnc_cfg_euler_step_skip")
-        return
-    _check(_timed("elementwise", 0.0, T * Npix * Cch * (16.0 if cfg else 12.0), load().pnc_cfg_euler_step, _ptr(eps_tok), ld, T,
-                  Npix, Cch, int(cfg), float(scale), _ptr(x), _ptr(c_out), _ptr(sigma), _ptr(sigma_next), _ptr(x_next),
-                  _stream()), "pnc_cfg_euler_step")
+    name, skip = _sibling("pnc_cfg_euler_step", "_skip", c_skip, "c_skip", torch.float32)
+    _check(_timed("elementwise", 0.0, T * Npix * Cch * (16.0 if cfg else 12.0), getattr(load(), name), _ptr(eps_tok), ld, T, Npix, Cch,
+                  int(cfg), float(scale), _ptr(x), *skip, _ptr(c_out), _ptr(sigma), _ptr(sigma_next), _ptr(x_next), _stream()), name)
 
 
 def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux=None, x0=None, aux=None,
@@ -617,11 +609,8 @@ def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, o
     p.n_hist, p.s_noise = len(hist), float(s_noise)
     planes = 3 + (x0 is not None) + (aux is not None) + (noise is not None) + (out_aux is not None) + len(hist)
     nbytes = T * Npix * Cch * (4.0 * planes + (4.0 if cfg else 0.0))
-    if c_skip is not None:
-        _check(_timed("elementwise", 0.0, nbytes, load().pnc_cfg_sampler_step_skip, C.byref(p), _ptr(c_skip, f32, "c_skip"),
-                      _stream()), "pnc_cfg_sampler_step_skip")
-        return
-    _check(_timed("elementwise", 0.0, nbytes, load().pnc_cfg_sampler_step, C.byref(p), _stream()), "pnc_cfg_sampler_step")
+    name, skip = _sibling("pnc_cfg_sampler_step", "_skip", c_skip, "c_skip", f32)
+    _check(_timed("elementwise", 0.0, nbytes, getattr(load(), name), C.byref(p), *skip, _stream()), name)
 
 
 def tokens_to_nchw_f32(x32, ld, F, Npix, Cch, out32):
@@ -633,15 +622,12 @@ def concat_add(a32, C1, s32, c32, C2, M, out32, out16, out16_lo=None, gn_part=No
     """`gn_part` (+ `frames`: M = frames * Npix; `ppc`: pixels per record): also write the GroupNorm(32) records of the output
     (pnc_concat_add_stats; [frames][ceil(Npix / ppc)][32][3] floats) — the GroupNorm that reads the concat then launches no statistics"""
     nb = M * (4.0 * C1 + (8.0 if c32 is not None else 4.0) * C2 + (6.0 + _lo_bytes(out16_lo)) * (C1 + C2))
-    if gn_part is not None:
-        if frames < 1 or M % frames:
-            raise PncError(f"concat_add with gn_part: M = {M} rows are not {frames} whole frames")
-        _check(_timed("elementwise", 0.0, nb, load().pnc_concat_add_stats, _ptr(a32), C1, _ptr(s32), _ptr(c32), C2, frames, M // frames, ppc,
-                      _ptr(out32), _ptr(out16), _ptr(out16_lo), lo_fmt(out16_lo), _ptr(gn_part, torch.float32, "gn_part"), _stream()),
-               "pnc_concat_add_stats")
-        return
-    _check(_timed("elementwise", 0.0, nb, load().pnc_concat_add, _ptr(a32), C1, _ptr(s32), _ptr(c32), C2, M,
-                  _ptr(out32), _ptr(out16), _ptr(out16_lo), lo_fmt(out16_lo), _stream()), "pnc_concat_add")
+    if gn_part is not None and (frames < 1 or M % frames):
+        raise PncError(f"concat_add with gn_part: M = {M} rows are not {frames} whole frames")
+    name, part = _sibling("pnc_concat_add", "_stats", gn_part, "gn_part", torch.float32)
+    rows = (frames, M // frames, ppc) if part else (M,)          # the sibling takes the rows as frames x pixels, and the record size
+    _check(_timed("elementwise", 0.0, nb, getattr(load(), name), _ptr(a32), C1, _ptr(s32), _ptr(c32), C2, *rows, _ptr(out32), _ptr(out16),
+                  _ptr(out16_lo), lo_fmt(out16_lo), *part, _stream()), name)
 
 
 def add_f32(x32, a32, n, y32, y16, y16_lo=None):

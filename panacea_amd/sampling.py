@@ -323,6 +323,14 @@ class _Eps:
                                      [t.contiguous() for t in v], out, out_aux=out_aux, **kw, **self.skip_kw())
         return out
 
+    def euler(self, sigma, next_sigma) -> torch.Tensor:
+        """pnc_cfg_euler_step on these tokens (HEUN1's `out` with no d kept); returns the new fp32 latent"""
+        from . import engine as E
+        out = torch.empty_like(self.x)
+        E.backend().cfg_euler_step(self.tok, self.ld, self.T, self.Npix, self.C, self.cfg, self.scale, self.x, self.c_out,
+                                   sigma.contiguous(), next_sigma.contiguous(), out, **self.skip_kw())
+        return out
+
 
 def _churn_gamma(s_churn, s_tmin, s_tmax, sigma_i: float, num_sigmas: int) -> float:
     """EDMSampler.__call__ (sampling.py:118-122) on the host: the device comparison is fp32 against the fp32-rounded bounds"""
@@ -354,12 +362,7 @@ class EulerEDMSampler(_EDM):
     def _fused_step(self, sigma, next_sigma, denoiser, x, cond, uc):
         """One step with three tiny torch ops (table snap of T sigmas) + the network + one exit kernel; same arithmetic, in
         the reference's rounding order, as denoise() + the Euler update below."""
-        from . import engine as E
-        e = self._fused_eps(sigma, denoiser, x, cond, uc)
-        out = torch.empty_like(e.x)
-        E.backend().cfg_euler_step(e.tok, e.ld, e.T, e.Npix, e.C, e.cfg, e.scale, e.x, e.c_out, sigma.contiguous(),
-                                   next_sigma.contiguous(), out, **e.skip_kw())
-        return out.to(x.dtype)
+        return self._fused_eps(sigma, denoiser, x, cond, uc).euler(sigma, next_sigma).to(x.dtype)
 
     def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0):
         if gamma > 0:

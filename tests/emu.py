@@ -572,22 +572,29 @@ def _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip):
 
 
 def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip=None):
-    X, D = _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip)
-    sg = sigma.reshape(T, 1, 1)
-    d = (X - D) / sg
-    x_next.reshape(T, Cch, Npix).copy_(X + (sigma_next.reshape(T, 1, 1) - sg) * d)
+    """as the library: HEUN1 with v = {sigma, sigma_next} into x_next, no d kept"""
+    _exit_step(SAMPLER_HEUN1, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, [sigma, sigma_next], x_next, c_skip=c_skip)
 
 
 def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux=None, x0=None, aux=None, hist=(),
                      noise=None, s_noise=1.0, c_skip=None):
     """`v` = the mode's per-frame [T] vectors in header order, `hist` = previous LMS d planes newest first"""
+    if mode == SAMPLER_HEUN1 and out_aux is None:                   # PNC_EINVAL: only the Euler entries leave it out
+        raise ValueError("HEUN1 without out_aux")
+    _exit_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux, x0, aux, hist, noise, s_noise, c_skip)
+
+
+def _exit_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, out, out_aux=None, x0=None, aux=None, hist=(), noise=None,
+               s_noise=1.0, c_skip=None):
+    """the one update behind both entries (the library's launch function)"""
     X, D = _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip)
     v = [t.reshape(T, 1, 1) for t in v]
     plane = lambda t: t.reshape(T, Cch, Npix)                       # noqa: E731
     if mode == SAMPLER_HEUN1:
         d = (X - D) / v[0]
         y = X + (v[1] - v[0]) * d
-        plane(out_aux).copy_(d)
+        if out_aux is not None:                                     # None: the Euler exit
+            plane(out_aux).copy_(d)
     elif mode == SAMPLER_HEUN2:
         d_new = (X - D) / v[1]
         d_prime = (plane(aux) + d_new) / 2.0

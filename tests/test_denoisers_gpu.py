@@ -3,6 +3,7 @@ c_noise) on the MI355X (-m gpu): the reference's own trajectories (tests/golden/
 replayed through the HIP kernels; plain vs fused vs fused + hoisted vs graphed on the tiny network; the general-skip entries
 against the eps entries with c_skip = 1; and a short v-prediction schedule at the config-3 shape."""
 import ctypes
+import hashlib
 from pathlib import Path
 
 import numpy as np
@@ -151,6 +152,54 @@ MODES = {  # mode -> (number of per-frame vectors, operands)
 }
 
 
+def _struct_entry(mode, o, shape, cfg, c_skip):
+    """(out, out_aux) of hip.cfg_sampler_step in `mode` on the operands `o`, with the operands MODES names (out_aux stays 0 where the
+    mode writes none)"""
+    T, C, Npix, ld = shape
+    nv, ops = MODES[mode]
+    out, out_aux = torch.zeros(T, C, Npix, device=DEV), torch.zeros(T, C, Npix, device=DEV)
+    kw = {k: o[k] for k in ops if k in ("x0", "aux", "noise")}
+    if "hist" in ops:
+        kw["hist"] = o["hist"]
+    if "out_aux" in ops:
+        kw["out_aux"] = out_aux
+    hip.cfg_sampler_step(mode, o["tok"], ld, T, Npix, C, cfg, 5.0, o["x"], o["c_out"], o["v"][:nv], out, s_noise=0.9, c_skip=c_skip, **kw)
+    torch.cuda.synchronize()
+    return out, out_aux
+
+
+def _sha(t):
+    return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+
+
+# (T, C, Npix, ld): the operands of the tests below; two workgroups with frame boundaries inside one, a partial last one and padded
+# token rows; one live thread
+EXIT_SHAPES = [(2, 4, 96, 8), (3, 4, 100, 8), (1, 1, 1, 1)]
+
+
+@pytest.mark.parametrize("shape", EXIT_SHAPES, ids=lambda s: "T%dC%dN%dld%d" % s)
+@pytest.mark.parametrize("skip", [False, True], ids=["eps", "skip"])
+@pytest.mark.parametrize("cfg", [True, False], ids=["cfg", "nocfg"])
+def test_euler_entries_are_heun1_of_the_struct_entries(cfg, skip, shape):
+    """pnc_cfg_euler_step[_skip] against `out` of pnc_cfg_sampler_step[_skip] in mode HEUN1 with v = {sigma, sigma_next} on the same
+    operands: the same bits, so the two kinds of entry cannot drift apart.  Prints the SHA-256 of every output plane of the Euler
+    entry and of all seven modes of the struct entry: the lines a run on another build of the same ABI (PANACEA_HIP_LIB) must
+    repeat one for one (profiles/sampler_exits.md)."""
+    T, C, Npix, ld = shape
+    o = _exit_operands(T, C, Npix, ld)
+    cs = (torch.arange(T, dtype=torch.float32) * 0.17 + 0.3).to(DEV) if skip else None
+    tag = f"cfg={int(cfg)} skip={int(skip)} T{T}C{C}N{Npix}ld{ld}"
+    x_next = torch.zeros(T, C, Npix, device=DEV)
+    hip.cfg_euler_step(o["tok"], ld, T, Npix, C, cfg, 5.0, o["x"], o["c_out"], o["v"][0], o["v"][1], x_next, c_skip=cs)
+    torch.cuda.synchronize()
+    print(f"exit-sha euler {tag} out={_sha(x_next)}")
+    for mode in MODES:
+        out, out_aux = _struct_entry(mode, o, shape, cfg, cs)
+        print(f"exit-sha mode{mode} {tag} out={_sha(out)} out_aux={_sha(out_aux)}")
+        if mode == hip.SAMPLER_HEUN1:
+            assert torch.isfinite(out).all() and torch.equal(x_next, out)
+
+
 @pytest.mark.parametrize("cfg", [True, False])
 def test_skip_entries_with_c_skip_one_are_the_eps_entries(cfg):
     """x * 1 is exact, so the general-skip instantiation with c_skip = 1 must give the eps entries' bits: the shared device code
@@ -159,19 +208,8 @@ def test_skip_entries_with_c_skip_one_are_the_eps_entries(cfg):
     o = _exit_operands(T, C, Npix, ld)
     ones = torch.ones(T, device=DEV)
     skip = torch.tensor([0.25, 0.0625], device=DEV)
-    for mode, (nv, ops) in MODES.items():
-        res = {}
-        for name, cs in (("eps", None), ("one", ones), ("skip", skip)):
-            out, out_aux = torch.zeros(T, C, Npix, device=DEV), torch.zeros(T, C, Npix, device=DEV)
-            kw = {k: o[k] for k in ops if k in ("x0", "aux", "noise")}
-            if "hist" in ops:
-                kw["hist"] = o["hist"]
-            if "out_aux" in ops:
-                kw["out_aux"] = out_aux
-            hip.cfg_sampler_step(mode, o["tok"], ld, T, Npix, C, cfg, 5.0, o["x"], o["c_out"], o["v"][:nv], out, s_noise=0.9,
-                                 c_skip=cs, **kw)
-            torch.cuda.synchronize()
-            res[name] = (out, out_aux)
+    for mode in MODES:
+        res = {name: _struct_entry(mode, o, (T, C, Npix, ld), cfg, cs) for name, cs in (("eps", None), ("one", ones), ("skip", skip))}
         assert torch.equal(res["eps"][0], res["one"][0]) and torch.equal(res["eps"][1], res["one"][1]), mode
         assert torch.isfinite(res["skip"][0]).all() and not torch.equal(res["skip"][0], res["eps"][0]), mode
     res = {}

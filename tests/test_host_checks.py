@@ -1,15 +1,18 @@
-"""What the attention and norm entry points return for bad arguments, on the CPU: a table of (entry point, arguments, expected
-return code), one row per rejecting `return` of their argument checks, each fault alone on otherwise valid arguments.  A rejected
+"""What the attention, norm, misc and stats entry points return for bad arguments, on the CPU: a table of (entry point, arguments,
+expected return code), one row per rejecting `return` of their argument checks, each fault alone on otherwise valid arguments.  A rejected
 call returns before it launches, and only rejecting rows call a launching entry point: no device is needed and the pointers (into a
 host buffer) are never followed.  The expected codes are what the library returned before the host layers of attn.hip,
-attn_split.hip and norm.hip were restructured (commit cd4909f, loaded through PANACEA_HIP_LIB): this file passes on that library
-unchanged.
+attn_split.hip and norm.hip were restructured (commit cd4909f, loaded through PANACEA_HIP_LIB), and for the rows of misc.hip and
+stats.hip what it returned when the Euler exit still had a kernel and a launch function of its own (commit da1a801): this file passes
+on those libraries unchanged.
 
 pnc_attn_uses_text_kernel is pure host code, so its rows also accept: the text geometry under PNC_OPT_ATTN_VARIANT 0 and 43, and
 each way out of attn_text_dispatch.
 
 No row: the second `return PNC_EINVAL` of pnc_concat_add_stats (more than 3 float4 vectors per lane after slicing) cannot be reached —
-C is a multiple of 64 up to 3072 there, which always slices down to 3."""
+C is a multiple of 64 up to 3072 there, which always slices down to 3.  Nor can the PNC_EABI of the exit launch be reached through
+pnc_cfg_euler_step[_skip]: they fill the parameter struct themselves.  The order among the checks of those two entries cannot be
+seen (every one is PNC_EINVAL); where an entry point of misc.hip / stats.hip mixes codes, a two-fault row pins the order."""
 import ctypes as C
 
 import pytest
@@ -164,6 +167,128 @@ _each("pnc_layernorm", LAYERNORM, EINVAL, x=NULL, gamma=NULL, beta=NULL, y16=NUL
 _each("pnc_layernorm", LAYERNORM, EALIGN, x=A8, gamma=A8, beta=A8, y16=A2, y16_lo=A2)
 
 
+# ---- the sampler exits (misc.hip) ------------------------------------------------------------------------------------------------
+EULER = dict(eps_tok=A16, ld=8, T=2, Npix=5, C=4, cfg=1, scale=5.0, x=A16, c_out=A16, sigma=A16, sigma_next=A16, x_next=A16)
+EULER_SKIP = dict(eps_tok=A16, ld=8, T=2, Npix=5, C=4, cfg=1, scale=5.0, x=A16, c_skip=A16, c_out=A16, sigma=A16, sigma_next=A16, x_next=A16)
+for entry, base in (("pnc_cfg_euler_step", EULER), ("pnc_cfg_euler_step_skip", EULER_SKIP)):
+    _each(entry, base, EINVAL, eps_tok=NULL, x=NULL, c_out=NULL, sigma=NULL, sigma_next=NULL, x_next=NULL, T=0, Npix=0, C=0, ld=3)
+_each("pnc_cfg_euler_step_skip", EULER_SKIP, EINVAL, c_skip=NULL)
+
+
+def _step(mode, struct_bytes=None, **over):
+    """a PncSamplerStepParams with every operand any mode reads (n_hist = 3), then `over`; v / hist entries by index: v2=NULL"""
+    p = hip.SamplerStepParams()
+    p.struct_bytes = C.sizeof(hip.SamplerStepParams) if struct_bytes is None else struct_bytes
+    p.mode, p.ld, p.T, p.Npix, p.C, p.cfg, p.scale, p.n_hist, p.s_noise = mode, 8, 2, 5, 4, 1, 5.0, 3, 1.0
+    p.eps_tok = p.x = p.c_out = p.x0 = p.aux = p.noise = p.out = p.out_aux = A16
+    for k in range(6):
+        p.v[k] = A16
+    for k in range(4):
+        p.hist[k] = A16
+    for name, val in over.items():
+        if name[0] in "vh" and name[-1].isdigit():
+            getattr(p, name.rstrip("0123456789"))[int(name[-1])] = val
+        else:
+            setattr(p, name, val)
+    return p
+
+
+# what each mode cannot do without: its operands and its per-frame vectors (DPM2M reads v[2..4] only next to a previous D)
+STEP_NEEDS = {hip.SAMPLER_HEUN1: ("out_aux", "v0", "v1"), hip.SAMPLER_HEUN2: ("x0", "aux", "v0", "v1"),
+              hip.SAMPLER_EULER_A: ("noise", "v0", "v1", "v2", "v3"), hip.SAMPLER_DPM2S_1: ("out_aux", "v0", "v1", "v2", "v3"),
+              hip.SAMPLER_DPM2S_2: ("x0", "aux", "noise", "v0", "v1", "v2", "v3", "v4"),
+              hip.SAMPLER_DPM2M: ("out_aux", "v0", "v1", "v2", "v3", "v4"), hip.SAMPLER_LMS: ("out_aux", "hist0", "hist1", "hist2", "v0", "v1", "v2", "v3", "v4")}
+for entry, tail in (("pnc_cfg_sampler_step", (None,)), ("pnc_cfg_sampler_step_skip", (A16, None))):
+    _row(entry, "params=NULL", (None,) + tail, EABI)
+    _row(entry, "struct_bytes", (_step(0, struct_bytes=C.sizeof(hip.SamplerStepParams) - 8),) + tail, EABI)
+    _row(entry, "struct_bytes=0", (_step(0, struct_bytes=0),) + tail, EABI)
+    for tag, over in [("eps_tok=NULL", dict(eps_tok=NULL)), ("x=NULL", dict(x=NULL)), ("c_out=NULL", dict(c_out=NULL)), ("out=NULL", dict(out=NULL)),
+                      ("T=0", dict(T=0)), ("Npix=0", dict(Npix=0)), ("C=0", dict(C=0)), ("ld<C", dict(ld=3))]:
+        _row(entry, tag, (_step(hip.SAMPLER_HEUN2, **over),) + tail, EINVAL)
+    for mode, needs in STEP_NEEDS.items():
+        for name in needs:
+            _row(entry, f"mode{mode}-{name}=NULL", (_step(mode, **{name: NULL}),) + tail, EINVAL)
+    _row(entry, "mode5-first-step-v1=NULL", (_step(hip.SAMPLER_DPM2M, aux=NULL, v1=NULL),) + tail, EINVAL)
+    for n_hist in (-1, 4):
+        _row(entry, f"mode6-n_hist={n_hist}", (_step(hip.SAMPLER_LMS, n_hist=n_hist),) + tail, EINVAL)
+    for mode in (-1, 7):                                           # 7: no public mode stands for "HEUN1 without out_aux"
+        _row(entry, f"mode={mode}", (_step(mode),) + tail, EINVAL)
+    _row(entry, "order:struct_bytes,eps_tok", (_step(0, struct_bytes=8, eps_tok=NULL),) + tail, EABI)
+    _row(entry, "order:struct_bytes,mode", (_step(7, struct_bytes=8),) + tail, EABI)
+_row("pnc_cfg_sampler_step_skip", "c_skip=NULL", (_step(hip.SAMPLER_HEUN2), None, None), EINVAL)
+_row("pnc_cfg_sampler_step_skip", "order:struct_bytes,c_skip", (_step(0, struct_bytes=8), None, None), EABI)
+
+# ---- the small-M linears ---------------------------------------------------------------------------------------------------------
+SEGS = (C.c_int32 * 3)(0, 8, 16)
+SEG_PTR = C.addressof(SEGS)
+
+
+def _segs(*start):
+    arr = (C.c_int32 * len(start))(*start)
+    _segs.keep.append(arr)                 # the rows hold the address only
+    return C.addressof(arr)
+
+
+_segs.keep = []
+SMALLM = dict(a=A16, lda=64, W=A16, bias=A16, out=A16, ldo=16, M=2, N=16, K=64, silu_in=0, silu_out=0)
+SMALLM_SPLIT = dict(a=A16, lda=64, W=A16, W_lo=A16, bias=A16, out=A16, ldo=16, M=2, N=16, K=64, silu_in=0, silu_out=0)
+SMALLM_SEG = dict(a=A16, lda=64, W=A16, bias=A16, out=A16, M=2, m0=0, Mtot=2, N=16, K=64, seg_start=SEG_PTR, nseg=2, silu_in=0, silu_out=0)
+SMALLM_SEG_SPLIT = dict(a=A16, lda=64, W=A16, W_lo=A16, bias=A16, out=A16, M=2, m0=0, Mtot=2, N=16, K=64, seg_start=SEG_PTR, nseg=2, silu_in=0,
+                        silu_out=0)
+for entry, base in (("pnc_linear_smallm", SMALLM), ("pnc_linear_smallm_split", SMALLM_SPLIT), ("pnc_linear_smallm_segments", SMALLM_SEG),
+                    ("pnc_linear_smallm_segments_split", SMALLM_SEG_SPLIT)):
+    _each(entry, base, EINVAL, a=NULL, W=NULL, out=NULL, M=[0, 17], N=0, K=[0, 7, 68], lda=66)
+    _each(entry, base, EALIGN, a=A8, W=A8)
+    _row(entry, "order:K%8,a", _args(base, K=68, a=A8), EINVAL)
+    if "W_lo" in base:
+        _each(entry, base, EALIGN, W_lo=A8)
+    if "nseg" in base:
+        _each(entry, base, EINVAL, seg_start=NULL, m0=[-1, 1], Mtot=1, nseg=[0, 65])
+        for tag, start, nseg in [("first!=0", (4, 8, 16), 2), ("last!=N", (0, 8, 12), 2), ("entry%4", (0, 6, 16), 2), ("not-ascending", (0, 8, 8, 16), 3),
+                                 ("descending", (0, 12, 8, 16), 3)]:
+            _row(entry, f"seg_start:{tag}", _args(base, seg_start=_segs(*start), nseg=nseg), EINVAL)
+        _row(entry, "order:a,seg_start", _args(base, a=A8, seg_start=_segs(4, 8, 16)), EALIGN)      # the segment table is read last
+
+# ---- embeddings, layout, elementwise, softmax ------------------------------------------------------------------------------------
+T_EMB = dict(t=A16, F=2, dim=64, freqs=A16, out=A16)
+TO_TOKENS = dict(a=A16, C1=4, a_scale=A16, a_frames=2, b=A16, C2=4, F=2, Npix=5, Cpad=8, out16=A16, out16_lo=A16)
+TO_NCHW = dict(x=A16, ld=8, F=2, Npix=5, C=4, out=A16)
+CONCAT_ADD = dict(a=A16, C1=8, s=A16, c=A16, C2=8, M=5, out32=A16, out16=A16, out16_lo=A16, lo_fmt=hip.LO_F16)
+ADD = dict(x=A16, a=A16, n=64, y32=A16, y16=A16, y16_lo=A16, lo_fmt=hip.LO_F16)
+CAST = dict(x=A16, n=64, y16=A16, y16_lo=A16, lo_fmt=hip.LO_F16)
+SOFTMAX = dict(s=A16, lds=64, M=3, N=64, scale=0.125, causal=0, n_valid=0, p16=A16, ldp=64)
+STATS = dict(hi=A16, lo=A16, lo_fmt=hip.LO_F16, rows=3, cols=64, ld=64, rec=A16)
+for entry in ("pnc_timestep_embedding", "pnc_timestep_embedding_f32"):
+    _each(entry, T_EMB, EINVAL, t=NULL, out=NULL, freqs=NULL, F=0, dim=1)
+_each("pnc_nchw_to_tokens_f16", TO_TOKENS, EINVAL, a=NULL, out16=NULL, F=0, Npix=0, C1=0, C2=-1, b=NULL, a_frames=[0, 3], Cpad=[12, 0])
+_each("pnc_nchw_to_tokens_f16", TO_TOKENS, EALIGN, out16=A8, out16_lo=A8)
+_row("pnc_nchw_to_tokens_f16", "order:Cpad,out16", _args(TO_TOKENS, Cpad=12, out16=A8), EINVAL)
+_each("pnc_tokens_to_nchw_f32", TO_NCHW, EINVAL, x=NULL, out=NULL, F=0, Npix=0, C=0, ld=3)
+_each("pnc_concat_add", CONCAT_ADD, EINVAL, a=NULL, s=NULL, M=0, C1=[6, 0], C2=[6, 0], lo_fmt=2, out16=NULL)
+_row("pnc_concat_add", "no-output", _args(CONCAT_ADD, out32=NULL, out16=NULL, out16_lo=NULL), EINVAL)
+_each("pnc_add_f32", ADD, EINVAL, x=NULL, n=[0, 6], lo_fmt=2, y16=NULL)
+_row("pnc_add_f32", "no-output", _args(ADD, y32=NULL, y16=NULL, y16_lo=NULL), EINVAL)
+_each("pnc_cast_f16", CAST, EINVAL, x=NULL, n=[0, 6], lo_fmt=2, y16=NULL)
+_row("pnc_cast_f16", "no-output", _args(CAST, y16=NULL, y16_lo=NULL), EINVAL)
+_each("pnc_softmax_rows_f16", SOFTMAX, EINVAL, s=NULL, p16=NULL, M=0, N=[0, 66, 16388], n_valid=65, lds=[66, 32], ldp=[66, 32])
+_each("pnc_softmax_rows_f16", SOFTMAX, EALIGN, s=A8, p16=A2)
+_row("pnc_softmax_rows_f16", "order:lds,s", _args(SOFTMAX, lds=66, s=A8), EINVAL)
+_row("pnc_softmax_rows_f16", "order:n_valid,p16", _args(SOFTMAX, n_valid=65, p16=A2), EINVAL)
+
+# ---- pnc_operand_stats_f16 (stats.hip), the range monitor, the options -------------------------------------------------------------
+_each("pnc_operand_stats_f16", STATS, EINVAL, hi=NULL, rec=NULL, rows=0, cols=0, ld=56, lo_fmt=2)
+_row("pnc_operand_stats_f16", "rows*ld>=2^59", _args(STATS, rows=1 << 54), EINVAL)                 # byte offsets leave int64
+_row("pnc_operand_stats_f16", "chunks>2^40", _args(STATS, rows=1 << 38), EINVAL)                   # a wave's 32-bit counters
+_each("pnc_operand_stats_f16", STATS, EALIGN, cols=60, ld=68, hi=A8, rec=A2, lo=A8)
+_row("pnc_operand_stats_f16", "e4m3-lo&7", _args(STATS, lo_fmt=hip.LO_E4M3, lo=A2), EALIGN)
+_row("pnc_operand_stats_f16", "order:lo_fmt,cols", _args(STATS, lo_fmt=2, cols=60), EINVAL)            # arguments before alignment
+_row("pnc_operand_stats_f16", "order:rows,ld%8", _args(STATS, rows=1 << 54, ld=68), EINVAL)
+_row("pnc_operand_stats_f16", "order:rows-chunks,hi", _args(STATS, rows=1 << 38, hi=A8), EINVAL)
+_row("pnc_range_monitor_collect", "out=NULL", (None, None), EINVAL)
+for option in (-1, 12):                                            # PNC_OPT_COUNT = 12; an accepted call returns the previous value
+    _row("pnc_set_option", f"option={option}", (option, 0), EINVAL)
+
+
 @pytest.mark.parametrize("entry,args,want", ROWS)
 def test_rejected_before_any_launch(entry, args, want):
     assert want < 0                       # only rejecting rows reach a launching entry point
@@ -175,7 +300,13 @@ def test_the_base_arguments_are_the_entry_points_own():
     """the ordered base dicts above have one value per parameter of their entry point (the stream is added by _args)"""
     for entry, base in (("pnc_attn_temporal_f16", TEMPORAL), ("pnc_attn_temporal_split_f16", TEMPORAL_SPLIT), ("pnc_groupnorm_stats", GN_STATS),
                         ("pnc_concat_add_stats", CONCAT), ("pnc_groupnorm_apply", GN_APPLY), ("pnc_groupnorm_combine", GN_COMBINE),
-                        ("pnc_groupnorm_temporal_silu", GN_T_SILU), ("pnc_groupnorm_temporal_part", GN_T_PART), ("pnc_layernorm", LAYERNORM)):
+                        ("pnc_groupnorm_temporal_silu", GN_T_SILU), ("pnc_groupnorm_temporal_part", GN_T_PART), ("pnc_layernorm", LAYERNORM),
+                        ("pnc_cfg_euler_step", EULER), ("pnc_cfg_euler_step_skip", EULER_SKIP), ("pnc_linear_smallm", SMALLM),
+                        ("pnc_linear_smallm_split", SMALLM_SPLIT), ("pnc_linear_smallm_segments", SMALLM_SEG),
+                        ("pnc_linear_smallm_segments_split", SMALLM_SEG_SPLIT), ("pnc_timestep_embedding", T_EMB),
+                        ("pnc_timestep_embedding_f32", T_EMB), ("pnc_nchw_to_tokens_f16", TO_TOKENS), ("pnc_tokens_to_nchw_f32", TO_NCHW),
+                        ("pnc_concat_add", CONCAT_ADD), ("pnc_add_f32", ADD), ("pnc_cast_f16", CAST), ("pnc_softmax_rows_f16", SOFTMAX),
+                        ("pnc_operand_stats_f16", STATS)):
         assert len(base) + 1 == len(hip._SIGNATURES[entry][1]), entry
 
 
