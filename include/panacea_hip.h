@@ -574,8 +574,10 @@ int pnc_operand_stats_f16(const void* hi, const void* lo, int lo_fmt, int64_t ro
 /* ------------------------------------------------------------------------- *
  * 5. First-stage decoder: row softmax of a materialised score
  *    matrix, p[m][:] = softmax(scale * s[m][:]) (fp32 in, fp32 statistics, fp16
- *    out), N <= 16384, N % 4 == 0.  Columns >= n_valid (n_valid <= 0: N) are masked; causal != 0 also masks columns
- *    j > m (row m = query m of ONE sequence: the OpenCLIP text tower's attn_mask, sgm/modules/encoders/modules.py:608).  The single-head d = 512 attention of the VAE
+ *    out), N % 4 == 0.  A row is kept in registers: N <= 16384 is THIS kernel's limit, not the attention block's (section 6
+ *    serves longer frames).  Columns >= n_valid (n_valid <= 0: N) are masked; causal != 0 also masks columns
+ *    j > m (row m = query m of ONE sequence: the OpenCLIP text tower's attn_mask, sgm/modules/encoders/modules.py:608).  For frames
+ *    of up to 16384 tokens the single-head d = 512 attention of the VAE
  *    mid block runs as  S = Q K^T (pnc_gemm_f16, fp32 out) -> this -> O = P V
  *    (pnc_gemm_f16 against the channel-major V^T).
  *     -> AttnBlock / MemoryEfficientAttnBlock.attention
@@ -583,6 +585,29 @@ int pnc_operand_stats_f16(const void* hi, const void* lo, int lo_fmt, int64_t ro
  * ------------------------------------------------------------------------- */
 int pnc_softmax_rows_f16(const float* s, int64_t lds, int M, int N, float scale, int causal, int n_valid,
                          void* p16, int64_t ldp, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * 6. First-stage attention, fused: single-head self-attention over the N tokens of each of F frames, head dim C, with an
+ *    online softmax — no N x N matrix, no workspace, ONE launch for all frames, any N.
+ *        o = softmax(scale * q k^T) v      per frame, fp16 in / out
+ *    q, k, o : fp16 token rows; the row of (frame f, token i) is f*N + i, element c at [(f*N + i)*ld + c], c < C
+ *    vt      : V channel-major per frame ("V^T"): vt[f*vt_fstride + c*ldvt + j] for key j < N, c < C
+ *    Every token of a frame attends to all N tokens of the same frame and to nothing else.  Scores are accumulated in fp32, the
+ *    running maximum, the row sum and the output accumulators are fp32; probabilities are rounded to fp16 against the running
+ *    maximum before the P V product (as section 2 does) and the result is normalised once at the end.
+ *    ONLY the named elements are read or written: row padding between C and ld, V^T columns between N and ldvt and rows after
+ *    the last frame may hold anything (NaN included) and a buffer may end right after its last named element; o's padding is
+ *    left as it was.  Deterministic: no atomics, the same bits on every run.  o must not overlap q, k or vt.
+ *    Accepted: C in {128, 256, 512}; F >= 1; N >= 8, N % 8 == 0; F * ceil(N / 64) < 2^31; ldq, ldk, ldo >= C, ldvt >= N,
+ *    vt_fstride >= 0; anything else -> PNC_EINVAL.  ldq, ldk, ldo, ldvt, vt_fstride multiples of 8 elements and q, k, vt, o
+ *    16-byte aligned, else PNC_EALIGN.  Checked in this order: null pointers, ranges, leading dimensions, pointer alignment;
+ *    nothing is launched on a refusal.
+ *     -> AttnBlock / MemoryEfficientAttnBlock.attention
+ *        (sgm/modules/diffusionmodules/model.py:393-408, 444-472)
+ * ------------------------------------------------------------------------- */
+int pnc_attn_frame_f16(const void* q, int64_t ldq, const void* k, int64_t ldk,
+                       const void* vt, int64_t ldvt, int64_t vt_fstride,
+                       void* o, int64_t ldo, int F, int N, int C, float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,7 @@ _SIGNATURES = {
     "pnc_attn_temporal_split_f16": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "pnc_softmax_rows_f16": (_I, [_P, _L, _I, _I, _F, _I, _I, _P, _L, _P]),
     "pnc_attn_temporal_f16": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "pnc_attn_frame_f16": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _F, _P]),
     "pnc_groupnorm_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "pnc_groupnorm_apply": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _I, _P, _I, _I, _P]),
     "pnc_groupnorm_combine": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -497,6 +498,14 @@ def attn_temporal_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, 
 def softmax_rows(s32, lds, M, N, scale, p16, ldp, causal=False, n_valid=0):
     _check(_timed("softmax_rows", 0.0, 6.0 * M * N, load().pnc_softmax_rows_f16, _ptr(s32), lds, M, N, scale, int(causal),
                   n_valid, _ptr(p16), ldp, _stream()), "pnc_softmax_rows_f16")
+
+
+def attn_frame(q, ldq, k, ldk, vt, ldvt, vt_fstride, o, ldo, *, F, N, C, scale):
+    """pnc_attn_frame_f16: o = softmax(scale * q k^T) v over the N tokens of each of F frames, single head of dim C (128 / 256 / 512),
+    fused (online softmax, no N x N matrix), one launch; vt is V channel-major per frame (include/panacea_hip.h section 6)"""
+    f16 = torch.float16
+    _check(_timed("attn_frame", 4.0 * F * N * N * C, 0.0, load().pnc_attn_frame_f16, _ptr(q, f16, "q"), ldq, _ptr(k, f16, "k"), ldk,
+                  _ptr(vt, f16, "vt"), ldvt, vt_fstride, _ptr(o, f16, "o"), ldo, F, N, C, scale, _stream()), "pnc_attn_frame_f16")
 
 
 def attn_temporal(q, ldq, k, ldk, v, ldv, o, ldo, *, B, T, Npix, heads, scale):

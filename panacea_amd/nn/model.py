@@ -9,11 +9,14 @@ sub-tree of a checkpoint loads with `strict=False`; all arithmetic runs through 
 * 1x1 `nin_shortcut`, q / k / v / proj_out                                 -> pnc_gemm_f16, residual adds in its epilogue;
 * the single-head d = C attention of the mid block (model.py:374-415)     -> S = Q K^T (fp32) -> pnc_softmax_rows_f16
   -> O = P V against the channel-major V^T the v-projection writes; one frame at a time (12288^2 scores at 256x3072).
+  Frames of FUSED_ATTN_MIN_TOKENS tokens or more (default: beyond the row softmax's 16384) -> pnc_attn_frame_f16, one fused
+  launch over all frames on the same q / k / V^T, no N x N matrix.
 
 The per-module `forward`s take/return NCHW tensors like the reference; `Decoder.forward` keeps everything resident.
 """
 from __future__ import annotations
 
+import os
 from typing import List
 
 import torch
@@ -22,6 +25,28 @@ import torch.nn as nn
 from .. import engine as E
 from ..engine import Act, Packable, Runtime
 from .util import act_from_nchw
+
+
+SOFTMAX_ROWS_MAX_TOKENS = 16384      # pnc_softmax_rows_f16 keeps a row in registers: the limit of the three-launch attention
+FUSED_ATTN_CHANNELS = (128, 256, 512)  # the head dims pnc_attn_frame_f16 is instantiated for
+
+
+def _fused_attn_min_tokens(default: int = SOFTMAX_ROWS_MAX_TOKENS + 1) -> int:
+    """PNC_VAE_FUSED_ATTN_MIN_TOKENS (read once, at import): a frame of that many tokens or more takes the fused attention
+    kernel.  Unset: only the frames the three-launch path cannot serve.  0 sends every frame there (measurements, tests)."""
+    raw = os.environ.get("PNC_VAE_FUSED_ATTN_MIN_TOKENS")
+    if raw is None or raw.strip() == "":
+        return default
+    try:
+        v = int(raw.strip())
+    except ValueError:
+        raise ValueError(f"PNC_VAE_FUSED_ATTN_MIN_TOKENS must be a non-negative integer, got {raw!r}") from None
+    if v < 0:
+        raise ValueError(f"PNC_VAE_FUSED_ATTN_MIN_TOKENS must be a non-negative integer, got {raw!r}")
+    return v
+
+
+FUSED_ATTN_MIN_TOKENS = _fused_attn_min_tokens()
 
 
 def Normalize(in_channels, num_groups=32):
@@ -174,10 +199,20 @@ class AttnBlock(nn.Module, Packable):
                     v=_conv1x1_params(self.v), o=_conv1x1_params(self.proj_out))
 
     def _run(self, rt: Runtime, x: Act) -> Act:
-        pk = self.packed()
         C, N, M, F = self.in_channels, x.N, x.M, x.F
-        if N > 16384 or N % 8:
-            raise NotImplementedError(f"AttnBlock over {N} tokens per frame (supported: multiples of 8 up to 16384)")
+        if N % 8:
+            raise NotImplementedError(f"AttnBlock over {N} tokens per frame (supported: multiples of 8)")
+        # The fused kernel is an OPTIONAL capability of the backend, looked up rather than called through the handle: the emulated
+        # backend of the tests has no twin of it yet and then behaves as before, refusal of long frames included.
+        attn_frame = getattr(rt.be, "attn_frame", None)
+        fused_ok = attn_frame is not None and C in FUSED_ATTN_CHANNELS
+        if N > SOFTMAX_ROWS_MAX_TOKENS and not fused_ok:
+            why = (f"the fused kernel is built for {FUSED_ATTN_CHANNELS} channels, not {C} channels" if attn_frame is not None
+                   else "this backend has no fused attention kernel (attn_frame)")
+            raise NotImplementedError(f"AttnBlock over {N} tokens per frame: the three-launch path serves up to "
+                                      f"{SOFTMAX_ROWS_MAX_TOKENS} tokens and {why}")
+        fused = fused_ok and N >= FUSED_ATTN_MIN_TOKENS
+        pk = self.packed()
         h16 = E.gn_spatial(rt, x.f32, F, N, C, *pk["n"], 1e-6, False).hi
         q16, k16 = rt.empty((M, C), torch.float16), rt.empty((M, C), torch.float16)
         vt16 = rt.empty((F, C, N), torch.float16)                       # channel-major V^T per frame
@@ -186,12 +221,15 @@ class AttnBlock(nn.Module, Packable):
         rt.be.gemm(h16, pk["v"][0], M=M, N=C, K=C, lda=C, bias=pk["v"][1], out16t=vt16, ldt=N, t_rows=N,
                    t_gstride=C * N, n_split=0)
         o16 = rt.empty((M, C), torch.float16)
-        s32 = rt.empty((N, N), torch.float32)                           # one frame's scores at a time (reused)
-        p16 = rt.empty((N, N), torch.float16)
-        for f in range(F):
-            rt.be.gemm(q16[f * N:], k16[f * N:(f + 1) * N], M=N, N=N, K=C, lda=C, out32=s32, ldc32=N)
-            rt.be.softmax_rows(s32, N, N, N, float(C) ** -0.5, p16, N)
-            rt.be.gemm(p16, vt16[f], M=N, N=C, K=N, lda=N, out16=o16[f * N:], ldc16=C)
+        if fused:
+            attn_frame(q16, C, k16, C, vt16, N, C * N, o16, C, F=F, N=N, C=C, scale=float(C) ** -0.5)
+        else:
+            s32 = rt.empty((N, N), torch.float32)                       # one frame's scores at a time (reused)
+            p16 = rt.empty((N, N), torch.float16)
+            for f in range(F):
+                rt.be.gemm(q16[f * N:], k16[f * N:(f + 1) * N], M=N, N=N, K=C, lda=C, out32=s32, ldc32=N)
+                rt.be.softmax_rows(s32, N, N, N, float(C) ** -0.5, p16, N)
+                rt.be.gemm(p16, vt16[f], M=N, N=C, K=N, lda=N, out16=o16[f * N:], ldc16=C)
         out = rt.empty((M, C), torch.float32)
         rt.be.gemm(o16, pk["o"][0], M=M, N=C, K=C, lda=C, bias=pk["o"][1], res1=x.f32, ldr1=C, out32=out, ldc32=C)
         return Act(F, x.H, x.W, C, f32=out)
