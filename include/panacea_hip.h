@@ -609,6 +609,34 @@ int pnc_attn_frame_f16(const void* q, int64_t ldq, const void* k, int64_t ldk,
                        const void* vt, int64_t ldvt, int64_t vt_fstride,
                        void* o, int64_t ldo, int F, int N, int C, float scale, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * 7. Image boundary: 8-bit channels-last frames in and out.  Additive under ABI 8.  Both entries
+ *    launch on the caller's stream, allocate nothing and do not synchronise; nothing is launched on a refusal.
+ *
+ *    pnc_u8_to_tokens_f16: uint8 [F][Npix][C] (contiguous, at ANY byte address) -> fp16 tokens [F*Npix][Cpad] through a table
+ *        v = lut[src[f][p][c]]         lut: 256 fp32 values on the device
+ *        c <  C        : out16 = (half)v,  out16_lo = (half)((v - (float)out16) * 2^11)      (out16_lo may be NULL)
+ *        C <= c < Cpad : out16 = out16_lo = +0
+ *    which is what pnc_nchw_to_tokens_f16 writes for a float input that holds v.  The table carries the scaling: the reference
+ *    scales on the host with IEEE fp32 divisions (`source.astype(np.float32) / 255.0` for the 19-channel BEV layout,
+ *    `target.astype(np.float32) / 127.5 - 1.0` for the frames; sgm/data/nuscenes_video/nuscenes_datasets_video.py:542-552), and a
+ *    table built with those very expressions over the 256 bytes reproduces them bit for bit; the kernel has no arithmetic of its own.
+ *    Only the F*Npix*C bytes of src are read: aligned vector loads never reach outside [src, src + F*Npix*C).
+ *    PNC_EINVAL: a null src / lut / out16, F < 1, Npix < 1, C < 1, C > 4096, Cpad % 8 != 0, Cpad < C.  PNC_EALIGN: out16 or
+ *    out16_lo not 16-byte aligned.
+ *
+ *    pnc_tokens_to_u8: fp32 tokens, M rows of C <= 8 columns with row stride ld >= C -> uint8 [M][C] (contiguous)
+ *        t = fminf(fmaxf(x, -1), 1);  t = (t + 1.0f) * 0.5f;  t = t * 255.0f;  out = (uint8)(int)t
+ *    every operation rounded on its own, in this order (no FMA contraction); (t + 1) * 0.5f has the bits of (t + 1) / 2.  NaN -> 0
+ *    (a choice: the reference's numpy cast of NaN is undefined).  The decoder's last conv writes [F*H*W][3] tokens, which already
+ *    are H x W x 3 frames: this is `torch.clamp(x, -1, 1); (x + 1) / 2; (x * 255).astype(np.uint8)` of inference.py:189-193
+ *    without the transposes to planes and back.  Exactly M * C bytes are written.
+ *    PNC_EINVAL: a null pointer, M < 1, C < 1, C > 8, ld < C.  PNC_EALIGN: x or out not 4-byte aligned.
+ * ------------------------------------------------------------------------- */
+int pnc_u8_to_tokens_f16(const uint8_t* src, const float* lut, int F, int Npix, int C, int Cpad,
+                         void* out16, void* out16_lo, void* stream);
+int pnc_tokens_to_u8(const float* x, int ld, int64_t M, int C, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

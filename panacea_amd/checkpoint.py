@@ -80,27 +80,44 @@ def _to_uint8(img: torch.Tensor):
     return (x * 255).astype(np.uint8)
 
 
+def _host_u8(frames: torch.Tensor):
+    """(T, H, W, 3) uint8 frames, from the device or the host -> one numpy array (ONE copy of the whole tensor)"""
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"uint8 frames are (T, H, W, 3) channels-last, got {tuple(frames.shape)}")
+    return frames.detach().cpu().numpy()
+
+
 def save_view_frames(frames: torch.Tensor, root: str, sample_names: Iterable[str], view_width: int = 512) -> List[str]:
-    """frames: (T, 3, H, 6*view_width) panorama frames in [-1, 1]; `sample_names[i]` names the clip of camera slot i.
+    """frames: (T, 3, H, 6*view_width) panorama frames in [-1, 1], or the same frames already quantised: (T, H, 6*view_width, 3)
+    uint8 (pipeline.sample_frames(output="uint8")), which give the same files; `sample_names[i]` names the clip of camera slot i.
     Writes `<root>/<name>/_{frame:06}.jpg` per view and frame (inference.py:181-202) and returns the paths."""
+    import numpy as np
     from PIL import Image
     names = list(sample_names)
     paths = []
+    host = _host_u8(frames) if frames.dtype == torch.uint8 else None
     for view in CAMERA_VIEWS:
         i = VIEW_SLOT[view]
         d = os.path.join(root, names[i])
         os.makedirs(d, exist_ok=True)
         for t in range(frames.shape[0]):
-            tile = frames[t][:, :, view_width * i: view_width * (i + 1)]
+            if host is not None:                # a view's tile is a column slice of the frame
+                img = np.ascontiguousarray(host[t, :, view_width * i: view_width * (i + 1)])
+            else:
+                img = _to_uint8(frames[t][:, :, view_width * i: view_width * (i + 1)])
             path = os.path.join(d, "_{:06}.jpg".format(t))
-            Image.fromarray(_to_uint8(tile)).save(path)
+            Image.fromarray(img).save(path)
             paths.append(path)
     return paths
 
 
 def save_gif(frames: torch.Tensor, filename: str, fps: int = 4) -> str:
-    """(T, 3, H, W) in [-1, 1] -> looping GIF at 4 frames/s (inference.py:128-137)."""
+    """(T, 3, H, W) in [-1, 1], or (T, H, W, 3) uint8 -> looping GIF at 4 frames/s (inference.py:128-137)."""
+    import numpy as np
     from PIL import Image
-    imgs = [Image.fromarray(_to_uint8(f)) for f in frames]
+    if frames.dtype == torch.uint8:
+        imgs = [Image.fromarray(np.ascontiguousarray(f)) for f in _host_u8(frames)]
+    else:
+        imgs = [Image.fromarray(_to_uint8(f)) for f in frames]
     imgs[0].save(filename, save_all=True, append_images=imgs[1:], duration=1000 // fps, loop=0)
     return filename

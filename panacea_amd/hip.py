@@ -150,6 +150,8 @@ _SIGNATURES = {
     "pnc_cast_f16": (_I, [_P, _L, _P, _P, _I, _P]),
     "pnc_range_monitor_collect": (_I, [_P, _P]),
     "pnc_operand_stats_f16": (_I, [_P, _P, _I, _L, _I, _L, _P, _P]),
+    "pnc_u8_to_tokens_f16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "pnc_tokens_to_u8": (_I, [_P, _I, _L, _I, _P, _P]),
 }
 
 _lib = None
@@ -589,6 +591,29 @@ def nchw_to_tokens_f16(a32, C1, b32, C2, F, Npix, Cpad, out16, out16_lo=None, a_
     _check(_timed("layout", 0.0, F * Npix * (4.0 * (C1 + C2) + 2.0 * Cpad), load().pnc_nchw_to_tokens_f16, _ptr(a32),
                   C1, _ptr(a_scale), a_frames or F, _ptr(b32), C2, F, Npix, Cpad, _ptr(out16), _ptr(out16_lo), _stream()),
            "pnc_nchw_to_tokens_f16")
+
+
+def u8_to_tokens_f16(src_u8, lut32, F, Npix, Cch, Cpad, out16, out16_lo=None):
+    """pnc_u8_to_tokens_f16: uint8 channels-last frames [F, Npix, Cch] (contiguous, any byte address) -> fp16 tokens [F * Npix, Cpad]
+    (+ lo plane) through the 256-entry fp32 device table `lut32`"""
+    if not src_u8.is_contiguous() or src_u8.numel() != F * Npix * Cch:
+        raise PncError(f"u8_to_tokens_f16: src is {F} x {Npix} x {Cch} contiguous bytes, got {tuple(src_u8.shape)} "
+                       f"(contiguous: {src_u8.is_contiguous()})")
+    if lut32.numel() != 256 or not lut32.is_contiguous():
+        raise PncError(f"u8_to_tokens_f16: the table is 256 contiguous fp32 values, got {tuple(lut32.shape)}")
+    nb = F * Npix * (1.0 * Cch + (2.0 if out16_lo is None else 4.0) * Cpad)
+    _check(_timed("layout", 0.0, nb, load().pnc_u8_to_tokens_f16, _ptr(src_u8, torch.uint8, "src"), _ptr(lut32, torch.float32, "lut"),
+                  F, Npix, Cch, Cpad, _ptr(out16, torch.float16, "out16"), _ptr(out16_lo, torch.float16, "out16_lo"), _stream()),
+           "pnc_u8_to_tokens_f16")
+
+
+def tokens_to_u8(x32, ld, M, Cch, out_u8):
+    """pnc_tokens_to_u8: the first Cch <= 8 columns of M fp32 token rows (row stride ld) -> uint8 [M, Cch], the reference's
+    clamp / (x + 1) / 2 / * 255 / truncate per element (inference.py:189-193)"""
+    if not out_u8.is_contiguous() or out_u8.numel() != M * Cch:
+        raise PncError(f"tokens_to_u8: out is {M} x {Cch} contiguous bytes, got {tuple(out_u8.shape)}")
+    _check(_timed("layout", 0.0, M * Cch * 5.0, load().pnc_tokens_to_u8, _ptr(x32, torch.float32, "x"), ld, M, Cch,
+                  _ptr(out_u8, torch.uint8, "out"), _stream()), "pnc_tokens_to_u8")
 
 
 def cfg_euler_step(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, sigma, sigma_next, x_next, c_skip=None):

@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import engine as E
+from .. import image
 from ..engine import Act, Packable, Runtime
 from .util import act_from_nchw
 
@@ -447,15 +448,43 @@ class FirstStageEncoder(nn.Module, Packable):
             ic = enc.packed()["ic"]
             x16 = rt.empty((F * H * W, ic), torch.float16)
             rt.be.nchw_to_tokens_f16(x.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, ic, x16)
-            h = enc._run(rt, x16, F, H, W)
-            w, b = self.packed()["q"]
-            n = self.quant_conv.out_channels
-            m32 = rt.empty((h.M, n), torch.float32)
-            rt.be.gemm(h.need_f16(rt).hi, w, M=h.M, N=n, K=h.C, lda=h.C, bias=b, out32=m32, ldc32=n)
-            return Act(h.F, h.H, h.W, n, f32=m32).to_nchw().to(x.dtype)
+            return self._moments_of_tokens(rt, x16, F, H, W).to(x.dtype)
+
+    def _moments_of_tokens(self, rt: Runtime, x16: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
+        """encoder + quant_conv on the image tokens x16 [F*H*W, ic] -> the moments, NCHW fp32"""
+        h = self.encoder._run(rt, x16, F, H, W)
+        w, b = self.packed()["q"]
+        n = self.quant_conv.out_channels
+        m32 = rt.empty((h.M, n), torch.float32)
+        rt.be.gemm(h.need_f16(rt).hi, w, M=h.M, N=n, K=h.C, lda=h.C, bias=b, out32=m32, ldc32=n)
+        return Act(h.F, h.H, h.W, n, f32=m32).to_nchw()
+
+    def moments_u8(self, x_u8: torch.Tensor, table: str = "image") -> torch.Tensor:
+        """`moments` of (F, H, W, 3) uint8 channels-last frames, scaled on their way into the token matrix by `table` ("image":
+        byte / 127.5 - 1, the dataset's scaling of frames; "layout": byte / 255): the bits of
+        `moments(table[x_u8].permute(0, 3, 1, 2))` without a float image anywhere.  Returns fp32."""
+        with torch.no_grad():
+            x_u8 = image.frames_u8(x_u8, "moments_u8")
+            F, H, W, C = x_u8.shape
+            if C != self.encoder.in_channels:
+                raise ValueError(f"moments_u8: frames of {C} channels for an encoder of {self.encoder.in_channels}")
+            image.table(table)                                     # (an unknown kind is refused here)
+            rt = Runtime(x_u8.device, F, 1)
+            image.capability(rt.be, "u8_to_tokens_f16")
+            ic = self.encoder.packed()["ic"]
+            x16 = rt.empty((F * H * W, ic), torch.float16)
+            image.u8_to_tokens(rt, x_u8, table, ic, E.Operand(x16))
+            return self._moments_of_tokens(rt, x16, F, H, W)
 
     def encode(self, x: torch.Tensor, generator=None, sample: bool = True) -> torch.Tensor:
-        mom = self.moments(x)
+        return self._posterior(self.moments(x), generator, sample)
+
+    def encode_u8(self, x_u8: torch.Tensor, generator=None, sample: bool = True, table: str = "image") -> torch.Tensor:
+        """`encode` of uint8 channels-last frames (see moments_u8): the same posterior, the same draw for the same generator state"""
+        return self._posterior(self.moments_u8(x_u8, table), generator, sample)
+
+    @staticmethod
+    def _posterior(mom: torch.Tensor, generator, sample: bool) -> torch.Tensor:
         mean, logvar = torch.chunk(mom, 2, dim=1)
         if not sample:
             return mean
@@ -489,17 +518,31 @@ class FirstStageDecoder(nn.Module, Packable):
         b[: self.decoder.z_channels] = self.post_quant_conv.bias.detach().float()
         return dict(w=w.contiguous(), b=b, ec=ec, zc=zc)
 
+    def _decode_tokens(self, rt: Runtime, z: torch.Tensor) -> Act:
+        """post_quant_conv + decoder on the latent z (F, C, H, W) -> the decoder's output in the resident layout"""
+        pk = self.packed()
+        F, C, H, W = z.shape
+        M = F * H * W
+        e16 = rt.empty((M, pk["ec"]), torch.float16)
+        rt.be.nchw_to_tokens_f16(z.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, pk["ec"], e16)
+        z16 = rt.empty((M, pk["zc"]), torch.float16)
+        rt.be.gemm(e16, pk["w"], M=M, N=pk["zc"], K=pk["ec"], lda=pk["ec"], bias=pk["b"], out16=z16, ldc16=pk["zc"])
+        return self.decoder._run(rt, z16, F, H, W)
+
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
-            pk = self.packed()
-            F, C, H, W = z.shape
-            rt = Runtime(z.device, F, 1)
-            M = F * H * W
-            e16 = rt.empty((M, pk["ec"]), torch.float16)
-            rt.be.nchw_to_tokens_f16(z.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, pk["ec"], e16)
-            z16 = rt.empty((M, pk["zc"]), torch.float16)
-            rt.be.gemm(e16, pk["w"], M=M, N=pk["zc"], K=pk["ec"], lda=pk["ec"], bias=pk["b"], out16=z16, ldc16=pk["zc"])
-            out = self.decoder._run(rt, z16, F, H, W).to_nchw()
+            out = self._decode_tokens(Runtime(z.device, z.shape[0], 1), z).to_nchw()
         return out.to(z.dtype)
+
+    def decode_u8(self, z: torch.Tensor) -> torch.Tensor:
+        """z (F, C, h, w) -> (F, 8h, 8w, 3) uint8 frames on z's device: the decoder's last conv writes an [F*H*W, 3] token matrix,
+        which already is H x W x 3, and pnc_tokens_to_u8 quantises it in place of `to_nchw()` + the host's clamp, (x + 1) / 2,
+        * 255, truncate (inference.py:189-193).  The bytes of `checkpoint._to_uint8(decode(z)[f])`, frame by frame."""
+        if self.decoder.tanh_out or self.decoder.give_pre_end:
+            raise NotImplementedError("decode_u8 quantises the output conv's tokens: tanh_out / give_pre_end decoders go through decode()")
+        with torch.no_grad():
+            rt = Runtime(z.device, z.shape[0], 1)
+            image.capability(rt.be, "tokens_to_u8")
+            return image.tokens_to_u8(rt, self._decode_tokens(rt, z))
 
     forward = decode

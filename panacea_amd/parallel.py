@@ -282,6 +282,8 @@ def local_views(t: torch.Tensor, layout: RankLayout) -> torch.Tensor:
     """this rank's band of views of an NCHW map (latent, `concat`, or the 8x larger hint): columns [v W/V, (v+1) W/V)"""
     if layout.views == 1:
         return t
+    if t.dtype == torch.uint8:
+        raise NotImplementedError("a uint8 channels-last hint is not cut into view bands here: shard the float NCHW layout")
     W = t.shape[-1]
     if W % layout.views:
         raise ValueError(f"map width {W} does not split into {layout.views} view groups")

@@ -13,14 +13,14 @@ from typing import Dict, Optional
 
 import torch
 
-from . import sampling
+from . import engine, image, sampling
 
 SCALE_FACTOR = 0.18215
 
 
 def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
                   noise: torch.Tensor, num_steps: int = 25, cfg_scale: float = 5.0, hoist: bool = True,
-                  scale_factor: float = SCALE_FACTOR, sampler=None, denoiser=None) -> torch.Tensor:
+                  scale_factor: float = SCALE_FACTOR, sampler=None, denoiser=None, output: str = "float") -> torch.Tensor:
     """noise: (T, 4, h, w) unit-variance latents of ONE sample; returns (T, 3, 8h, 8w) frames.  T is taken from `noise` and has
     to be the `num_frames` the network was built with (configs.with_frames), 1 <= T <= 16: the temporal kernels hold at most 16
     frames of a pixel, and a network for a longer clip is refused when it is built.
@@ -28,7 +28,16 @@ def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[
     panacea_amd.sampling; or a reference `sampler_config` dict (sampling.from_config; its num_steps, else `num_steps`).
     `denoiser`: None = the YAML's DiscreteDenoiser with EpsScaling; a denoiser mirror of panacea_amd.sampling (Denoiser or
     DiscreteDenoiser with EpsScaling / VScaling / EDMScaling); or a reference `denoiser_config` dict
-    (sampling.denoiser_from_config)."""
+    (sampling.denoiser_from_config).
+    `output`: "float" = (T, 3, 8h, 8w) frames in [-1, 1]; "uint8" = (T, 8h, 8w, 3) uint8 frames on the device, quantised from the
+    decoder's token matrix (FirstStageDecoder.decode_u8) — what checkpoint.save_view_frames / save_gif write for the float frames.
+    `cond["cond_feat"]` / `uc["cond_feat"]` may be the dataset's uint8 channels-last BEV layout (T, 8h, 8w, C)."""
+    if output not in ("float", "uint8"):
+        raise ValueError(f"output: 'float' or 'uint8', got {output!r}")
+    if output == "uint8":               # refused before the first step, not after the last
+        if not hasattr(first_stage, "decode_u8"):
+            raise TypeError(f"output='uint8' needs a first stage with decode_u8; {type(first_stage).__name__} has none")
+        image.capability(engine.backend(), "tokens_to_u8")
     dev = noise.device
     if denoiser is None:
         den = sampling.DiscreteDenoiser()
@@ -45,4 +54,4 @@ def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[
             smp.num_steps = num_steps
     with torch.no_grad():
         z = smp(sampling.BoundDenoiser(den, network), noise, cond, uc, network=network if hoist else None)
-        return first_stage.decode(z / scale_factor)
+        return first_stage.decode_u8(z / scale_factor) if output == "uint8" else first_stage.decode(z / scale_factor)

@@ -9,6 +9,7 @@ per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference'
     python tools/sample.py --prediction v --steps 5       (a v-prediction checkpoint; `edm` = EDMScaling + the continuous Denoiser)
     python tools/sample.py --prediction edm --discretization edm --sampler heun --steps 18
     python tools/sample.py --frames 16 --steps 5          (clips of 1 .. 16 frames; the default 8 is the released FrameLength)
+    python tools/sample.py --u8 --steps 5                 (uint8 channels-last BEV layout in, uint8 frames out: panacea_amd.image)
 """
 import argparse, json, sys, time
 from pathlib import Path
@@ -79,6 +80,9 @@ def main():
                     help="profile the operand ranges of the first two evaluations of the run under the chosen policy "
                          "(UNetModel3D.profile_ranges): prints the class table, the ten widest sites and the recommended operand "
                          "policy; FILE: also write the report as JSON")
+    ap.add_argument("--u8", action="store_true",
+                    help="the image boundary on the device: the synthetic BEV layout enters as uint8 channels-last bytes (scaled / 255 in "
+                         "the hint stem's entry kernel) and the frames leave the decoder as uint8 (T, H, W, 3)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
@@ -100,6 +104,9 @@ def main():
     g = {k: v.to(dev) for k, v in synth.synth_inputs(2, T, h, w, context_dim=kw["context_dim"]).items()}
     cond = {"crossattn": g["crossattn"][1:2], "concat": g["concat"][T:], "cond_feat": g["cond_feat"][T:]}
     uc = {"crossattn": g["crossattn"][0:1], "concat": g["concat"][:T], "cond_feat": g["cond_feat"][:T]}
+    if a.u8:       # the layout as the dataset holds it: H x W x C bytes, one tensor shared by the two CFG halves
+        layout = (g["cond_feat"][T:] * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        cond["cond_feat"] = uc["cond_feat"] = layout
     noise = torch.randn(T, 4, h, w, generator=torch.Generator().manual_seed(a.seed)).to(dev)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     smp = sampling.from_config({"target": P + "sampling." + SAMPLERS[a.sampler],
@@ -111,15 +118,20 @@ def main():
     profiling = net.diffusion_model.profile_ranges(evaluations=2) if a.range_profile is not None else contextlib.nullcontext()
     with profiling as prof:
         frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
-                                        denoiser=denoiser_config(a.prediction))
+                                        denoiser=denoiser_config(a.prediction), output="uint8" if a.u8 else "float")
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
-    print(f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.steps} steps + decode of {T} frames {tuple(frames.shape)}: {dt:.2f} s "
-          f"(range {frames.min().item():.2f} .. {frames.max().item():.2f}, finite={bool(torch.isfinite(frames).all())})")
+    what = f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.steps} steps + decode of {T} frames {tuple(frames.shape)}"
+    if a.u8:
+        print(f"{what}: {dt:.2f} s (uint8, range {frames.min().item()} .. {frames.max().item()})")
+    else:
+        print(f"{what}: {dt:.2f} s "
+              f"(range {frames.min().item():.2f} .. {frames.max().item():.2f}, finite={bool(torch.isfinite(frames).all())})")
     if prof is not None:
         print_range_profile(prof, net.diffusion_model, a.range_profile)
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
-    checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=frames.shape[-1] // 6)
-    checkpoint.save_gif(frames[:, :, ::4, ::4], str(out / "panorama_quarter.gif"))
+    width = frames.shape[2] if a.u8 else frames.shape[-1]
+    checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=width // 6)
+    checkpoint.save_gif(frames[:, ::4, ::4] if a.u8 else frames[:, :, ::4, ::4], str(out / "panorama_quarter.gif"))
     print("wrote", out)
 
 
