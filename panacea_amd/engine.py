@@ -24,7 +24,7 @@ import dataclasses
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, NamedTuple, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -306,6 +306,10 @@ class Runtime:
         t = whole[:shape[0]]
         t._pnc_tail = whole
         return t
+
+    def band_tail_rows(self, F: int, H: int) -> int:
+        """`tail_rows` of a 3x3 conv's operand: room for a view band's two neighbour columns (ViewShard.band_operand)"""
+        return 2 * F * H if self.vshard is not None else 0
 
     def zeros(self, shape, dtype) -> torch.Tensor:
         return torch.zeros(shape, device=self.device, dtype=dtype)
@@ -735,6 +739,32 @@ def gn_temporal_sharded(rt: Runtime, sh: "FrameShard", x32: torch.Tensor, N: int
     rt.be.groupnorm_temporal_part(x32, B, Tl, N, C, gamma, beta, eps, stats, 2, rt.T, y.hi, y.lo, 1)
     sh.halo_frames(y.planes(), B, Tl)
     return y
+
+
+class TemporalLayout(NamedTuple):
+    """Where the T frames of a pixel are when a ResBlock3D temporal site (per pixel: GroupNorm over (C/32, T) + conv1d over T) runs on
+    the fp32 stream h [F*N, C] of the frame layout: all that the layouts differ in (nn.openaimodel.ResBlock3D._temporal_site)"""
+    emb_all: bool         # the epilogue's per-frame rows are those of ALL B*T frames (rt.emb_all): the batched EmbProjector is not read
+    operand: Callable     # (rt, started, N, C, gamma, beta, eps) -> (h in the conv's layout, the conv's normalised Operand)
+    tconv: Callable       # (rt, C, N) -> the conv's geometry: B * T * Npix rows, Npix of them per row of the row bias
+    start: Callable = lambda rt, h, N: h    # -> h on its way to the conv's layout (`started`): what is enqueued before `operand` runs under the transfer
+    # (rt, h in the conv's layout, N) -> h; None: the conv's rows ARE the frame layout's and its epilogue takes the skip path, fp16 output, gn_records
+    home: Optional[Callable] = None
+
+
+# all T frames are this rank's: the site runs on h as it lies
+RESIDENT = TemporalLayout(False, lambda rt, h, *gn: (h, gn_temporal(rt, h, *gn)), lambda rt, C, N: dict(C=C, T=rt.T, Npix=N))
+# FrameShard(resblock="halo"): h stays; the GroupNorm's sums are added over the frame group, the operand gets ONE frame per neighbour rank
+HALO = TemporalLayout(False, lambda rt, h, *gn: (h, gn_temporal_sharded(rt, rt.shard, h, *gn)),
+                      lambda rt, C, N: dict(C=C, T=rt.T_local, Npix=N, halo=1))
+# FrameShard(resblock="transpose"): h goes to the pixel sharding (all T frames of N / G pixels) and back
+TRANSPOSE = TemporalLayout(True, lambda rt, pend, N, *gn: (hp := pend.result(), gn_temporal(rt, hp, N // rt.shard.G, *gn)),
+                           lambda rt, C, N: dict(C=C, T=rt.T, Npix=N // rt.shard.G),
+                           lambda rt, h, N: rt.shard.to_pixels_start(h, rt.B, N), lambda rt, hp, N: rt.shard.to_frames(hp, rt.B, N))
+
+
+def temporal_layout(rt: Runtime) -> TemporalLayout:
+    return RESIDENT if rt.shard is None else HALO if rt.shard.resblock == "halo" else TRANSPOSE
 
 
 def layer_norm(rt: Runtime, x32: torch.Tensor, M: int, C: int, gamma, beta) -> Operand:

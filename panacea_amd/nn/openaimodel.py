@@ -205,92 +205,62 @@ class ResBlock3D(TimestepBlock, Packable):
             pk["ws"], pk["bs"] = E.pk_linear(self.skip_connection.weight, lo), f32(self.skip_connection.bias)
         return pk
 
-    def _emb_out(self, rt: Runtime, emb32: torch.Tensor, pk, F: int, Co: int) -> torch.Tensor:
-        """emb_layers(emb) of this block, [F, Co] fp32: the network's EmbProjector computed it for every block in one launch
-        (same values), or — a block run on its own — its own launch"""
+    def _emb_out(self, rt: Runtime, lay: E.TemporalLayout, emb32: torch.Tensor, pk, Co: int) -> torch.Tensor:
+        """emb_layers(emb) of this block, fp32, one row per frame that the layout's conv sees: the network's EmbProjector computed
+        it for every block in one launch (same values), or — a block run on its own, or on the rows of all frames — its own launch"""
+        emb = rt.emb_all if lay.emb_all else emb32
         out = rt.emb_proj.get(id(self))
-        if out is not None and out.shape == (F, Co):
+        if out is not None and out.shape == (emb.shape[0], Co):
             return out
-        return E.small_linear(rt, emb32, pk, "we", "be", F, Co, self.emb_channels)
+        return E.small_linear(rt, emb, pk, "we", "be", emb.shape[0], Co, self.emb_channels)
+
+    def _temporal_site(self, rt: Runtime, lay: E.TemporalLayout, sent, F: int, N: int, gamma, beta, w, bias, rows=None, res2=None,
+                       o16=None, want_stats: bool = False):
+        """One temporal site: h + conv1d_t(SiLU(GN_t(h))) + what the epilogue adds, written over the fp32 stream h [F*N, Co] of the
+        frame layout.  `sent` = lay.start(rt, h, N), h on its way to the conv's layout: what the caller enqueued since then runs under
+        that transfer.  gamma .. bias: the site's keys in the packed parameters.  Site 1 adds the per-frame `rows` (rowbias); site 2
+        adds the skip path `res2` and writes the fp16 operand `o16` of the sum.  -> (h, its GroupNorm records (E.gn_records) or None)"""
+        pk, Co = self.packed(), self.out_channels
+        tconv = lay.tconv(rt, Co, N)
+        at_home = lay.home is None      # the conv's rows are the frame layout's: its epilogue takes the skip path, o16 and the records
+        epi = dict(res2=res2, ldr2=Co, ldc16=Co) if at_home else {}      # (away from home the skip path is added after the way back)
+        if rows is not None:
+            epi = dict(rowbias=rows, rb_rows=tconv["Npix"], rb_mod=rows.shape[0])
+        # the normalised operand; the conv GEMM, which adds into the stream in place (res1 = out32 = h); back to the frame layout
+        h, t = lay.operand(rt, sent, N, Co, pk[gamma], pk[beta], 1e-5)
+        part = E.gn_records(rt, F, N) if want_stats and at_home else None
+        E.gemm(rt, t, pk, w, o16 if at_home else None, M=rt.B * tconv["T"] * tconv["Npix"], N=Co, K=3 * Co, a_mode=E._hip.A_CONV1D_T,
+               tconv=tconv, bias=pk[bias], res1=h, ldr1=Co, out32=h, ldc32=Co, gn_part=part, **epi)
+        if not at_home:
+            h = lay.home(rt, h, N)
+            if res2 is not None:        # the skip path stayed in the frame layout
+                rt.be.add_f32(h, res2, F * N * Co, h, *(o16 or (None, None)))
+        return h, part
 
     def _run(self, rt: Runtime, x: Act, emb32: torch.Tensor, want_f16: bool = False, want_stats: bool = False) -> Act:
         if rt.T != self.num_frames:
             raise ValueError(f"runtime has {rt.T} frames per sample, block was built for {self.num_frames}")
-        pk = self.packed()
         F, H, W, N, M = x.F, x.H, x.W, x.N, x.M
-        Cin, Co = self.channels, self.out_channels
-        hip = E._hip
-        sh = rt.shard
-        # The two temporal sites (GroupNorm over (C/32, T) of one pixel + conv1d over its T frames) see all T frames of
-        # a pixel.  Frame-sharded runs (engine.FrameShard) execute them in the pixel-sharded layout: Mt rows of Nt pixels.
-        Nt = N // sh.G if sh is not None else N
-        Mt = rt.B * rt.T * Nt
-        tconv = dict(C=Co, T=rt.T, Npix=Nt)
+        pk, Cin, Co = self.packed(), self.channels, self.out_channels
+        lay = E.temporal_layout(rt)     # where the T frames of a pixel are: the two temporal sites see all of them
+        tail = rt.band_tail_rows(F, H)
         # in_layers: GN + SiLU + conv3x3
-        tail = 2 * F * x.H if rt.vshard is not None else 0      # room for a view band's neighbour columns (run_conv3x3)
         a = E.gn_spatial(rt, x.f32, F, N, Cin, pk["g1"], pk["b1"], 1e-5, True, split="gn_res", tail_rows=tail, part=x.gn_part)
         h = run_conv3x3(rt, a, F, H, W, Cin, pk, "w1", Co, pk["c1"]).f32
-        # h = h + conv1d_t(SiLU(GN_t(h))) + emb_layers(emb)[frame]      (:505-531)
-        # emb32 arrives as SiLU(emb): the activation of `emb_layers` is applied ONCE per network evaluation by
-        # _time_embedding (32 ResBlocks x 16 x 1280 identical SiLUs otherwise), the Linear runs here
-        s = None
-        halo = sh is not None and sh.resblock == "halo"
-        if halo:
-            # Round 4: the site stays in the FRAME layout.  The temporal GroupNorm's per-(pixel, group) sums are added over the frame
-            # group (256 B per pixel), the normalised fp16 operand gets ONE halo frame from each neighbour rank, and the temporal
-            # conv reads the (T_local + 2)-frame layout (PncGemmParams.t_halo); the fp32 stream h never leaves the rank.
-            emb_out = self._emb_out(rt, emb32, pk, F, Co)
-            t = E.gn_temporal_sharded(rt, sh, h, N, Co, pk["gt1"], pk["bt1"], 1e-5)
-            tch = dict(C=Co, T=rt.T_local, Npix=N, halo=1)
-            part1 = E.gn_records(rt, F, N)
-            E.gemm(rt, t, pk, "wt1", M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tch, bias=pk["ct1"],
-                   rowbias=emb_out, rb_rows=N, rb_mod=F, res1=h, ldr1=Co, out32=h, ldc32=Co, gn_part=part1)
-        elif sh is not None:
-            # (round 2's form, FrameShard(resblock="transpose"): the fp32 stream to the pixel sharding and back)
-            # the exchange runs on the communicator's stream; what this site computes independently of it — the timestep
-            # embedding's linear and the skip path — is enqueued under the transfer
-            pend = sh.to_pixels_start(h, rt.B, N)
-            emb_out = E.small_linear(rt, rt.emb_all, pk, "we", "be", rt.B * rt.T, Co, self.emb_channels)
-            s = self._skip(rt, x, pk)
-            h = pend.result()
-        else:
-            emb_out = self._emb_out(rt, emb32, pk, F, Co)
-        if not halo:
-            t = E.gn_temporal(rt, h, Nt, Co, pk["gt1"], pk["bt1"], 1e-5)
-            # the GroupNorm of out_layers reads what this conv writes: its statistics come out of the conv's epilogue (frame layout only)
-            part1 = E.gn_records(rt, F, N) if sh is None else None
-            E.gemm(rt, t, pk, "wt1", M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct1"],
-                   rowbias=emb_out, rb_rows=Nt, rb_mod=rt.B * rt.T, res1=h, ldr1=Co, out32=h, ldc32=Co, gn_part=part1)
-            if sh is not None:
-                h = sh.to_frames(h, rt.B, N)
+        # h = h + conv1d_t(SiLU(GN_t(h))) + emb_layers(emb)[frame]      (:505-531).  h is sent off first: what does not depend on it —
+        # emb_layers' rows (emb32 arrives as SiLU(emb), applied ONCE per network evaluation by _time_embedding) and, where h travels
+        # (on the communicator's stream), the skip path — is enqueued under the transfer.  want_stats: out_layers' GroupNorm reads the result
+        sent = lay.start(rt, h, N)
+        rows = self._emb_out(rt, lay, emb32, pk, Co)
+        s = self._skip(rt, x, pk) if lay.home is not None else None
+        h, part1 = self._temporal_site(rt, lay, sent, F, N, "gt1", "bt1", "wt1", "ct1", rows=rows, want_stats=True)
         # out_layers: GN + SiLU + conv3x3
         a = E.gn_spatial(rt, h, F, N, Co, pk["g2"], pk["b2"], 1e-5, True, split="gn_res", tail_rows=tail, part=part1)
         g = run_conv3x3(rt, a, F, H, W, Co, pk, "w2", Co, pk["c2"]).f32
-        # skip path
-        if s is None:
-            s = self._skip(rt, x, pk)
-        # return skip(x) + (g + conv1d_t(SiLU(GN_t(g))))                 (:533-542)
+        s = self._skip(rt, x, pk) if s is None else s
+        # return skip(x) + (g + conv1d_t(SiLU(GN_t(g))))                 (:533-542); `want_stats`: for the GroupNorm the next layer starts with
         o16 = rt.operand((M, Co), "stream") if want_f16 else None
-        part2 = None
-        if sh is None or halo:
-            if halo:
-                t = E.gn_temporal_sharded(rt, sh, g, N, Co, pk["gt2"], pk["bt2"], 1e-5)
-                tc2 = dict(C=Co, T=rt.T_local, Npix=N, halo=1)
-            else:
-                t = E.gn_temporal(rt, g, N, Co, pk["gt2"], pk["bt2"], 1e-5)
-                tc2 = tconv
-            # ... and so do the statistics of the block's output, for the GroupNorm the next layer starts with
-            part2 = E.gn_records(rt, F, N) if want_stats else None
-            E.gemm(rt, t, pk, "wt2", o16, M=M, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tc2, bias=pk["ct2"],
-                   res1=g, ldr1=Co, res2=s, ldr2=Co, out32=g, ldc32=Co, ldc16=Co, gn_part=part2)
-        else:
-            # the skip path stays in the frame layout: g + conv1d in the pixel layout, exchange back, then + skip
-            gp = sh.to_pixels(g, rt.B, N)
-            t = E.gn_temporal(rt, gp, Nt, Co, pk["gt2"], pk["bt2"], 1e-5)
-            E.gemm(rt, t, pk, "wt2", M=Mt, N=Co, K=3 * Co, a_mode=hip.A_CONV1D_T, tconv=tconv, bias=pk["ct2"],
-                   res1=gp, ldr1=Co, out32=gp, ldc32=Co)
-            g = sh.to_frames(gp, rt.B, N)
-            rt.be.add_f32(g, s, M * Co, g, *(o16 or (None, None)))
+        g, part2 = self._temporal_site(rt, lay, lay.start(rt, g, N), F, N, "gt2", "bt2", "wt2", "ct2", res2=s, o16=o16, want_stats=want_stats)
         return Act(F, H, W, Co, f32=g, f16=o16, gn_part=part2)
 
     def _skip(self, rt: Runtime, x: Act, pk: dict) -> torch.Tensor:
@@ -758,9 +728,9 @@ class UNetModel3D(nn.Module, Packable):
         tp.run(rt)
 
     def _project_emb(self, rt: Runtime, emb32: torch.Tensor):
-        """emb_layers(emb) of every ResBlock3D of this network in one launch (EmbProjector); not in the round-2 frame sharding,
-        whose sites read the rows of ALL frames (rt.emb_all)"""
-        if (rt.shard is not None and rt.shard.resblock != "halo") or not E.EMB_BATCH:
+        """emb_layers(emb) of every ResBlock3D of this network in one launch (EmbProjector); not in a layout whose temporal sites
+        read the rows of ALL frames (rt.emb_all)"""
+        if E.temporal_layout(rt).emb_all or not E.EMB_BATCH:
             return
         ep = self.__dict__.get("_emb_proj")
         if ep is None:
@@ -797,8 +767,7 @@ class UNetModel3D(nn.Module, Packable):
         """self.out: GN + SiLU + conv3x3 -> NCHW fp32 (:1245-1253, controlmodel.py:197-202); `tokens`: the channels-last
         fp32 tokens instead (consumed by the fused sampler-step exit, pnc_cfg_euler_step)."""
         pk = self.packed()
-        a = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, pk["og"], pk["ob"], 1e-5, True, split="gn_head",
-                         tail_rows=2 * h.F * h.H if rt.vshard is not None else 0)
+        a = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, pk["og"], pk["ob"], 1e-5, True, split="gn_head", tail_rows=rt.band_tail_rows(h.F, h.H))
         o = run_conv3x3(rt, a, h.F, h.H, h.W, h.C, pk, "ow", self.out_channels, pk["oc"])
         if tokens:
             return o
