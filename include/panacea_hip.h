@@ -576,7 +576,11 @@ int pnc_operand_stats_f16(const void* hi, const void* lo, int lo_fmt, int64_t ro
  *    matrix, p[m][:] = softmax(scale * s[m][:]) (fp32 in, fp32 statistics, fp16
  *    out), N % 4 == 0.  A row is kept in registers: N <= 16384 is THIS kernel's limit, not the attention block's (section 6
  *    serves longer frames).  Columns >= n_valid (n_valid <= 0: N) are masked; causal != 0 also masks columns
- *    j > m (row m = query m of ONE sequence: the OpenCLIP text tower's attn_mask, sgm/modules/encoders/modules.py:608).  For frames
+ *    j > m (row m = query m of ONE sequence: the OpenCLIP text tower's attn_mask, sgm/modules/encoders/modules.py:608).
+ *    The masks are predicates, for every scale >= 0 (0 and denormal-small ones included: the visible columns are then uniform): a
+ *    masked column receives +0 and takes no part in the row sum; its score may hold anything, NaN and +-Inf included, and does not
+ *    influence the output by one bit.  Every column j < N of every row m < M of p is written (a row m >= N under a causal mask sees
+ *    all n_valid columns); columns N .. lds - 1 of s are never read, columns N .. ldp - 1 of p never written.  For frames
  *    of up to 16384 tokens the single-head d = 512 attention of the VAE
  *    mid block runs as  S = Q K^T (pnc_gemm_f16, fp32 out) -> this -> O = P V
  *    (pnc_gemm_f16 against the channel-major V^T).

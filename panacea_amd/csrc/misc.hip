@@ -555,7 +555,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
         if (c < nv) {
             v[j] = *reinterpret_cast<const f32x4*>(row + c * 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[j][e] = (c * 4 + e < lim) ? v[j][e] : -3.0e38f;      // masked: exp2 -> 0
+            for (int e = 0; e < 4; ++e) v[j][e] = (c * 4 + e < lim) ? v[j][e] : -3.0e38f;      // masked: out of the maximum
             m = fmaxf(fmaxf(fmaxf(v[j][0], v[j][1]), fmaxf(v[j][2], v[j][3])), m);
         }
     }
@@ -572,7 +572,14 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
         const int c = tid + j * 256;
         if (c < nv) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { v[j][e] = __builtin_amdgcn_exp2f(fmaf(v[j][e], sc, -off)); sum += v[j][e]; }
+            for (int e = 0; e < 4; ++e) {
+                // the mask is a predicate: exp2 of the -3.0e38 stand-in is 0 only while 3e38 * sc is huge, and at scale = 0 (or a
+                // tiny one) fmaf(-3e38, sc, -off) is 0 or small.  A masked element adds +0 to the sum and stores +0, whatever the scale;
+                // a visible one is computed as before, so unmasked launches keep their bits
+                const float pe = __builtin_amdgcn_exp2f(fmaf(v[j][e], sc, -off));
+                v[j][e] = (c * 4 + e < lim) ? pe : 0.0f;
+                sum += v[j][e];
+            }
         }
     }
     sum = wave_sum(sum);

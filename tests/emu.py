@@ -401,12 +401,16 @@ def attn_temporal_split_exact(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, *, B, T,
 
 
 def softmax_rows(s32, lds, M, N, scale, p16, ldp, causal=False, n_valid=0):
-    sc = _mat(s32, M, N, lds).float() * scale
-    col, row = torch.arange(N, device=sc.device)[None, :], torch.arange(M, device=sc.device)[:, None]
-    keep = col < (n_valid or N)
+    """The masks are predicates (a masked score is never a value: it may be NaN), and the row maximum is subtracted BEFORE the scaling,
+    as the kernel's fma(s, sc, -max * sc) does in effect: scale * s rounded on its own loses |scale * s| 2^-24 of every exponent, which on
+    scores with a large common offset (+1e4) is more than half the allowance of tests/misc_ref64.py, softmax_rows."""
+    S = _mat(s32, M, N, lds).float()
+    col, row = torch.arange(N, device=S.device)[None, :], torch.arange(M, device=S.device)[:, None]
+    keep = col < (n_valid if n_valid > 0 else N)
     if causal:
         keep = keep & (col <= row)
-    pr = torch.softmax(sc.masked_fill(~keep, float("-inf")), dim=-1)
+    mx = S.masked_fill(~keep, float("-inf")).amax(dim=-1, keepdim=True)
+    pr = torch.softmax(((S - mx) * scale).masked_fill(~keep, float("-inf")), dim=-1)
     _mat(p16, M, N, ldp).copy_(r16(pr, 'softmax_rows'))
 
 
@@ -532,7 +536,9 @@ def linear_smallm_segments(a32, lda, w16, bias, out32, M, m0, Mtot, N, K, seg_st
 def timestep_embedding(t_i64, F, dim, freqs, out32):
     args = t_i64.reshape(-1)[:F, None].float() * freqs.reshape(-1)[None, : dim // 2]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
-    out32.reshape(-1)[: F * dim].view(F, dim)[:, : 2 * (dim // 2)].copy_(emb)
+    o = out32.reshape(-1)[: F * dim].view(F, dim)
+    o[:, : 2 * (dim // 2)].copy_(emb)
+    o[:, 2 * (dim // 2):] = 0.0                     # the zero column of an odd dim, which the kernel writes
 
 
 def timestep_embedding_f32(t_f32, F, dim, freqs, out32):
