@@ -14,6 +14,8 @@ float path as before.
 """
 from __future__ import annotations
 
+import operator
+from dataclasses import dataclass
 from typing import Dict, Tuple
 
 import numpy as np
@@ -63,6 +65,54 @@ def frames_u8(x: torch.Tensor, what: str) -> torch.Tensor:
     if x.dim() != 4:
         raise ValueError(f"{what}: uint8 frames are (F, H, W, C) channels-last, got {tuple(x.shape)}")
     return x.detach().contiguous()
+
+
+@dataclass(frozen=True, eq=False)
+class SparseClip:
+    """A conditioning clip of `num_frames` frames of which only K are given: `frames_u8` (K, H, W, 3) uint8 channels-last sit at
+    `slots` (K distinct indices in [0, num_frames), negative ones counted from the end), every other slot is the blank frame — float
+    0.0 after the dataset's scaling, which no byte scales to.  This is `final_cond_zero` (nuscenes_datasets_video.py:559-566) with
+    K = 1: the anchor in the last (use_last_frame) or first slot of an all-zero clip.  `slots` is kept as a tuple of non-negative
+    indices."""
+    frames_u8: torch.Tensor
+    slots: Tuple[int, ...]
+    num_frames: int
+
+    def __post_init__(self):
+        x = self.frames_u8
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"SparseClip: frames_u8 is a uint8 tensor, got {type(x).__name__}")
+        if x.dtype != torch.uint8:
+            raise TypeError(f"SparseClip: uint8 channels-last frames expected, got {x.dtype}")
+        if x.dim() != 4 or 0 in x.shape[1:]:
+            raise ValueError(f"SparseClip: frames_u8 is (K, H, W, C) channels-last, got {tuple(x.shape)}")
+        T = self.num_frames
+        if isinstance(T, bool) or not isinstance(T, int):
+            raise TypeError(f"SparseClip: num_frames is an int, got {type(T).__name__}")
+        if T < 1:
+            raise ValueError(f"SparseClip: num_frames >= 1, got {T}")
+        try:
+            slots = tuple(operator.index(s) for s in self.slots)
+        except TypeError:
+            raise TypeError(f"SparseClip: slots are integers, got {self.slots!r}") from None
+        if len(slots) != x.shape[0]:
+            raise ValueError(f"SparseClip: {x.shape[0]} frames for {len(slots)} slots")
+        if any(not -T <= s < T for s in slots):
+            raise ValueError(f"SparseClip: slots {slots} outside a clip of {T} frames")
+        slots = tuple(s % T for s in slots)
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"SparseClip: slots {slots} name a frame twice")
+        object.__setattr__(self, "frames_u8", x.detach().contiguous())
+        object.__setattr__(self, "slots", slots)
+
+    def gather_index(self) -> torch.Tensor:
+        """(num_frames,) int64 on the frames' device: for every slot of the clip, the row of [the K given frames, the blank frame]
+        that fills it"""
+        K = len(self.slots)
+        idx = [K] * self.num_frames
+        for j, s in enumerate(self.slots):
+            idx[s] = j
+        return torch.tensor(idx, dtype=torch.int64, device=self.frames_u8.device)
 
 
 def u8_to_tokens(rt: Runtime, x_u8: torch.Tensor, kind: str, Cpad: int, out: Operand):

@@ -476,8 +476,36 @@ class FirstStageEncoder(nn.Module, Packable):
             image.u8_to_tokens(rt, x_u8, table, ic, E.Operand(x16))
             return self._moments_of_tokens(rt, x16, F, H, W)
 
+    def moments_sparse_u8(self, clip: "image.SparseClip", table: str = "image") -> torch.Tensor:
+        """`moments` of the clip `clip` stands for — its K uint8 frames at their slots, float 0.0 frames everywhere else — from ONE
+        encoder run over K + 1 frames instead of `num_frames`: the K given frames enter like `moments_u8`'s, the blank frame is an
+        all-zero token plane (the bits nchw_to_tokens_f16 writes for a float-zero frame), and since every layer of the encoder acts on
+        each frame by itself, the blank frame's moments are those of every blank slot.  K = 0 gives an all-blank clip, K = num_frames
+        runs no blank frame.  Returns (num_frames, 2C, h, w) fp32."""
+        if not isinstance(clip, image.SparseClip):
+            raise TypeError(f"moments_sparse_u8: an image.SparseClip expected, got {type(clip).__name__}")
+        with torch.no_grad():
+            x_u8 = clip.frames_u8
+            K, H, W, C = x_u8.shape
+            if C != self.encoder.in_channels:
+                raise ValueError(f"moments_sparse_u8: frames of {C} channels for an encoder of {self.encoder.in_channels}")
+            image.table(table)                                     # (an unknown kind is refused here)
+            F = K + (1 if K < clip.num_frames else 0)
+            rt = Runtime(x_u8.device, F, 1)
+            image.capability(rt.be, "u8_to_tokens_f16")
+            ic = self.encoder.packed()["ic"]
+            x16 = (rt.zeros if F > K else rt.empty)((F * H * W, ic), torch.float16)
+            if K:
+                image.u8_to_tokens(rt, x_u8, table, ic, E.Operand(x16[: K * H * W]))
+            return self._moments_of_tokens(rt, x16, F, H, W).index_select(0, clip.gather_index())
+
     def encode(self, x: torch.Tensor, generator=None, sample: bool = True) -> torch.Tensor:
         return self._posterior(self.moments(x), generator, sample)
+
+    def encode_sparse_u8(self, clip: "image.SparseClip", generator=None, sample: bool = True, table: str = "image") -> torch.Tensor:
+        """`encode` of a sparse clip (see moments_sparse_u8): the posterior of the full (num_frames, 2C, h, w) moments, so a generator
+        state gives the draw that encoding the dense clip gives — one randn of (num_frames, C, h, w)"""
+        return self._posterior(self.moments_sparse_u8(clip, table), generator, sample)
 
     def encode_u8(self, x_u8: torch.Tensor, generator=None, sample: bool = True, table: str = "image") -> torch.Tensor:
         """`encode` of uint8 channels-last frames (see moments_u8): the same posterior, the same draw for the same generator state"""

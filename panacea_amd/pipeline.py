@@ -6,16 +6,38 @@
 which is what `DiffusionEngine3D.sample` + `decode_first_stage` do around the network (diffusion.py:138-151, 242-249;
 `scale_factor` 0.18215, inference_nuscenes.yaml:5).  The text / image conditioners are not part of it:
 `cond` and `uc` arrive as tensors.
+
+`rollout_frames` chains such windows into a video of any length by conditioning, on one device: the `concat` of window k is the
+first-stage encoding of a `final_cond_zero` clip (image.SparseClip) around an anchor frame, and the anchor of window k + 1 is a frame
+window k decoded.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import engine, image, sampling
 
 SCALE_FACTOR = 0.18215
+
+
+def _sampler_stack(dev, num_steps: int, cfg_scale: float, sampler, denoiser):
+    """(sampler, denoiser) on `dev` from the `sampler` / `denoiser` arguments of sample_frames and rollout_frames"""
+    if denoiser is None:
+        den = sampling.DiscreteDenoiser()
+    else:
+        den = sampling.denoiser_from_config(denoiser) if isinstance(denoiser, dict) else denoiser
+        if not isinstance(den, sampling.Denoiser):
+            raise TypeError(f"denoiser: a panacea_amd.sampling denoiser mirror or a denoiser_config dict (got {type(den).__name__})")
+    den = den.to(dev)
+    if sampler is None:
+        smp = sampling.EulerEDMSampler(num_steps, guider=sampling.VanillaCFG(cfg_scale), device=dev)
+    else:
+        smp = sampling.from_config(sampler, device=dev) if isinstance(sampler, dict) else sampler
+        if smp.num_steps is None:
+            smp.num_steps = num_steps
+    return smp, den
 
 
 def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[str, torch.Tensor],
@@ -38,20 +60,79 @@ def sample_frames(network, first_stage, cond: Dict[str, torch.Tensor], uc: Dict[
         if not hasattr(first_stage, "decode_u8"):
             raise TypeError(f"output='uint8' needs a first stage with decode_u8; {type(first_stage).__name__} has none")
         image.capability(engine.backend(), "tokens_to_u8")
-    dev = noise.device
-    if denoiser is None:
-        den = sampling.DiscreteDenoiser()
-    else:
-        den = sampling.denoiser_from_config(denoiser) if isinstance(denoiser, dict) else denoiser
-        if not isinstance(den, sampling.Denoiser):
-            raise TypeError(f"denoiser: a panacea_amd.sampling denoiser mirror or a denoiser_config dict (got {type(den).__name__})")
-    den = den.to(dev)
-    if sampler is None:
-        smp = sampling.EulerEDMSampler(num_steps, guider=sampling.VanillaCFG(cfg_scale), device=dev)
-    else:
-        smp = sampling.from_config(sampler, device=dev) if isinstance(sampler, dict) else sampler
-        if smp.num_steps is None:
-            smp.num_steps = num_steps
+    smp, den = _sampler_stack(noise.device, num_steps, cfg_scale, sampler, denoiser)
     with torch.no_grad():
         z = smp(sampling.BoundDenoiser(den, network), noise, cond, uc, network=network if hoist else None)
         return first_stage.decode_u8(z / scale_factor) if output == "uint8" else first_stage.decode(z / scale_factor)
+
+
+def rollout_frames(network, first_stage_dec, first_stage_enc, anchor_u8: torch.Tensor, windows: Sequence[Tuple[Dict, Dict]],
+                   noise: torch.Tensor, *, anchor: str = "last", share_noise_level: float = 0.07, sample_posterior: bool = True,
+                   generator=None, num_steps: int = 25, cfg_scale: float = 5.0, hoist: bool = True,
+                   scale_factor: float = SCALE_FACTOR, sampler=None, denoiser=None) -> torch.Tensor:
+    """A video of W windows of T frames chained on one device by conditioning, the way the model reaches past one clip: window k
+    is sampled with `concat` = the first-stage latents of a `final_cond_zero` clip (nuscenes_datasets_video.py:559-566) whose one
+    given frame, the anchor, is `anchor_u8` for window 0 and a frame window k-1 generated for every later one.  Returns
+    (N, H, W, 3) uint8 frames on the device in temporal order, N = T + (W - 1)(T - 1).
+
+    anchor_u8: (H, W, 3) uint8.  windows: W pairs (cond, uc) as sample_frames takes them but WITHOUT `concat` (`cond_feat` float
+    NCHW or the uint8 layout).  noise: (W, T, 4, h, w) unit-variance latents; T has to be the network's `num_frames`.
+    anchor: "last" puts the anchor in slot T-1 (inference.py --use_last_frame, the reference's default), "first" in slot 0.
+
+    Window k: c["concat"] and uc["concat"] each come from their own pass of image.SparseClip(anchor_k[None], [slot], T) through
+    `scale_factor * first_stage_enc.encode_sparse_u8` — what VAEEmbedder does, twice, as get_unconditional_conditioning runs the
+    conditioner twice: with `sample_posterior` two posterior draws from `generator`, c before uc; without, twice the posterior mean.
+    The start latent is sampling.share_noise_init(noise[k], c["concat"], share_noise_level) (diffusion.py:242-249: `concat[-1]`
+    whatever the anchor's slot).  The window is sampled and decoded by `first_stage_dec.decode_u8`, and the frame at the far end
+    from the anchor — slot 0 for "last", slot T-1 for "first" — is anchor k+1, a slice of the decoded frames on the device.
+
+    From window 1 on the anchor's slot depicts a frame that was already emitted and is dropped.  With "last" window k+1 lies BEFORE
+    window k in time, so the result is [w_{W-1}[:-1], ..., w_1[:-1], w_0]; with "first" it is [w_0, w_1[1:], ...].  The layouts
+    and text of the windows have to overlap by one frame in the same way: that is the caller's to arrange.
+
+    Refused before the first launch: first stages without decode_u8 / encode_sparse_u8 (TypeError), a backend without the
+    image-boundary kernels (NotImplementedError), a network carrying a frame or view shard (NotImplementedError: one device),
+    T != num_frames and a malformed anchor, `noise` or window (ValueError).  Other arguments: see sample_frames."""
+    if anchor not in ("last", "first"):
+        raise ValueError(f"anchor: 'last' or 'first', got {anchor!r}")
+    if not hasattr(first_stage_dec, "decode_u8"):
+        raise TypeError(f"rollout_frames needs a first stage with decode_u8; {type(first_stage_dec).__name__} has none")
+    if not hasattr(first_stage_enc, "encode_sparse_u8"):
+        raise TypeError(f"rollout_frames needs a first stage with encode_sparse_u8; {type(first_stage_enc).__name__} has none")
+    for name in ("tokens_to_u8", "u8_to_tokens_f16"):
+        image.capability(engine.backend(), name)
+    model = network.diffusion_model
+    for m in (model, getattr(model, "controlnet", None)):
+        if getattr(m, "frame_shard", None) is not None or getattr(m, "view_shard", None) is not None:
+            raise NotImplementedError("rollout_frames runs on one device: the network carries a frame or view shard")
+    windows = list(windows)
+    if not isinstance(noise, torch.Tensor) or noise.dim() != 5 or noise.shape[0] != len(windows) or not windows:
+        raise ValueError(f"noise: (W, T, 4, h, w) with one entry per window ({len(windows)}), got "
+                         f"{tuple(noise.shape) if isinstance(noise, torch.Tensor) else type(noise).__name__}")
+    T, (h, w) = noise.shape[1], noise.shape[3:]
+    if T != model.num_frames:
+        raise ValueError(f"noise carries {T} frames per window, the network was built for num_frames = {model.num_frames}")
+    if (not isinstance(anchor_u8, torch.Tensor) or anchor_u8.dtype != torch.uint8 or anchor_u8.dim() != 3 or anchor_u8.shape[2] != 3
+            or anchor_u8.shape[0] % h or anchor_u8.shape[1] % w or anchor_u8.shape[0] // h != anchor_u8.shape[1] // w):
+        raise ValueError(f"anchor_u8: one (H, W, 3) uint8 frame at a multiple of the {h} x {w} latent, got "
+                         f"{tuple(anchor_u8.shape) if isinstance(anchor_u8, torch.Tensor) else type(anchor_u8).__name__}"
+                         f"{' ' + str(anchor_u8.dtype) if isinstance(anchor_u8, torch.Tensor) else ''}")
+    for k, pair in enumerate(windows):
+        if len(pair) != 2 or not all(isinstance(d, dict) for d in pair):
+            raise ValueError(f"windows[{k}]: a (cond, uc) pair of dicts expected")
+        if any("concat" in d for d in pair):
+            raise ValueError(f"windows[{k}] carries `concat`: rollout_frames builds it from the window's anchor")
+    smp, den = _sampler_stack(noise.device, num_steps, cfg_scale, sampler, denoiser)
+    slot, far = (T - 1, 0) if anchor == "last" else (0, T - 1)
+    frame, out = anchor_u8.to(noise.device), []
+    with torch.no_grad():
+        for k, (cond, uc) in enumerate(windows):
+            clip = image.SparseClip(frame[None], (slot,), T)
+            c, u = (dict(d, concat=scale_factor * first_stage_enc.encode_sparse_u8(clip, generator=generator, sample=sample_posterior))
+                    for d in (cond, uc))
+            x0 = sampling.share_noise_init(noise[k], c["concat"], share_noise_level)
+            z = smp(sampling.BoundDenoiser(den, network), x0, c, u, network=network if hoist else None)
+            frames = first_stage_dec.decode_u8(z / scale_factor)
+            frame = frames[far]
+            out.append(frames if k == 0 else frames[:-1] if anchor == "last" else frames[1:])
+    return torch.cat(out[::-1] if anchor == "last" else out)

@@ -10,6 +10,8 @@ per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference'
     python tools/sample.py --prediction edm --discretization edm --sampler heun --steps 18
     python tools/sample.py --frames 16 --steps 5          (clips of 1 .. 16 frames; the default 8 is the released FrameLength)
     python tools/sample.py --u8 --steps 5                 (uint8 channels-last BEV layout in, uint8 frames out: panacea_amd.image)
+    python tools/sample.py --windows 4 --steps 5          (a video of 8 + 3 * 7 = 29 frames: windows chained on an anchor frame,
+                                                           pipeline.rollout_frames; `--anchor first` rolls forward in time)
 """
 import argparse, json, sys, time
 from pathlib import Path
@@ -83,7 +85,15 @@ def main():
     ap.add_argument("--u8", action="store_true",
                     help="the image boundary on the device: the synthetic BEV layout enters as uint8 channels-last bytes (scaled / 255 in "
                          "the hint stem's entry kernel) and the frames leave the decoder as uint8 (T, H, W, 3)")
+    ap.add_argument("--windows", type=int, default=0, metavar="N",
+                    help="roll out N windows of --frames frames chained by conditioning (pipeline.rollout_frames): a synthetic anchor "
+                         "frame, then each window anchored on the far-end frame of the one before; T + (N - 1)(T - 1) uint8 frames")
+    ap.add_argument("--anchor", choices=["last", "first"], default="last",
+                    help="--windows: the anchor's slot in the conditioning clip (last = the reference's --use_last_frame: the video "
+                         "grows backwards in time; first: forwards)")
     a = ap.parse_args()
+    if a.windows < 0:
+        ap.error("--windows takes N >= 1")
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
     net = build_network(kw)
@@ -117,11 +127,18 @@ def main():
     import contextlib
     profiling = net.diffusion_model.profile_ranges(evaluations=2) if a.range_profile is not None else contextlib.nullcontext()
     with profiling as prof:
-        frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
-                                        denoiser=denoiser_config(a.prediction), output="uint8" if a.u8 else "float")
+        if a.windows:
+            frames = rollout(a, net, fs, smp, g, dev)
+        else:
+            frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
+                                            denoiser=denoiser_config(a.prediction), output="uint8" if a.u8 else "float")
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    u8 = frames.dtype == torch.uint8
     what = f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.steps} steps + decode of {T} frames {tuple(frames.shape)}"
-    if a.u8:
+    if a.windows:
+        what = (f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.windows} windows of {T} frames, anchor {a.anchor}, "
+                f"{a.steps} steps each, {tuple(frames.shape)}")
+    if u8:
         print(f"{what}: {dt:.2f} s (uint8, range {frames.min().item()} .. {frames.max().item()})")
     else:
         print(f"{what}: {dt:.2f} s "
@@ -129,10 +146,39 @@ def main():
     if prof is not None:
         print_range_profile(prof, net.diffusion_model, a.range_profile)
     out = Path(a.out); out.mkdir(parents=True, exist_ok=True)
-    width = frames.shape[2] if a.u8 else frames.shape[-1]
+    width = frames.shape[2] if u8 else frames.shape[-1]
     checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=width // 6)
-    checkpoint.save_gif(frames[:, ::4, ::4] if a.u8 else frames[:, :, ::4, ::4], str(out / "panorama_quarter.gif"))
+    checkpoint.save_gif(frames[:, ::4, ::4] if u8 else frames[:, :, ::4, ::4], str(out / "panorama_quarter.gif"))
     print("wrote", out)
+
+
+def rollout(a, net, fs, smp, g, dev):
+    """--windows: a synthetic anchor frame and one (cond, uc) pair per window -> the video's uint8 frames.  Window k reads the layouts
+    of the video frames it covers (one synthetic layout per video frame, so neighbouring windows share the layout of the frame where
+    they meet); the first-stage encoder gets synthetic weights, or the checkpoint's `first_stage_model.*` like the decoder."""
+    T, W = a.frames, a.windows
+    N = T + (W - 1) * (T - 1)
+    enc = model.FirstStageEncoder(4, VAE)
+    if a.ckpt:
+        print(enc.load_state_dict(checkpoint.denoiser_state_dict(checkpoint.read_state_dict(a.ckpt), "first_stage_model."), strict=False))
+    else:
+        enc.load_state_dict(synth.synth_state_dict({k: list(v.shape) for k, v in enc.state_dict().items()}), strict=True)
+    enc = enc.to(dev)
+    _, _, h, w = configs.SHAPES["full"]
+    hint = g["cond_feat"][T:]                                                   # T synthetic layouts, cycled over the N video frames
+    layout = torch.stack([hint[i % T] for i in range(N)])
+    if a.u8:
+        layout = (layout * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    windows = []
+    for k in range(W):
+        first = (W - 1 - k) * (T - 1) if a.anchor == "last" else k * (T - 1)
+        lay = layout[first:first + T].contiguous()
+        windows.append(({"crossattn": g["crossattn"][1:2], "cond_feat": lay}, {"crossattn": g["crossattn"][0:1], "cond_feat": lay}))
+    gen = torch.Generator().manual_seed(a.seed)
+    noise = torch.randn(W, T, 4, h, w, generator=gen).to(dev)
+    anchor = torch.randint(0, 256, (8 * h, 8 * w, 3), generator=gen, dtype=torch.uint8).to(dev)
+    return pipeline.rollout_frames(net, fs, enc, anchor, windows, noise, anchor=a.anchor, num_steps=a.steps, sampler=smp,
+                                   denoiser=denoiser_config(a.prediction))
 
 
 if __name__ == "__main__":
