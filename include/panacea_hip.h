@@ -614,6 +614,33 @@ int pnc_attn_frame_f16(const void* q, int64_t ldq, const void* k, int64_t ldk,
                        void* o, int64_t ldo, int F, int N, int C, float scale, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * 6b. First-stage attention on SPLIT operands: the geometry of section 6 (F frames of N tokens, one head of dim C, one launch, online
+ *    softmax, no N x N matrix, no workspace) on the operands of the split attention kernels of section 2.  Additive under ABI 8.
+ *    Every operand x is an fp16 pair x = x_hi + 2^-11 x_lo (PncGemmParams.A_lo):
+ *        S = Qh.Kh + 2^-11 (Qh.Kl + Ql.Kh)                   the lo.lo products are dropped; fp32 accumulation
+ *        P = softmax(scale * S) per row, online;  P = Ph + 2^-11 Pl, an fp16 pair rounded against the running maximum
+ *        O = Ph.Vh + 2^-11 (Ph.Vl + Pl.Vh)                   normalised once at the end, written as o = fp16(O), o_lo = fp16((O - o) * 2^11)
+ *    q, k, v, o : fp16 token rows, hi planes; the row of (frame f, token i) is f*N + i, element c at [(f*N + i)*ld + c], c < C
+ *    q_lo .. o_lo : the lo planes, each with the layout and the leading dimension of its hi plane
+ *    V is ROW-major, laid out like K — what a QKV projection writes as out16 + out16_lo (the transposed out16t store of the GEMM has
+ *    no lo plane); the kernel transposes on its way to the MFMA.
+ *    Every token of a frame attends to all N tokens of the same frame and to nothing else.  The hi.hi and the cross products are
+ *    accumulated apart in fp32 and meet once, scaled by 2^-11; the running maximum and the row sum are fp32.
+ *    ONLY the named elements are read or written: row padding between C and ld (of either plane) and rows after the last frame may
+ *    hold anything (NaN included) and a buffer may end right after its last named element; the padding of o and o_lo is left as it
+ *    was.  Keys >= N of the last key tile are never loaded and are masked after the partial scores are added.  Deterministic: no
+ *    atomics, the same bits on every run.  o and o_lo must not overlap each other or any input.
+ *    Accepted: C in {128, 256, 512}; F >= 1; N >= 8, N % 8 == 0; F * ceil(N / 32) < 2^31; ldq, ldk, ldv, ldo >= C; anything else ->
+ *    PNC_EINVAL.  ldq, ldk, ldv, ldo multiples of 8 elements and all eight pointers 16-byte aligned, else PNC_EALIGN.  Checked in
+ *    this order: null pointers, ranges, leading dimensions, pointer alignment; nothing is launched on a refusal.
+ *     -> AttnBlock / MemoryEfficientAttnBlock.attention under the first stage's split policies
+ *        (sgm/modules/diffusionmodules/model.py:393-408, 444-472)
+ * ------------------------------------------------------------------------- */
+int pnc_attn_frame_split_f16(const void* q, const void* q_lo, int64_t ldq, const void* k, const void* k_lo, int64_t ldk,
+                             const void* v, const void* v_lo, int64_t ldv, void* o, void* o_lo, int64_t ldo,
+                             int F, int N, int C, float scale, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * 7. Image boundary: 8-bit channels-last frames in and out.  Additive under ABI 8.  Both entries
  *    launch on the caller's stream, allocate nothing and do not synchronise; nothing is launched on a refusal.
  *

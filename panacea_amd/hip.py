@@ -126,6 +126,7 @@ _SIGNATURES = {
     "pnc_softmax_rows_f16": (_I, [_P, _L, _I, _I, _F, _I, _I, _P, _L, _P]),
     "pnc_attn_temporal_f16": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "pnc_attn_frame_f16": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _F, _P]),
+    "pnc_attn_frame_split_f16": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _F, _P]),
     "pnc_groupnorm_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "pnc_groupnorm_apply": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _I, _P, _I, _I, _P]),
     "pnc_groupnorm_combine": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -508,6 +509,16 @@ def attn_frame(q, ldq, k, ldk, vt, ldvt, vt_fstride, o, ldo, *, F, N, C, scale):
     f16 = torch.float16
     _check(_timed("attn_frame", 4.0 * F * N * N * C, 0.0, load().pnc_attn_frame_f16, _ptr(q, f16, "q"), ldq, _ptr(k, f16, "k"), ldk,
                   _ptr(vt, f16, "vt"), ldvt, vt_fstride, _ptr(o, f16, "o"), ldo, F, N, C, scale, _stream()), "pnc_attn_frame_f16")
+
+
+def attn_frame_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, F, N, C, scale):
+    """pnc_attn_frame_split_f16: `attn_frame` on split operands (every *_lo an fp16 plane with its hi plane's leading dimension); V
+    is ROW-major, laid out like K; three MFMA products per product of the single-plane kernel (include/panacea_hip.h section 6b)"""
+    f16 = torch.float16
+    _check(_timed("attn_frame_split", 12.0 * F * N * N * C, 0.0, load().pnc_attn_frame_split_f16,
+                  _ptr(q, f16, "q"), _ptr(q_lo, f16, "q_lo"), ldq, _ptr(k, f16, "k"), _ptr(k_lo, f16, "k_lo"), ldk,
+                  _ptr(v, f16, "v"), _ptr(v_lo, f16, "v_lo"), ldv, _ptr(o, f16, "o"), _ptr(o_lo, f16, "o_lo"), ldo,
+                  F, N, C, scale, _stream()), "pnc_attn_frame_split_f16")
 
 
 def attn_temporal(q, ldq, k, ldk, v, ldv, o, ldo, *, B, T, Npix, heads, scale):

@@ -13,6 +13,13 @@ sub-tree of a checkpoint loads with `strict=False`; all arithmetic runs through 
   launch over all frames on the same q / k / V^T, no N x N matrix.
 
 The per-module `forward`s take/return NCHW tensors like the reference; `Decoder.forward` keeps everything resident.
+
+OPERAND POLICY.  `FirstStageDecoder` / `FirstStageEncoder` take `precision=` ("fast", the default: plain fp16 operands and weights;
+"precise-wide": every GEMM and attention operand an fp16 pair hi + 2^-11 lo; "precise-full": the weights split as well, for fp32
+checkpoints — the reference runs its first stage in fp32).  The policy is an attribute of every module of the tree
+(`set_precision`), each Runtime a module creates carries it (`rt.prec`), and the operands follow it: `rt.operand` allocates the lo
+planes, `engine.gemm` hands on A_lo / out16_lo and the weights' lo twins.  Under a split policy the mid-block attention is ONE
+pnc_attn_frame_split_f16 launch at every N on row-major q / k / v pairs (no V^T: the transposed store has no lo plane).
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .. import image
-from ..engine import Act, Packable, Runtime
+from ..engine import Act, Operand, Packable, Runtime
 from .util import act_from_nchw
 
 
@@ -55,12 +62,66 @@ def Normalize(in_channels, num_groups=32):
     return torch.nn.GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=1e-6, affine=True)
 
 
-def _conv3x3_params(conv: nn.Conv2d):
-    return E.pk_conv3x3(conv.weight), E.pk_f32(conv.bias)
+FIRST_STAGE_PRECISIONS = ("fast", "precise-wide", "precise-full")
 
 
-def _conv1x1_params(conv: nn.Conv2d):
-    return E.pk_linear(conv.weight), E.pk_f32(conv.bias)
+def first_stage_precision(p) -> E.Precision:
+    """the operand policy of a first stage: one of FIRST_STAGE_PRECISIONS or the matching engine.Precision object"""
+    try:
+        q = E.precision(p)
+    except (ValueError, TypeError):
+        q = None
+    if not any(q is E.PRECISIONS[n] or (type(q) is type(E.PRECISIONS[n]) and q == E.PRECISIONS[n]) for n in FIRST_STAGE_PRECISIONS):
+        raise ValueError(f"first-stage precision {p!r}: choose one of {list(FIRST_STAGE_PRECISIONS)} (or the matching engine.Precision); "
+                         "policies with e4m3 lo planes are not measured for the first stage")
+    return q
+
+
+def set_precision(module: nn.Module, p) -> E.Precision:
+    """store the operand policy on every module below `module` (their `_run`s read it through the Runtime their entry creates)"""
+    q = first_stage_precision(p)
+    for m in module.modules():
+        m.precision = q
+    return q
+
+
+def _runtime(module: nn.Module, device, F: int) -> Runtime:
+    """the Runtime of one run of `module`, carrying the module's operand policy"""
+    rt = Runtime(device, F, 1)
+    rt.prec = getattr(module, "precision", E.FAST)
+    if _split(rt):           # a backend or a width without the split attention kernel is refused before anything is launched
+        for m in module.modules():
+            if isinstance(m, AttnBlock):
+                m.split_kernel(rt)
+    return rt
+
+
+def _split(rt: Runtime) -> bool:
+    return E.is_wide(rt.prec)
+
+
+def _tokens_of_nchw(rt: Runtime, x: torch.Tensor, cpad: int) -> Operand:
+    """(F, C, H, W) floats -> the [F*H*W, cpad] token operand a first conv gathers from (operand class `stem`)"""
+    F, C, H, W = x.shape
+    x16 = rt.operand((F * H * W, cpad), "stem")
+    rt.be.nchw_to_tokens_f16(x.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, cpad, *x16)
+    return x16
+
+
+def _input_operand(rt: Runtime, x16) -> Operand:
+    """the token operand handed to a network's `_run` (a bare tensor is an operand without a lo plane)"""
+    x16 = x16 if isinstance(x16, Operand) else Operand(x16)
+    if _split(rt) and x16.lo is None:
+        raise ValueError(f"the operand policy {rt.prec.name} needs the lo plane of the input tokens (an engine.Operand)")
+    return x16
+
+
+def _conv3x3_params(conv: nn.Conv2d, lo: bool = False):
+    return E.pk_conv3x3(conv.weight, lo=lo), E.pk_f32(conv.bias)
+
+
+def _conv1x1_params(conv: nn.Conv2d, lo: bool = False):
+    return E.pk_linear(conv.weight, lo), E.pk_f32(conv.bias)
 
 
 def _gn_params(gn: nn.GroupNorm):
@@ -69,19 +130,18 @@ def _gn_params(gn: nn.GroupNorm):
     return E.pk_f32(gn.weight), E.pk_f32(gn.bias)
 
 
-def _conv3x3(rt: Runtime, x16, F, Hin, Win, Cin, w16, b, Cout, *, upsample=False, down_br=False, res32=None,
-             out16=False) -> Act:
+def _conv3x3(rt: Runtime, x: Operand, F, Hin, Win, Cin, pk, key, Cout, *, upsample=False, down_br=False, res32=None) -> Act:
+    """3x3 conv of the operand `x` (both planes under a split policy) with the weights pk[key] (+ their lo twin: engine.gemm)"""
     if down_br and (Hin % 2 or Win % 2):
         raise NotImplementedError("the stride-2 Downsample needs even image sizes")
     Hout, Wout = (2 * Hin, 2 * Win) if upsample else ((Hin // 2, Win // 2) if down_br else (Hin, Win))
     M = F * Hout * Wout
     o32 = rt.empty((M, Cout), torch.float32)
-    o16 = rt.operand((M, Cout)) if out16 else None      # (the first stage runs plain fp16 operands: no lo planes)
-    rt.be.gemm(x16, w16, M=M, N=Cout, K=9 * Cin, a_mode=E._hip.A_CONV3X3,
-               conv=dict(Cin=Cin, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=2 if down_br else 1,
-                         upsample=int(upsample), pad_br=int(down_br)),
-               bias=b, res1=res32, ldr1=Cout, out32=o32, ldc32=Cout, out16=o16 and o16.hi, ldc16=Cout)
-    return Act(F, Hout, Wout, Cout, f32=o32, f16=o16)
+    E.gemm(rt, x, pk, key, M=M, N=Cout, K=9 * Cin, a_mode=E._hip.A_CONV3X3,
+           conv=dict(Cin=Cin, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, stride=2 if down_br else 1,
+                     upsample=int(upsample), pad_br=int(down_br)),
+           res1=res32, ldr1=Cout, out32=o32, ldc32=Cout, ldc16=Cout)
+    return Act(F, Hout, Wout, Cout, f32=o32)
 
 
 class Upsample(nn.Module, Packable):
@@ -95,15 +155,14 @@ class Upsample(nn.Module, Packable):
         self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
         self._init_packable()
 
-    def _pack(self):
-        return dict(c=_conv3x3_params(self.conv))
+    def _pack(self, lo: bool = False):
+        return dict(c=_conv3x3_params(self.conv, lo))
 
     def _run(self, rt: Runtime, x: Act) -> Act:
-        w, b = self.packed()["c"]
-        return _conv3x3(rt, x.need_f16(rt).hi, x.F, x.H, x.W, x.C, w, b, x.C, upsample=True)
+        return _conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, x.C, self.packed(), "c", x.C, upsample=True)
 
     def forward(self, x):
-        rt = Runtime(x.device, x.shape[0], 1)
+        rt = _runtime(self, x.device, x.shape[0])
         return self._run(rt, act_from_nchw(rt, x)).to_nchw().to(x.dtype)
 
 
@@ -118,15 +177,14 @@ class Downsample(nn.Module, Packable):
         self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
         self._init_packable()
 
-    def _pack(self):
-        return dict(c=_conv3x3_params(self.conv))
+    def _pack(self, lo: bool = False):
+        return dict(c=_conv3x3_params(self.conv, lo))
 
     def _run(self, rt: Runtime, x: Act) -> Act:
-        w, b = self.packed()["c"]
-        return _conv3x3(rt, x.need_f16(rt).hi, x.F, x.H, x.W, x.C, w, b, x.C, down_br=True)
+        return _conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, x.C, self.packed(), "c", x.C, down_br=True)
 
     def forward(self, x):
-        rt = Runtime(x.device, x.shape[0], 1)
+        rt = _runtime(self, x.device, x.shape[0])
         return self._run(rt, act_from_nchw(rt, x)).to_nchw().to(x.dtype)
 
 
@@ -151,32 +209,31 @@ class ResnetBlock(nn.Module, Packable):
             setattr(self, name, _conv(in_channels, out_channels, k))
         self._init_packable()
 
-    def _pack(self):
-        pk = dict(n1=_gn_params(self.norm1), c1=_conv3x3_params(self.conv1), n2=_gn_params(self.norm2),
-                  c2=_conv3x3_params(self.conv2))
+    def _pack(self, lo: bool = False):
+        pk = dict(n1=_gn_params(self.norm1), c1=_conv3x3_params(self.conv1, lo), n2=_gn_params(self.norm2),
+                  c2=_conv3x3_params(self.conv2, lo))
         if self.in_channels != self.out_channels:
-            pk["sc"] = _conv3x3_params(self.conv_shortcut) if self.use_conv_shortcut else _conv1x1_params(self.nin_shortcut)
+            pk["sc"] = _conv3x3_params(self.conv_shortcut, lo) if self.use_conv_shortcut else _conv1x1_params(self.nin_shortcut, lo)
         return pk
 
     def _run(self, rt: Runtime, x: Act) -> Act:
         pk = self.packed()
         Ci, Co = self.in_channels, self.out_channels
-        h16 = E.gn_spatial(rt, x.f32, x.F, x.N, Ci, *pk["n1"], 1e-6, True).hi
-        h = _conv3x3(rt, h16, x.F, x.H, x.W, Ci, *pk["c1"], Co)
-        h16 = E.gn_spatial(rt, h.f32, x.F, x.N, Co, *pk["n2"], 1e-6, True).hi
+        h16 = E.gn_spatial(rt, x.f32, x.F, x.N, Ci, *pk["n1"], 1e-6, True, split="gn_res")
+        h = _conv3x3(rt, h16, x.F, x.H, x.W, Ci, pk, "c1", Co)
+        h16 = E.gn_spatial(rt, h.f32, x.F, x.N, Co, *pk["n2"], 1e-6, True, split="gn_res")
         skip = x.f32
         if Ci != Co:
-            w, b = pk["sc"]
             if self.use_conv_shortcut:
-                skip = _conv3x3(rt, x.need_f16(rt).hi, x.F, x.H, x.W, Ci, w, b, Co).f32
+                skip = _conv3x3(rt, x.need_f16(rt), x.F, x.H, x.W, Ci, pk, "sc", Co).f32
             else:
                 skip = rt.empty((x.M, Co), torch.float32)
-                rt.be.gemm(x.need_f16(rt).hi, w, M=x.M, N=Co, K=Ci, lda=Ci, bias=b, out32=skip, ldc32=Co)
-        return _conv3x3(rt, h16, x.F, x.H, x.W, Co, *pk["c2"], Co, res32=skip)      # x (or shortcut(x)) + h
+                E.gemm(rt, x.need_f16(rt), pk, "sc", M=x.M, N=Co, K=Ci, lda=Ci, out32=skip, ldc32=Co)
+        return _conv3x3(rt, h16, x.F, x.H, x.W, Co, pk, "c2", Co, res32=skip)      # x (or shortcut(x)) + h
 
     def forward(self, x, temb=None):
         assert temb is None
-        rt = Runtime(x.device, x.shape[0], 1)
+        rt = _runtime(self, x.device, x.shape[0])
         return self._run(rt, act_from_nchw(rt, x)).to_nchw().to(x.dtype)
 
 
@@ -195,14 +252,42 @@ class AttnBlock(nn.Module, Packable):
         self.proj_out = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
         self._init_packable()
 
-    def _pack(self):
-        return dict(n=_gn_params(self.norm), q=_conv1x1_params(self.q), k=_conv1x1_params(self.k),
-                    v=_conv1x1_params(self.v), o=_conv1x1_params(self.proj_out))
+    def _pack(self, lo: bool = False):
+        return dict(n=_gn_params(self.norm), q=_conv1x1_params(self.q, lo), k=_conv1x1_params(self.k, lo),
+                    v=_conv1x1_params(self.v, lo), o=_conv1x1_params(self.proj_out, lo))
+
+    def split_kernel(self, rt: Runtime):
+        """the backend's `attn_frame_split`, the ONLY attention of a split policy; NotImplementedError naming what is missing"""
+        fn = getattr(rt.be, "attn_frame_split", None)
+        if fn is None:
+            raise NotImplementedError(f"AttnBlock under the operand policy {rt.prec.name}: this backend has no fused attention kernel on "
+                                      "split operands (attn_frame_split)")
+        if self.in_channels not in FUSED_ATTN_CHANNELS:
+            raise NotImplementedError(f"AttnBlock under the operand policy {rt.prec.name}: pnc_attn_frame_split_f16 is built for "
+                                      f"{FUSED_ATTN_CHANNELS} channels, not {self.in_channels} channels")
+        return fn
+
+    def _run_split(self, rt: Runtime, x: Act) -> Act:
+        """q, k, v as row-major pairs -> one attn_frame_split launch over all frames, at every N -> proj_out on the split output"""
+        C, N, M, F = self.in_channels, x.N, x.M, x.F
+        attn = self.split_kernel(rt)
+        pk = self.packed()
+        h = E.gn_spatial(rt, x.f32, F, N, C, *pk["n"], 1e-6, False, split="gn_stt")
+        q, k, v = (rt.operand((M, C), "qkv") for _ in range(3))
+        for key, out in (("q", q), ("k", k), ("v", v)):
+            E.gemm(rt, h, pk, key, out, M=M, N=C, K=C, lda=C, ldc16=C)
+        o = rt.operand((M, C), "attn_o")
+        attn(q.hi, q.lo, C, k.hi, k.lo, C, v.hi, v.lo, C, o.hi, o.lo, C, F=F, N=N, C=C, scale=float(C) ** -0.5)
+        out = rt.empty((M, C), torch.float32)
+        E.gemm(rt, o, pk, "o", M=M, N=C, K=C, lda=C, res1=x.f32, ldr1=C, out32=out, ldc32=C)
+        return Act(F, x.H, x.W, C, f32=out)
 
     def _run(self, rt: Runtime, x: Act) -> Act:
         C, N, M, F = self.in_channels, x.N, x.M, x.F
         if N % 8:
             raise NotImplementedError(f"AttnBlock over {N} tokens per frame (supported: multiples of 8)")
+        if _split(rt):
+            return self._run_split(rt, x)
         # The fused kernel is an OPTIONAL capability of the backend, looked up rather than called through the handle: the emulated
         # backend of the tests has no twin of it yet and then behaves as before, refusal of long frames included (DESIGN.md §10 f2).
         attn_frame = getattr(rt.be, "attn_frame", None)
@@ -236,7 +321,7 @@ class AttnBlock(nn.Module, Packable):
         return Act(F, x.H, x.W, C, f32=out)
 
     def forward(self, x, **kwargs):
-        rt = Runtime(x.device, x.shape[0], 1)
+        rt = _runtime(self, x.device, x.shape[0])
         return self._run(rt, act_from_nchw(rt, x)).to_nchw().to(x.dtype)
 
 
@@ -318,15 +403,16 @@ class Decoder(nn.Module, Packable):
     def get_last_layer(self, **kwargs):
         return self.conv_out.weight
 
-    def _pack(self):
+    def _pack(self, lo: bool = False):
         zc = (self.z_channels + 7) // 8 * 8
-        return dict(cin=(E.pk_conv3x3(self.conv_in.weight, zc), E.pk_f32(self.conv_in.bias)), zc=zc,
-                    no=_gn_params(self.norm_out), cout=_conv3x3_params(self.conv_out))
+        return dict(cin=(E.pk_conv3x3(self.conv_in.weight, zc, lo), E.pk_f32(self.conv_in.bias)), zc=zc,
+                    no=_gn_params(self.norm_out), cout=_conv3x3_params(self.conv_out, lo))
 
-    def _run(self, rt: Runtime, z16: torch.Tensor, F: int, H: int, W: int) -> Act:
-        """z16: [F*H*W, zc] fp16 tokens (channels zero-padded to zc)."""
+    def _run(self, rt: Runtime, z16, F: int, H: int, W: int) -> Act:
+        """z16: [F*H*W, zc] fp16 tokens (channels zero-padded to zc), a tensor or — with its lo plane — an Operand."""
         pk = self.packed()
-        h = _conv3x3(rt, z16, F, H, W, pk["zc"], *pk["cin"], self.conv_in.out_channels)
+        z16 = _input_operand(rt, z16)
+        h = _conv3x3(rt, z16, F, H, W, pk["zc"], pk, "cin", self.conv_in.out_channels)
         h = self.mid.block_1._run(rt, h)
         if isinstance(self.mid.attn_1, AttnBlock):
             h = self.mid.attn_1._run(rt, h)
@@ -341,17 +427,14 @@ class Decoder(nn.Module, Packable):
                 h = up.upsample._run(rt, h)
         if self.give_pre_end:
             return h
-        h16 = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True).hi
-        w, b = pk["cout"]
-        return _conv3x3(rt, h16, h.F, h.H, h.W, h.C, w, b, self.out_ch)
+        h16 = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True, split="gn_head")
+        return _conv3x3(rt, h16, h.F, h.H, h.W, h.C, pk, "cout", self.out_ch)
 
     def forward(self, z, **kwargs):
         with torch.no_grad():
             F, C, H, W = z.shape
-            rt = Runtime(z.device, F, 1)
-            zc = self.packed()["zc"]
-            z16 = rt.empty((F * H * W, zc), torch.float16)
-            rt.be.nchw_to_tokens_f16(z.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, zc, z16)
+            rt = _runtime(self, z.device, F)
+            z16 = _tokens_of_nchw(rt, z, self.packed()["zc"])
             out = self._run(rt, z16, F, H, W).to_nchw()
             if self.tanh_out:
                 out = torch.tanh(out)
@@ -384,15 +467,17 @@ class Encoder(nn.Module, Packable):
         self.conv_out = _conv(widths[-1], self.out_channels)
         self._init_packable()
 
-    def _pack(self):
+    def _pack(self, lo: bool = False):
         ic = (self.in_channels + 7) // 8 * 8
-        return dict(cin=(E.pk_conv3x3(self.conv_in.weight, ic), E.pk_f32(self.conv_in.bias)), ic=ic,
-                    no=_gn_params(self.norm_out), cout=_conv3x3_params(self.conv_out))
+        return dict(cin=(E.pk_conv3x3(self.conv_in.weight, ic, lo), E.pk_f32(self.conv_in.bias)), ic=ic,
+                    no=_gn_params(self.norm_out), cout=_conv3x3_params(self.conv_out, lo))
 
-    def _run(self, rt: Runtime, x16: torch.Tensor, F: int, H: int, W: int) -> Act:
-        """x16: [F*H*W, ic] fp16 tokens (channels zero-padded to ic).  Returns the moments as an Act (fp32)."""
+    def _run(self, rt: Runtime, x16, F: int, H: int, W: int) -> Act:
+        """x16: [F*H*W, ic] fp16 tokens (channels zero-padded to ic), a tensor or — with its lo plane — an Operand.  Returns the
+        moments as an Act (fp32)."""
         pk = self.packed()
-        h = _conv3x3(rt, x16, F, H, W, pk["ic"], *pk["cin"], self.ch)
+        x16 = _input_operand(rt, x16)
+        h = _conv3x3(rt, x16, F, H, W, pk["ic"], pk, "cin", self.ch)
         for i_level in range(self.num_resolutions):
             down = self.down[i_level]
             for i_block in range(self.num_res_blocks):
@@ -405,19 +490,16 @@ class Encoder(nn.Module, Packable):
         if isinstance(self.mid.attn_1, AttnBlock):
             h = self.mid.attn_1._run(rt, h)
         h = self.mid.block_2._run(rt, h)
-        h16 = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True).hi
-        w, b = pk["cout"]
-        return _conv3x3(rt, h16, h.F, h.H, h.W, h.C, w, b, self.out_channels)
+        h16 = E.gn_spatial(rt, h.f32, h.F, h.N, h.C, *pk["no"], 1e-6, True, split="gn_head")
+        return _conv3x3(rt, h16, h.F, h.H, h.W, h.C, pk, "cout", self.out_channels)
 
     def forward(self, x):
         with torch.no_grad():
             if x.dim() == 5:                                   # (b t c h w) video input (model.py:855-856)
                 x = x.reshape(-1, *x.shape[2:])
             F, C, H, W = x.shape
-            rt = Runtime(x.device, F, 1)
-            ic = self.packed()["ic"]
-            x16 = rt.empty((F * H * W, ic), torch.float16)
-            rt.be.nchw_to_tokens_f16(x.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, ic, x16)
+            rt = _runtime(self, x.device, F)
+            x16 = _tokens_of_nchw(rt, x, self.packed()["ic"])
             out = self._run(rt, x16, F, H, W).to_nchw()
         return out.to(x.dtype)
 
@@ -427,36 +509,33 @@ class FirstStageEncoder(nn.Module, Packable):
     DiagonalGaussianDistribution(moments): mean, logvar clamped to [-30, 20], sample = mean + exp(logvar / 2) * eps
     (`AutoencoderKLInferenceWrapper.encode` returns `.sample()`, autoencoder.py:371-373)."""
 
-    def __init__(self, embed_dim: int, ddconfig: dict):
+    def __init__(self, embed_dim: int, ddconfig: dict, *, precision="fast"):
         super().__init__()
         assert ddconfig["double_z"]
         self.encoder = Encoder(**ddconfig)
         self.quant_conv = torch.nn.Conv2d(2 * ddconfig["z_channels"], 2 * embed_dim, 1)
         self.embed_dim = embed_dim
         self._init_packable()
+        set_precision(self, precision)                       # (the Encoder's signature mirrors the reference's ddconfig)
 
-    def _pack(self):
-        return dict(q=_conv1x1_params(self.quant_conv))
+    def _pack(self, lo: bool = False):
+        return dict(q=_conv1x1_params(self.quant_conv, lo))
 
     def moments(self, x: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
             if x.dim() == 5:
                 x = x.reshape(-1, *x.shape[2:])
-            enc = self.encoder
             F, C, H, W = x.shape
-            rt = Runtime(x.device, F, 1)
-            ic = enc.packed()["ic"]
-            x16 = rt.empty((F * H * W, ic), torch.float16)
-            rt.be.nchw_to_tokens_f16(x.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, ic, x16)
+            rt = _runtime(self, x.device, F)
+            x16 = _tokens_of_nchw(rt, x, self.encoder.packed()["ic"])
             return self._moments_of_tokens(rt, x16, F, H, W).to(x.dtype)
 
-    def _moments_of_tokens(self, rt: Runtime, x16: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
+    def _moments_of_tokens(self, rt: Runtime, x16: Operand, F: int, H: int, W: int) -> torch.Tensor:
         """encoder + quant_conv on the image tokens x16 [F*H*W, ic] -> the moments, NCHW fp32"""
         h = self.encoder._run(rt, x16, F, H, W)
-        w, b = self.packed()["q"]
         n = self.quant_conv.out_channels
         m32 = rt.empty((h.M, n), torch.float32)
-        rt.be.gemm(h.need_f16(rt).hi, w, M=h.M, N=n, K=h.C, lda=h.C, bias=b, out32=m32, ldc32=n)
+        E.gemm(rt, h.need_f16(rt), self.packed(), "q", M=h.M, N=n, K=h.C, lda=h.C, out32=m32, ldc32=n)
         return Act(h.F, h.H, h.W, n, f32=m32).to_nchw()
 
     def moments_u8(self, x_u8: torch.Tensor, table: str = "image") -> torch.Tensor:
@@ -469,11 +548,11 @@ class FirstStageEncoder(nn.Module, Packable):
             if C != self.encoder.in_channels:
                 raise ValueError(f"moments_u8: frames of {C} channels for an encoder of {self.encoder.in_channels}")
             image.table(table)                                     # (an unknown kind is refused here)
-            rt = Runtime(x_u8.device, F, 1)
+            rt = _runtime(self, x_u8.device, F)
             image.capability(rt.be, "u8_to_tokens_f16")
             ic = self.encoder.packed()["ic"]
-            x16 = rt.empty((F * H * W, ic), torch.float16)
-            image.u8_to_tokens(rt, x_u8, table, ic, E.Operand(x16))
+            x16 = rt.operand((F * H * W, ic), "stem")
+            image.u8_to_tokens(rt, x_u8, table, ic, x16)
             return self._moments_of_tokens(rt, x16, F, H, W)
 
     def moments_sparse_u8(self, clip: "image.SparseClip", table: str = "image") -> torch.Tensor:
@@ -491,12 +570,13 @@ class FirstStageEncoder(nn.Module, Packable):
                 raise ValueError(f"moments_sparse_u8: frames of {C} channels for an encoder of {self.encoder.in_channels}")
             image.table(table)                                     # (an unknown kind is refused here)
             F = K + (1 if K < clip.num_frames else 0)
-            rt = Runtime(x_u8.device, F, 1)
+            rt = _runtime(self, x_u8.device, F)
             image.capability(rt.be, "u8_to_tokens_f16")
             ic = self.encoder.packed()["ic"]
-            x16 = (rt.zeros if F > K else rt.empty)((F * H * W, ic), torch.float16)
+            alloc = rt.zeros if F > K else rt.empty              # the blank frame is zero in both planes
+            x16 = Operand(alloc((F * H * W, ic), torch.float16), alloc((F * H * W, ic), torch.float16) if _split(rt) else None)
             if K:
-                image.u8_to_tokens(rt, x_u8, table, ic, E.Operand(x16[: K * H * W]))
+                image.u8_to_tokens(rt, x_u8, table, ic, x16.map(lambda t: t[: K * H * W]))
             return self._moments_of_tokens(rt, x16, F, H, W).index_select(0, clip.gather_index())
 
     def encode(self, x: torch.Tensor, generator=None, sample: bool = True) -> torch.Tensor:
@@ -528,20 +608,21 @@ class FirstStageDecoder(nn.Module, Packable):
     match the reference's, so `load_state_dict(first_stage_sd, strict=False)` fills it (encoder / quant_conv /
     loss keys are reported as unexpected, like any partial load)."""
 
-    def __init__(self, embed_dim: int, ddconfig: dict):
+    def __init__(self, embed_dim: int, ddconfig: dict, *, precision="fast"):
         super().__init__()
         self.decoder = Decoder(**ddconfig)
         self.post_quant_conv = torch.nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
         self.embed_dim = embed_dim
         self._init_packable()
+        set_precision(self, precision)                       # (the Decoder's signature mirrors the reference's ddconfig)
 
-    def _pack(self):
+    def _pack(self, lo: bool = False):
         # 1x1 conv embed_dim -> z_channels, both zero-padded to multiples of 8 so that its fp16 output is directly the
         # padded token matrix conv_in gathers from
         ec, zc = (self.embed_dim + 7) // 8 * 8, (self.decoder.z_channels + 7) // 8 * 8
         w = torch.zeros((zc, ec), dtype=torch.float16, device=self.post_quant_conv.weight.device)
-        w[: self.decoder.z_channels, : self.embed_dim] = self.post_quant_conv.weight.detach().reshape(
-            self.decoder.z_channels, self.embed_dim).to(torch.float16)
+        w[: self.decoder.z_channels, : self.embed_dim] = E._cast16(self.post_quant_conv.weight.reshape(
+            self.decoder.z_channels, self.embed_dim), lo)
         b = torch.zeros(zc, dtype=torch.float32, device=w.device)
         b[: self.decoder.z_channels] = self.post_quant_conv.bias.detach().float()
         return dict(w=w.contiguous(), b=b, ec=ec, zc=zc)
@@ -551,15 +632,14 @@ class FirstStageDecoder(nn.Module, Packable):
         pk = self.packed()
         F, C, H, W = z.shape
         M = F * H * W
-        e16 = rt.empty((M, pk["ec"]), torch.float16)
-        rt.be.nchw_to_tokens_f16(z.detach().to(torch.float32).contiguous(), C, None, 0, F, H * W, pk["ec"], e16)
-        z16 = rt.empty((M, pk["zc"]), torch.float16)
-        rt.be.gemm(e16, pk["w"], M=M, N=pk["zc"], K=pk["ec"], lda=pk["ec"], bias=pk["b"], out16=z16, ldc16=pk["zc"])
+        e16 = _tokens_of_nchw(rt, z, pk["ec"])
+        z16 = rt.operand((M, pk["zc"]), "stem")
+        E.gemm(rt, e16, pk, "w", z16, M=M, N=pk["zc"], K=pk["ec"], lda=pk["ec"], bias=pk["b"], ldc16=pk["zc"])
         return self.decoder._run(rt, z16, F, H, W)
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
-            out = self._decode_tokens(Runtime(z.device, z.shape[0], 1), z).to_nchw()
+            out = self._decode_tokens(_runtime(self, z.device, z.shape[0]), z).to_nchw()
         return out.to(z.dtype)
 
     def decode_u8(self, z: torch.Tensor) -> torch.Tensor:
@@ -569,7 +649,7 @@ class FirstStageDecoder(nn.Module, Packable):
         if self.decoder.tanh_out or self.decoder.give_pre_end:
             raise NotImplementedError("decode_u8 quantises the output conv's tokens: tanh_out / give_pre_end decoders go through decode()")
         with torch.no_grad():
-            rt = Runtime(z.device, z.shape[0], 1)
+            rt = _runtime(self, z.device, z.shape[0])
             image.capability(rt.be, "tokens_to_u8")
             return image.tokens_to_u8(rt, self._decode_tokens(rt, z))
 

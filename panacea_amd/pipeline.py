@@ -10,6 +10,11 @@ which is what `DiffusionEngine3D.sample` + `decode_first_stage` do around the ne
 `rollout_frames` chains such windows into a video of any length by conditioning, on one device: the `concat` of window k is the
 first-stage encoding of a `final_cond_zero` clip (image.SparseClip) around an anchor frame, and the anchor of window k + 1 is a frame
 window k decoded.
+
+The first stages arrive as objects and carry their own operand policy (`FirstStageDecoder / FirstStageEncoder(..., precision=)`):
+"fast" runs them on plain fp16 operands and fp16 weights; "precise-wide" / "precise-full" on fp16 pairs (and split weights), which
+is what an fp32 checkpoint wants — the reference runs its first stage in fp32, and in a rollout the encoder's moments enter every
+evaluation of the next window.  Nothing here changes with the policy.
 """
 from __future__ import annotations
 

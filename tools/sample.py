@@ -78,6 +78,9 @@ def main():
                     help="operand policy of the denoiser (default: the network's own, `precise`); `precise-ckpt` splits the weights too — "
                          "the policy for fp32 checkpoints with an ordinary activation range (|v| < 512); `precise-full` splits every "
                          "operand and the weights (|v| < 65504, at 3-4x the time)")
+    ap.add_argument("--first-stage-precision", choices=list(model.FIRST_STAGE_PRECISIONS), default="fast",
+                    help="operand policy of the first-stage decoder and encoder: `precise-wide` carries every GEMM and attention operand as "
+                         "an fp16 pair, `precise-full` splits the weights too (fp32 checkpoints: the reference runs its first stage in fp32)")
     ap.add_argument("--range-profile", nargs="?", const="", default=None, metavar="FILE",
                     help="profile the operand ranges of the first two evaluations of the run under the chosen policy "
                          "(UNetModel3D.profile_ranges): prints the class table, the ten widest sites and the recommended operand "
@@ -97,7 +100,7 @@ def main():
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
     net = build_network(kw)
-    fs = model.FirstStageDecoder(4, VAE)
+    fs = model.FirstStageDecoder(4, VAE, precision=a.first_stage_precision)
     if a.ckpt:
         print(checkpoint.load_denoiser(net, a.ckpt))
         sd = checkpoint.denoiser_state_dict(checkpoint.read_state_dict(a.ckpt), "first_stage_model.")
@@ -158,7 +161,7 @@ def rollout(a, net, fs, smp, g, dev):
     they meet); the first-stage encoder gets synthetic weights, or the checkpoint's `first_stage_model.*` like the decoder."""
     T, W = a.frames, a.windows
     N = T + (W - 1) * (T - 1)
-    enc = model.FirstStageEncoder(4, VAE)
+    enc = model.FirstStageEncoder(4, VAE, precision=a.first_stage_precision)
     if a.ckpt:
         print(enc.load_state_dict(checkpoint.denoiser_state_dict(checkpoint.read_state_dict(a.ckpt), "first_stage_model."), strict=False))
     else:
