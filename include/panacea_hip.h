@@ -641,6 +641,36 @@ int pnc_attn_frame_split_f16(const void* q, const void* q_lo, int64_t ldq, const
                              int F, int N, int C, float scale, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * 6c. Text-tower attention on SPLIT operands: the causal self-attention of the OpenCLIP text tower, all heads of all prompts in one
+ *    launch, on the operands and with the formulae of section 6b.  Additive under ABI 8.
+ *    A prompt is a group of Lp token rows; the row of (prompt g, token i) is g*Lp + i; head h takes columns 64h .. 64h+63 (head
+ *    dim 64); element c of head h of that row is at [(g*Lp + i)*ld + 64h + c], c < 64.
+ *    Every operand x is an fp16 pair x = x_hi + 2^-11 x_lo; q_lo .. o_lo have the layout and the leading dimension of their hi plane.
+ *    V is ROW-major like K — what a QKV projection writes as out16 + out16_lo with N = 3 W and no out16t; q, k and v may be column
+ *    blocks of that one buffer (ld = 3 W).
+ *        S = Qh.Kh + 2^-11 (Qh.Kl + Ql.Kh)                   the lo.lo products are dropped; fp32 accumulation, the hi.hi and the
+ *                                                            cross sums kept apart and met once
+ *        query i attends key j  iff  j <= i  and  j < kv_valid
+ *        P = softmax(scale * S) over the attended keys;  P = Ph + 2^-11 Pl, an fp16 pair rounded against the row's maximum (two
+ *                                                            passes over the row: no running maximum, no rescale)
+ *        O = Ph.Vh + 2^-11 (Ph.Vl + Pl.Vh)                   normalised once, written as o = fp16(O), o_lo = fp16((O - o) * 2^11)
+ *    Query rows kv_valid <= i < Lp are padding: they attend all keys < kv_valid and ARE written (finite when their q row is finite);
+ *    the caller drops them.  Key and value rows >= kv_valid may hold anything, NaN included: they are never loaded.
+ *    ONLY the named elements are read or written: row padding between 64*heads and ld and rows after groups*Lp keep their bits, and
+ *    a buffer may end right after its last named element.  Deterministic: no atomics, the same bits on every run.  o and o_lo must
+ *    not overlap each other or any input.
+ *    Accepted: groups >= 1; heads >= 1; groups*heads < 2^31; Lp % 8 == 0, 8 <= Lp <= 96; 1 <= kv_valid <= Lp; ldq, ldk, ldv, ldo >=
+ *    64*heads; anything else -> PNC_EINVAL.  ldq, ldk, ldv, ldo multiples of 8 elements and all eight pointers 16-byte aligned, else
+ *    PNC_EALIGN.  Checked in this order: null pointers, ranges, leading dimensions, pointer alignment; nothing is launched on a
+ *    refusal.
+ *     -> FrozenOpenCLIPEmbedder.encode_with_transformer / text_transformer_forward under the tower's split policies: the attention
+ *        of every residual block (sgm/modules/encoders/modules.py:604-616)
+ * ------------------------------------------------------------------------- */
+int pnc_attn_text_split_f16(const void* q, const void* q_lo, int64_t ldq, const void* k, const void* k_lo, int64_t ldk,
+                            const void* v, const void* v_lo, int64_t ldv, void* o, void* o_lo, int64_t ldo,
+                            int groups, int heads, int Lp, int kv_valid, float scale, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * 7. Image boundary: 8-bit channels-last frames in and out.  Additive under ABI 8.  Both entries
  *    launch on the caller's stream, allocate nothing and do not synchronise; nothing is launched on a refusal.
  *

@@ -127,6 +127,7 @@ _SIGNATURES = {
     "pnc_attn_temporal_f16": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     "pnc_attn_frame_f16": (_I, [_P, _L, _P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _F, _P]),
     "pnc_attn_frame_split_f16": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _F, _P]),
+    "pnc_attn_text_split_f16": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _L, _P, _P, _L, _I, _I, _I, _I, _F, _P]),
     "pnc_groupnorm_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "pnc_groupnorm_apply": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _I, _P, _I, _I, _P]),
     "pnc_groupnorm_combine": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -519,6 +520,17 @@ def attn_frame_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, 
                   _ptr(q, f16, "q"), _ptr(q_lo, f16, "q_lo"), ldq, _ptr(k, f16, "k"), _ptr(k_lo, f16, "k_lo"), ldk,
                   _ptr(v, f16, "v"), _ptr(v_lo, f16, "v_lo"), ldv, _ptr(o, f16, "o"), _ptr(o_lo, f16, "o_lo"), ldo,
                   F, N, C, scale, _stream()), "pnc_attn_frame_split_f16")
+
+
+def attn_text_split(q, q_lo, ldq, k, k_lo, ldk, v, v_lo, ldv, o, o_lo, ldo, *, groups, heads, Lp, kv_valid, scale):
+    """pnc_attn_text_split_f16: the text tower's causal self-attention on split operands, all heads (of 64) of all prompts (groups of
+    Lp <= 96 token rows, the first kv_valid of them real keys) in one launch; V is ROW-major like K, so q / k / v may be column blocks
+    of one QKV buffer (include/panacea_hip.h section 6c).  Flops: three MFMA products per product, about half the tiles causal."""
+    f16 = torch.float16
+    _check(_timed("attn_text_split", 6.0 * groups * heads * Lp * kv_valid * 64, 0.0, load().pnc_attn_text_split_f16,
+                  _ptr(q, f16, "q"), _ptr(q_lo, f16, "q_lo"), ldq, _ptr(k, f16, "k"), _ptr(k_lo, f16, "k_lo"), ldk,
+                  _ptr(v, f16, "v"), _ptr(v_lo, f16, "v_lo"), ldv, _ptr(o, f16, "o"), _ptr(o_lo, f16, "o_lo"), ldo,
+                  groups, heads, Lp, kv_valid, scale, _stream()), "pnc_attn_text_split_f16")
 
 
 def attn_temporal(q, ldq, k, ldk, v, ldv, o, ldo, *, B, T, Npix, heads, scale):
