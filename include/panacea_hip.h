@@ -540,6 +540,19 @@ int pnc_add_f32(const float* x, const float* a, int64_t n, float* y32, void* y16
                 void* stream);
 /* fp32 -> fp16 (+ lo plane in lo_fmt) */
 int pnc_cast_f16(const float* x, int64_t n, void* y16, void* y16_lo, int lo_fmt, void* stream);
+/* Second half of a nearest-x2 Upsample conv computed at SOURCE resolution (openaimodel.py:106-142).  P holds, per
+ * source pixel (row (f * Hin + sy) * Win + sx, ldp floats between rows), the nine tap products of the 3x3 conv: column
+ * (u * 3 + v) * Cout + n = sum_k x[src][k] * W[n][k][u][v] (a plain-A GEMM against the weight as [9 * Cout][Cin]).  For output pixel
+ * (y, x) of the [F][2 Hin][2 Win][Cout] map
+ *     acc = bias[n];  for u = 0..2, v = 0..2 in this order:  yy = y + u - 1, xx = x + v - 1;
+ *                     if 0 <= yy < 2 Hin and 0 <= xx < 2 Win:  acc += P[(f, yy >> 1, xx >> 1)][(u * 3 + v) * Cout + n]
+ * Taps outside the upsampled image are the conv's zero padding and are not read.  The order of the additions is the one written, so
+ * the result does not depend on the launch geometry.  out32 receives acc; out16 / out16_lo (optional; a lo plane needs out16) its
+ * fp16 plane and lo plane in lo_fmt (PNC_LO_*), packed like every other writer of the `stream` class (range monitor included).
+ * bias may be NULL (0).  Cout % 4 == 0, ldp % 4 == 0, ldp >= 9 * Cout (PNC_EINVAL); P, bias, out32, out16, out16_lo 16-byte aligned
+ * (PNC_EALIGN); both are answered before any launch.  Additive to ABI 8. */
+int pnc_upsample_combine(const float* P, int64_t ldp, const float* bias, int F, int Hin, int Win, int Cout, float* out32,
+                         void* out16, void* out16_lo, int lo_fmt, void* stream);
 
 /* Range monitor (round 6; ABI 7).  The eps contract of the `precise` operand policy is written for a residual stream inside the e4m3
  * lo plane's range (|v| < 512: beyond it the lo plane of a split operand saturates at +-448 and the operand falls back to fp16's 11

@@ -234,6 +234,80 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ x, c
     }
 }
 
+// pnc_upsample_combine (include/panacea_hip.h): the nine tap products of a nearest-x2 Upsample conv, computed per SOURCE pixel by a
+// plain-A GEMM, summed into the output pixels.  A work item owns the 2 x 2 output pixels of one source pixel (sy, sx) for 4 channels.
+// Along y they read, per tap row u, the source rows  y = 2 sy: (u0, sy-1) (u1, sy) (u2, sy);  y = 2 sy + 1: (u0, sy) (u1, sy) (u2, sy+1)
+// — five distinct (tap row, source row) slots, and the same five along x: 25 float4 loads, all issued ahead of the adds, for four
+// output quads of nine terms each.  A workgroup is a UC_TH x UC_TW tile of source pixels x UC_TQ channel quads (512 contiguous bytes
+// of a P row per tap): every P element is wanted by four output pixels, which sit in at most two neighbouring work items per axis, so
+// the repeats are L1 / L2 hits of the same or the neighbouring workgroup (the block order keeps neighbours on one XCD).
+constexpr int UC_TQ = 32, UC_TW = 4, UC_TH = 2;
+static_assert(UC_TQ * UC_TW * UC_TH == 256, "one work item per thread of the 256-thread workgroup");
+
+__global__ __launch_bounds__(256) void upsample_combine_kernel(const float* __restrict__ P, int64_t ldp,
+                                                               const float* __restrict__ bias, int Hin, int Win, int Cout,
+                                                               int tiles_x, int tiles_y, int qslices,
+                                                               float* __restrict__ out32, half_t* __restrict__ out16,
+                                                               void* __restrict__ out16_lo, int lo_fmt) {
+    // block -> (frame, channel slice, tile row, tile column), tile column fastest
+    int b = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y; b /= tiles_y;
+    const int qs = b % qslices;
+    const int f = b / qslices;
+    const int tid = threadIdx.x;
+    const int q = qs * UC_TQ + (tid & (UC_TQ - 1));
+    const int pix = tid / UC_TQ;
+    const int sx = tx * UC_TW + (pix % UC_TW), sy = ty * UC_TH + (pix / UC_TW);
+    if (q * 4 >= Cout || sx >= Win || sy >= Hin) return;
+    const int n = q * 4;
+    // slot i of an axis: tap index SU[i] at source offset SD[i]; output parity d reads the slots SEL[d][0..2] for u = 0, 1, 2
+    constexpr int SU[5] = {0, 0, 1, 2, 2}, SD[5] = {-1, 0, 0, 0, 1};
+    constexpr int SEL[2][3] = {{0, 2, 3}, {1, 2, 4}};
+    const bool rv[5] = {sy > 0, true, true, true, sy + 1 < Hin};       // a slot outside the image is zero padding: never read
+    const bool cv[5] = {sx > 0, true, true, true, sx + 1 < Win};
+    const float* Pn = P + n;
+    f32x4 v[5][5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            if (rv[i] && cv[j]) {
+                const int64_t row = ((int64_t)f * Hin + (sy + SD[i])) * Win + (sx + SD[j]);
+                v[i][j] = *reinterpret_cast<const f32x4*>(Pn + row * ldp + (int64_t)(SU[i] * 3 + SU[j]) * Cout);
+            } else {
+                v[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            }
+        }
+    }
+    const f32x4 bv = bias ? *reinterpret_cast<const f32x4*>(bias + n) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            f32x4 acc = bv;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+#pragma unroll
+                for (int w = 0; w < 3; ++w) {
+                    const int i = SEL[dy][u], j = SEL[dx][w];
+                    if (rv[i] && cv[j]) acc += v[i][j];              // (a skipped tap adds nothing: not even a +0 to a -0)
+                }
+            }
+            const int64_t o = (((int64_t)f * (2 * Hin) + (2 * sy + dy)) * (2 * Win) + (2 * sx + dx)) * Cout + n;
+            *reinterpret_cast<f32x4*>(out32 + o) = acc;
+            if (out16) {
+                half4v h = {(half_t)acc[0], (half_t)acc[1], (half_t)acc[2], (half_t)acc[3]};
+                *reinterpret_cast<half4v*>(out16 + o) = h;
+                if (out16_lo) {
+                    const float r[4] = {acc[0], acc[1], acc[2], acc[3]};
+                    store_lo4(out16_lo, lo_fmt, o, r, h);
+                }
+            }
+        }
+    }
+}
+
 // Exit of a sampler step: eps tokens of the CFG batch -> next latent, one pass.  The arithmetic
 // follows the reference's sequence of fp32 roundings (no contraction into FMAs), so a trajectory matches the reference's
 // sampler to the last few ulps.  Every product and sum is rounded on its own, like the reference's separate elementwise kernels:
@@ -534,6 +608,19 @@ extern "C" int pnc_add_f32(const float* x, const float* a, int64_t n, float* y32
     if (!x || n < 4 || n % 4 || (!y32 && !y16) || (y16_lo && !y16)) return PNC_EINVAL;
     if (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3) return PNC_EINVAL;
     return launch_1d(add_kernel, n / 4, stream, x, a, n / 4, y32, f16p(y16), y16_lo, lo_fmt);
+}
+
+extern "C" int pnc_upsample_combine(const float* P, int64_t ldp, const float* bias, int F, int Hin, int Win, int Cout, float* out32,
+                                    void* out16, void* out16_lo, int lo_fmt, void* stream) {
+    if (!P || !out32 || F < 1 || Hin < 1 || Win < 1 || Cout < 4 || Cout % 4 || ldp % 4 || ldp < 9 * (int64_t)Cout) return PNC_EINVAL;
+    if (lo_fmt != PNC_LO_F16 && lo_fmt != PNC_LO_E4M3) return PNC_EINVAL;
+    if (out16_lo && !out16) return PNC_EINVAL;
+    if (((uintptr_t)P | (uintptr_t)bias | (uintptr_t)out32 | (uintptr_t)out16 | (uintptr_t)out16_lo) & 15) return PNC_EALIGN;
+    const int tiles_x = (Win + UC_TW - 1) / UC_TW, tiles_y = (Hin + UC_TH - 1) / UC_TH, qslices = (Cout / 4 + UC_TQ - 1) / UC_TQ;
+    const int64_t blocks = (int64_t)F * tiles_y * tiles_x * qslices;
+    if (blocks >= ((int64_t)1 << 31)) return PNC_EINVAL;
+    return launch_1d(upsample_combine_kernel, blocks * 256, stream, P, ldp, bias, Hin, Win, Cout, tiles_x, tiles_y, qslices, out32,
+                     f16p(out16), out16_lo, lo_fmt);                  // a workgroup per (frame, channel slice, source tile)
 }
 
 // row softmax: one 256-thread block per row, the row lives in registers (<= 16 x float4 per thread), one HBM read

@@ -408,7 +408,7 @@ class RangeProfile:
         return self._cls.get(t.untyped_storage().data_ptr(), "unsplit")
 
     def _site(self, pk, key, site) -> str:
-        if key is None:
+        if key is None or site is not None:
             owner, name = site if site is not None else (None, "stacked")
         else:
             owner, name = getattr(pk, "owner", None), ".".join(str(k) for k in (key if isinstance(key, tuple) else (key,)))
@@ -559,6 +559,12 @@ def pk_conv3x3(w: torch.Tensor, cin_pad: Optional[int] = None, lo: bool = False)
     return p.reshape(co, 9 * cp).contiguous()
 
 
+def pk_conv3x3_taps(w: torch.Tensor, lo: bool = False) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> the linear weight [9*Cout, Cin] whose row (u*3 + v)*Cout + n is W[n, :, u, v]: the nine taps of a 3x3 conv
+    as nine column blocks of ONE plain-A GEMM on the conv's source pixels (Upsample at source resolution, pnc_upsample_combine)"""
+    return pk_linear(w.detach().permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]), lo)
+
+
 def pk_conv1d(w: torch.Tensor, lo: bool = False) -> torch.Tensor:
     """[Cout, Cin, 3] -> [Cout, 3*Cin] with K ordered (dt, ci); (ci/64, dt, ci%64) when Cin % 64 == 0 (include/panacea_hip.h:
     the three taps of a 64-channel slice become adjacent K tiles)."""
@@ -662,6 +668,21 @@ GN_EPILOGUE_CHUNK = 64      # pixels per record of PncGemmParams.gn_part (the te
 GN_FROM_EPILOGUE = True     # False (bench.py --no-gn-epilogue, A/B): every spatial GroupNorm launches its own statistics kernel
 EMB_BATCH = os.environ.get("PNC_EMB_BATCH", "1") != "0"      # A/B: "0" = one emb_layers launch per ResBlock3D (rounds 1-4)
 TEXTKV_ONE_GEMM = os.environ.get("PNC_TEXTKV_ONE_GEMM", "1") != "0"      # A/B: "0" = text K/V of a network as one GEMM per width
+# A/B: "0" = the denoiser's Upsample convs as one 9-tap implicit GEMM at the OUTPUT resolution (rounds 1-6); default: the nine taps as
+# a plain-A GEMM on the source pixels + pnc_upsample_combine (nn.openaimodel.Upsample)
+UPSAMPLE_SOURCE_RES = os.environ.get("PNC_UPSAMPLE_SOURCE_RES", "1") != "0"
+UPSAMPLE_CHUNK_FRAMES = int(os.environ.get("PNC_UPSAMPLE_CHUNK_FRAMES", "0"))      # sweeps / tests: > 0 forces the frames per chunk
+
+
+def upsample_chunk_frames(F: int, Hin: int, Win: int, Cout: int) -> int:
+    """Frames per GEMM + combine round of an Upsample at source resolution: a pure function of the shapes.  The sweep over 1, 2, 4, 8
+    and 16 frames (profiles/upsample_source_res.md) shows no chunk size that beats all 16 frames at once by more than the run-to-run
+    spread at the two large sites — a P that fits the Infinity Cache speeds the combine up and slows the GEMM down by as much — and
+    small chunks lose up to 3x at the small one, so the rule is the whole batch, cut only where P (36 * Cout bytes per source pixel)
+    would pass 2 GiB (the 16-frame level 1->0 site holds 1.13 GB)."""
+    if UPSAMPLE_CHUNK_FRAMES > 0:
+        return min(F, UPSAMPLE_CHUNK_FRAMES)
+    return max(1, min(F, (1 << 31) // (36 * Cout * Hin * Win)))
 
 
 def gn_records(rt: Runtime, F: int, N: int) -> Optional[torch.Tensor]:
@@ -784,7 +805,8 @@ def gemm(rt: Runtime, a: Operand, pk, key, out: Optional[Operand] = None, *, w_l
     Under a policy that hands the twin over BESIDE the launch (`precise-ckpt`, weights_beside) the fp16 lo twin goes along as `w_lo16`
     for every state of a.lo, next to whatever the list above says.
     `key=None`: `pk` is W itself, a stacked matrix that is no Packable's (TextKVProjector, EmbProjector), and `w_lo` its lo twin — used
-    under the same conditions as a module's.  `site` = (owning network, fixed name) names such a matrix in a range profile.
+    under the same conditions as a module's.  `site` = (owning network, fixed name) names such a matrix in a range profile; with a key it
+    names the launch of a SECOND packing of a module's weight (Upsample's `w9`) like the launch of the first, (module, "w")).
     With a range profile on (rt.profile, UNetModel3D.profile_ranges) the planes of `a` are observed ahead of the launch, on its stream."""
     w = pk
     if key is not None:

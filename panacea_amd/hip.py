@@ -150,6 +150,7 @@ _SIGNATURES = {
     "pnc_concat_add_stats": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "pnc_add_f32": (_I, [_P, _P, _L, _P, _P, _P, _I, _P]),
     "pnc_cast_f16": (_I, [_P, _L, _P, _P, _I, _P]),
+    "pnc_upsample_combine": (_I, [_P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "pnc_range_monitor_collect": (_I, [_P, _P]),
     "pnc_operand_stats_f16": (_I, [_P, _P, _I, _L, _I, _L, _P, _P]),
     "pnc_u8_to_tokens_f16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -690,6 +691,21 @@ def concat_add(a32, C1, s32, c32, C2, M, out32, out16, out16_lo=None, gn_part=No
 def add_f32(x32, a32, n, y32, y16, y16_lo=None):
     _check(_timed("elementwise", 0.0, 12.0 * n, load().pnc_add_f32, _ptr(x32), _ptr(a32), n, _ptr(y32), _ptr(y16),
                   _ptr(y16_lo), lo_fmt(y16_lo), _stream()), "pnc_add_f32")
+
+
+def upsample_combine(P, ldp, bias, F, Hin, Win, Cout, out32, out16=None, out16_lo=None):
+    """pnc_upsample_combine: the nine tap products P [F * Hin * Win, ldp >= 9 * Cout] fp32 of a nearest-x2 Upsample conv, one row per
+    SOURCE pixel (column (u * 3 + v) * Cout + n), summed with `bias` into out32 [F * 2 Hin * 2 Win, Cout] (+ its fp16 / lo planes)"""
+    rows, outs = F * Hin * Win, 4 * F * Hin * Win * Cout
+    short = [t for t in (out32, out16, out16_lo) if t is not None and t.numel() < outs]      # (the library sees pointers only)
+    if P.numel() < (rows - 1) * ldp + 9 * Cout or short:
+        raise PncError(f"upsample_combine: P holds {rows} rows of {9 * Cout} products (ldp {ldp}) and every output {outs} elements")
+    fmt = lo_fmt(out16_lo)
+    nb = 36.0 * rows * Cout + outs * (4.0 + (2.0 if out16 is not None else 0.0) + _lo_bytes(out16_lo))
+    _check(_timed("upsample_combine", 0.0, nb, load().pnc_upsample_combine, _ptr(P, torch.float32, "P"), ldp,
+                  _ptr(bias, torch.float32, "bias"), F, Hin, Win, Cout, _ptr(out32, torch.float32, "out32"),
+                  _ptr(out16, torch.float16, "out16"), _ptr(out16_lo, LO_DTYPE[fmt], "out16_lo"), fmt, _stream()),
+           "pnc_upsample_combine")
 
 
 def range_monitor_collect(out_i32: torch.Tensor):

@@ -121,7 +121,7 @@ class Upsample(nn.Module, Packable):
 
     def _pack(self, lo=False):
         w, b = conv_params(self.conv, lo)
-        return dict(w=w, b=b)
+        return dict(w=w, b=b, w9=E.pk_conv3x3_taps(self.conv.weight, lo))      # w: the output-resolution conv (fallback, A/B partner)
 
     # the conv's operand as a precise pair (class `stream`).  False (bench.py --upsample-plain-operand, an A/B of the error budget):
     # the three Upsample convs of the UNet decoder read the fp16 plane only — their e4m3 lo pass is 1.6 ms of the step
@@ -132,8 +132,27 @@ class Upsample(nn.Module, Packable):
         x16 = x.need_f16(rt)
         if not self.precise_operand:
             x16 = E.Operand(x16.hi)
-        return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk, "w", self.out_channels, pk["b"], upsample=True, out16=want_f16,
-                           split_out="stream")
+        Co = self.out_channels
+        # (an OPTIONAL entry of the backend: the torch emulation of the C-ABI the CPU tests run on has none and keeps the conv below)
+        combine = getattr(rt.be, "upsample_combine", None)
+        if not (E.UPSAMPLE_SOURCE_RES and combine is not None and rt.vshard is None and x.C % 64 == 0 and Co % 4 == 0):
+            return run_conv3x3(rt, x16, x.F, x.H, x.W, x.C, pk, "w", Co, pk["b"], upsample=True, out16=want_f16, split_out="stream")
+        # Multiply at SOURCE resolution: neighbouring output pixels read the same source pixel through the same tap, so only 9 of the
+        # 36 products per source pixel of the output-resolution conv are distinct.  P = x @ w9^T holds them (the hi and lo passes of any
+        # `stream` operand, as engine.gemm runs them); pnc_upsample_combine adds each output pixel's nine, in tap order, to the bias.
+        # Frames go in chunks (engine.upsample_chunk_frames) over ONE P buffer: the launches of a stream run in order.
+        N, Mo = x.N, 4 * x.M
+        o32 = rt.empty((Mo, Co), torch.float32)
+        o16 = rt.operand((Mo, Co), "stream") if want_f16 else None
+        fc = E.upsample_chunk_frames(x.F, x.H, x.W, Co)
+        P = rt.empty((fc * N, 9 * Co), torch.float32)
+        for f0 in range(0, x.F, fc):
+            nf = min(fc, x.F - f0)
+            E.gemm(rt, x16.map(lambda t: t[f0 * N:(f0 + nf) * N]), pk, "w9", site=(self, "w"), M=nf * N, N=9 * Co, K=x.C, lda=x.C,
+                   out32=P, ldc32=9 * Co)
+            outs = [None if t is None else t[4 * f0 * N:] for t in (o32, *(o16 or (None, None)))]
+            combine(P, 9 * Co, pk["b"], nf, x.H, x.W, Co, *outs)
+        return Act(x.F, 2 * x.H, 2 * x.W, Co, f32=o32, f16=o16)
 
 
 class Downsample(nn.Module, Packable):
