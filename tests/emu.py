@@ -564,7 +564,9 @@ def nchw_to_tokens_f16(a32, C1, b32, C2, F, Npix, Cpad, out16, out16_lo=None, a_
 
 # ---- sampler exits (pnc_cfg_euler_step[_skip], pnc_cfg_sampler_step[_skip]) -----------------------------------------------------
 # The reference's torch ops in the reference's order (denoiser.py:22-28, guiders.py:25-29, sampling.py:85-365) on channels-last eps
-# tokens.  The HIP kernels are held to the same trajectories on the MI355X (tests/test_samplers_gpu.py, tests/test_denoisers_gpu.py).
+# tokens.  The HIP kernel is held to these BITS on the MI355X, per mode, entry, selector and aliased launch, in poisoned allocations
+# (tests/test_sampler_exit_gpu.py against the per-op reference tests/sampler_exit_ref.py, which tests/test_sampler_exit_ref.py ties
+# to this emulation bit for bit); the trajectories of tests/test_samplers_gpu.py / tests/test_denoisers_gpu.py sit on top of that.
 def _denoised(eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, c_skip):
     """(X [T, C, Npix], guided D).  `c_skip` None: the eps path, D_h = E_h * c_out + X; else D_h = E_h * c_out + X * c_skip
     (denoiser.py:28) with both products and the sum rounded on their own.  Then CFG."""
