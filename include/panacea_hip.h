@@ -133,6 +133,11 @@ int pnc_set_option(int option, int value);
  *     v += res1[m*ldr1+n] + res2[m*ldr2+n]          (fp32 residual stream)
  *     out32[m*ldc32+n] = v;  out16[m*ldc16+n] = (fp16)v  for n <  n_split
  *     out16t[(m/t_rows)*t_gstride + (n-n_split)*ldt + m%t_rows] = (fp16)v for n >= n_split
+ *   RANGE of the operands: every finite fp16 value, subnormals included — nothing is flushed.  The accumulation is fp32 with an
+ *   error relative to sum |a| |w|, with one exception the MI355X's fp16 MFMA makes: a product with an fp16-SUBNORMAL factor
+ *   (below 2^-14) is exact going in but is aligned in the adder as if that factor were 2^-14, so its truncation is relative to
+ *   2^-14 |other factor|, not to the product.  A row of A that lies entirely at 2^-24 therefore keeps ~14 of fp32's 24 bits; from
+ *   2^-14 on the full precision holds.  (tests/test_gemm_range_gpu.py; tests/gemm_ref64.py MFMA_UNNORMALISED_SUBNORMALS.)
  * ------------------------------------------------------------------------- */
 enum { PNC_A_PLAIN = 0, PNC_A_CONV3X3 = 1, PNC_A_CONV1D_T = 2 };
 /* Storage format of the lo plane of a precise ("split") operand, r = (v - fp16(v)) * 2^11  (PncGemmParams.A_lo):
@@ -147,7 +152,12 @@ enum { PNC_A_PLAIN = 0, PNC_A_CONV3X3 = 1, PNC_A_CONV1D_T = 2 };
  *                 The denoiser's split operands are normalised activations and fp16 copies of the residual stream; the three
  *                 parity pins (synthetic weights) do not probe the range, and the published checkpoint is not available offline
  *                 to measure its stream.  A caller whose operands reach the hundreds keeps PNC_LO_F16 for them
- *                 (engine.Precision(lo8=False), policy "precise-f16lo").  tests/test_lo8_gpu.py holds values of 700, 1200, 60000. */
+ *                 (engine.Precision(lo8=False), policy "precise-f16lo").  tests/test_lo8_gpu.py holds values of 700, 1200, 60000;
+ *                 tests/test_gemm_range_gpu.py holds the GEMM family over the whole range below 65504: as a CONSUMER (A_lo bytes from
+ *                 e4m3's subnormals to the +-448 of a clamped producer, w_lo_exp from 96 to 130) and as a PRODUCER — a launch that
+ *                 writes out32 next to an e4m3 out16_lo writes out16 = fp16(out32) and the byte e4m3(clamp((out32 - out16) * 2^11))
+ *                 exactly, at any magnitude; beyond the clamp |v - (out16 + 2^-11 out16_lo)| <= |v - out16|, and no written byte is
+ *                 the NaN code 0x7F / 0xFF. */
 enum { PNC_LO_F16 = 0, PNC_LO_E4M3 = 1 };
 enum { PNC_ACT_NONE = 0, PNC_ACT_SILU = 1, PNC_ACT_GELU = 2 /* erf GELU: open_clip text-tower MLP */ };
 
@@ -560,7 +570,12 @@ int pnc_upsample_combine(const float* P, int64_t ldp, const float* bias, int F, 
  * autocast fp16 path overflows at 65504 without notice, sgm/modules/diffusionmodules/wrappers.py:37-70).  Every kernel that packs an
  * e4m3 lo plane counts the packed quads that clamped; this call ADDS the counts since the previous call to *out (a device word the
  * caller zeroes) on `stream` and resets them — a handful of one-thread launches, once per network evaluation.  0 = the evaluation
- * stayed inside the range its contract is written for. */
+ * stayed inside the range its contract is written for.
+ * UNIT.  (count > 0) == (a packed residual was beyond +-448) is the contract; the number itself is in the unit of the writer.  The
+ * vector writers — the helpers, every fast GEMM epilogue and the split-K reduce — pack ALIGNED QUADS (columns 4 q .. 4 q + 3 of a row)
+ * and count a quad once, however many of its four residuals clamp.  The generic GEMM epilogue (N % 8 != 0, leading dimensions or
+ * pointers outside the vector contract, option sets without a specialised variant such as GELU next to out32) packs one element per
+ * call and counts clamped ELEMENTS.  tests/test_gemm_range_gpu.py holds both, from the launch's own out32. */
 int pnc_range_monitor_collect(unsigned int* out, void* stream);
 
 /* Range profile of ONE contraction operand (a diagnostic pass: UNetModel3D.profile_ranges; the denoising path never launches it).
