@@ -43,7 +43,8 @@ const char* pnc_version(void);
  *  PncGemmParams.W_lo with A_lo = NULL, which pnc_gemm_f16 used to ignore, is now PNC_EINVAL — clear the field with A_lo;
  *  still 8 (additive): + pnc_attn_uses_text_kernel.  One dispatch is narrower: the few-key kernel takes key buffers whose row count
  *  kvH * kvW is a multiple of 8 only, a ragged buffer (77 rows) runs on the general kernel — same attention, see PncAttnParams.kv_valid;
- *  still 8 (additive): + pnc_gemm_wsplit_f16) */
+ *  still 8 (additive): + pnc_gemm_wsplit_f16;
+ *  still 8 (additive): + pnc_frames_renoise) */
 #define PNC_ABI_VERSION 8
 int pnc_abi_version(void);
 /* hex SHA-256 of the sources + compile flags the library was built from (panacea_amd/build.py computes the same digest over
@@ -530,6 +531,26 @@ int pnc_cfg_euler_step_skip(const float* eps_tok, int ld, int T, int Npix, int C
                             const float* x, const float* c_skip, const float* c_out, const float* sigma,
                             const float* sigma_next, float* x_next, void* stream);
 int pnc_cfg_sampler_step_skip(const PncSamplerStepParams* p, const float* c_skip, void* stream);
+/* Known frames put back at a noise level: the start of a schedule from a recorded clip and, after every step, the frames the
+ * caller keeps (clip editing).  Additive under ABI 8.  z, noise, x, out NCHW [T][C][Npix] fp32 — the latent layout of the exit
+ * entries above; sigma, keep [T] fp32 on the device.  For frame t
+ *   keep[t] > 0   : out[t] = z[t] + noise[t] * sigma[t]     the product rounded to fp32, then the sum (no FMA contraction, as the
+ *                                                           exits above); where sigma[t] == 0 out[t] is z[t] bit for bit and
+ *                                                           noise[t] is not read (NaN noise is inert there)
+ *   otherwise     : out[t] = x[t] bit for bit               keep[t] 0.0, -0.0, negative or NaN; with out == x the frame is not
+ *                                                           touched at all
+ * keep == NULL keeps every frame; x may be NULL only then.  out may alias x element for element, never z or noise.  A frame's
+ * C * Npix floats are one contiguous run: it moves in 16-byte loads and stores between the 16-byte boundaries of out[t] when
+ * z[t] (x[t]) and noise[t] sit at out[t]'s offset from a boundary, with up to three single elements either side, and element
+ * by element otherwise; Npix need not be a multiple of 4.  Checked in this order, nothing is launched on a refusal:
+ *   PNC_EINVAL  a NULL z, noise, sigma or out (the selector lives on the device: the host never knows that nothing is kept), a
+ *               keep without x, T < 1, C < 1, Npix < 1, C * Npix > 2^40, T * ceil(C * Npix / 1024) >= 2^31;
+ *   PNC_EALIGN  any pointer not 4-byte aligned.
+ *    -> the noising `input + noise * append_dims(sigmas, input.ndim)` (sgm/modules/diffusionmodules/loss.py:61), which is also the
+ *       point a deterministic Euler step (sampling.py:96-133) reaches from z + noise * sigma when the denoised frame is z; the
+ *       reference has no sampling entry that starts from a clip */
+int pnc_frames_renoise(const float* z, const float* noise, const float* sigma, const float* keep, const float* x, float* out,
+                       int T, int C, int64_t Npix, void* stream);
 /* channels-last fp32 [F*Npix][ld] -> NCHW fp32 (first C columns) */
 int pnc_tokens_to_nchw_f32(const float* x, int ld, int F, int Npix, int C,
                            float* out, void* stream);

@@ -432,6 +432,62 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_kernel(const PncSamplerS
     }
 }
 
+// pnc_frames_renoise (include/panacea_hip.h): known frames put back at a noise level.  A frame is ONE contiguous run of L = C * Npix
+// floats (its C planes lie back to back), and a workgroup owns RN_SLICE consecutive elements of one frame: the selector, the sigma
+// and the alignment case are workgroup-uniform.  The run is cut at the 16-byte boundaries of `out`: up to three head elements, a
+// body of float4s, up to three tail elements.  The body runs as 16-byte loads and stores when the frame's operands sit at out's
+// offset from a boundary (the sampler's tensors do: same shape, allocator-aligned bases, whatever Npix is); operands at other
+// offsets take the frame element by element.  Every element is read before it is written and only by the thread that writes it,
+// so out may be x.  The product is rounded on its own, then the sum (guided_denoised's discipline).
+constexpr int RN_SLICE = 1024;
+
+__device__ __forceinline__ float renoised(float a, float n, float s) {
+#pragma clang fp contract(off)
+    const float p = n * s;
+    return a + p;
+}
+
+__global__ __launch_bounds__(256) void frames_renoise_kernel(const float* __restrict__ z, const float* __restrict__ noise,
+                                                             const float* __restrict__ sigma, const float* __restrict__ keep,
+                                                             const float* x, float* out, int64_t L, int slices) {
+    const int t = (int)(blockIdx.x / (unsigned)slices), b = (int)(blockIdx.x - (unsigned)t * (unsigned)slices);
+    const int tid = threadIdx.x;
+    const bool kept = keep ? keep[t] > 0.0f : true;                  // 0.0, -0.0, negative, NaN: not kept
+    if (!kept && x == out) return;                                   // the frame is where it belongs: not touched
+    const float s = kept ? sigma[t] : 0.0f;
+    const bool add = kept && s != 0.0f;                              // sigma 0: z's bits, the noise is not read
+    const float* a = (kept ? z : x) + (int64_t)t * L;
+    const float* n = noise + (int64_t)t * L;
+    float* o = out + (int64_t)t * L;
+    const unsigned off = (unsigned)((uintptr_t)o & 15);
+    const bool vec = ((uintptr_t)a & 15) == off && (!add || ((uintptr_t)n & 15) == off);
+    if (!vec) {                                                      // element by element, a slice per workgroup
+#pragma unroll
+        for (int k = 0; k < RN_SLICE / 256; ++k) {
+            const int64_t j = (int64_t)b * RN_SLICE + k * 256 + tid;
+            if (j < L) o[j] = add ? renoised(a[j], n[j], s) : a[j];
+        }
+        return;
+    }
+    const int64_t head = min((int64_t)((16 - off) & 15) >> 2, L);   // elements in front of out's first 16-byte boundary
+    const int64_t nv = (L - head) >> 2;                             // whole float4s behind it (<= slices * 256)
+    const int64_t i = (int64_t)b * 256 + tid;
+    if (i < nv) {
+        const int64_t j = head + i * 4;
+        f32x4 v = *reinterpret_cast<const f32x4*>(a + j);
+        if (add) {
+            const f32x4 w = *reinterpret_cast<const f32x4*>(n + j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = renoised(v[e], w[e], s);
+        }
+        *reinterpret_cast<f32x4*>(o + j) = v;
+    }
+    if (b == 0 && tid < 8) {                                         // lanes 0..3: the head, lanes 4..7: the tail
+        const int64_t j = tid < 4 ? tid : head + nv * 4 + (tid - 4);
+        if (tid < 4 ? j < head : j < L) o[j] = add ? renoised(a[j], n[j], s) : a[j];
+    }
+}
+
 inline hipStream_t hip_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
 
 // every launch of this file: 256-thread workgroups over n threads' worth of work (a thread per item: n items; a wave per item:
@@ -503,6 +559,17 @@ extern "C" int pnc_cfg_sampler_step(const PncSamplerStepParams* pp, void* stream
 
 extern "C" int pnc_cfg_sampler_step_skip(const PncSamplerStepParams* pp, const float* c_skip, void* stream) {
     return cfg_sampler_step_launch(pp, c_skip, true, false, stream);
+}
+
+extern "C" int pnc_frames_renoise(const float* z, const float* noise, const float* sigma, const float* keep, const float* x,
+                                  float* out, int T, int C, int64_t Npix, void* stream) {
+    // the selector lives on the device: the host never knows that nothing is kept, so z and noise are always wanted
+    if (!z || !noise || !sigma || !out || (keep && !x) || T < 1 || C < 1 || Npix < 1) return PNC_EINVAL;
+    if (Npix > ((int64_t)1 << 40) / C) return PNC_EINVAL;            // a frame of at most 2^40 elements ...
+    const int64_t L = (int64_t)C * Npix, slices = (L + RN_SLICE - 1) / RN_SLICE;
+    if ((int64_t)T * slices >= ((int64_t)1 << 31)) return PNC_EINVAL;  // ... and a grid the launch can count
+    if (((uintptr_t)z | (uintptr_t)noise | (uintptr_t)sigma | (uintptr_t)keep | (uintptr_t)x | (uintptr_t)out) & 3) return PNC_EALIGN;
+    return launch_1d(frames_renoise_kernel, (int64_t)T * slices * 256, stream, z, noise, sigma, keep, x, out, L, (int)slices);
 }
 
 extern "C" const char* pnc_version(void) { return "panacea_hip 0.4.0 gfx950"; }

@@ -155,6 +155,7 @@ _SIGNATURES = {
     "pnc_operand_stats_f16": (_I, [_P, _P, _I, _L, _I, _L, _P, _P]),
     "pnc_u8_to_tokens_f16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pnc_tokens_to_u8": (_I, [_P, _I, _L, _I, _P, _P]),
+    "pnc_frames_renoise": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _P]),
 }
 
 _lib = None
@@ -669,6 +670,27 @@ def cfg_sampler_step(mode, eps_tok, ld, T, Npix, Cch, cfg, scale, x, c_out, v, o
     nbytes = T * Npix * Cch * (4.0 * planes + (4.0 if cfg else 0.0))
     name, skip = _sibling("pnc_cfg_sampler_step", "_skip", c_skip, "c_skip", f32)
     _check(_timed("elementwise", 0.0, nbytes, getattr(load(), name), C.byref(p), *skip, _stream()), name)
+
+
+def frames_renoise(z, noise, sigma, out, keep=None, x=None):
+    """pnc_frames_renoise on (T, C, ...) fp32 latents: out[t] = z[t] + noise[t] * sigma[t] where keep[t] > 0 (`keep` None: every
+    frame), x[t] elsewhere; `sigma`, `keep`: [T] fp32 on the device.  `out` may be `x` (frames that are not kept stay untouched)"""
+    f32 = torch.float32
+    T, Cch = z.shape[0], z.shape[1]
+    planes = [("z", z), ("noise", noise), ("out", out)] + ([] if x is None else [("x", x)])
+    for name, t in planes:
+        if t.shape != z.shape or not t.is_contiguous():
+            raise PncError(f"frames_renoise: {name} is a contiguous {tuple(z.shape)} latent, got {tuple(t.shape)} "
+                           f"(contiguous: {t.is_contiguous()})")
+    for name, t in (("sigma", sigma), ("keep", keep)):
+        if t is not None and (t.shape != (T,) or not t.is_contiguous()):
+            raise PncError(f"frames_renoise: {name} is a contiguous [{T}] vector, got {tuple(t.shape)}")
+    if keep is not None and x is None:
+        raise PncError("frames_renoise: frames that are not kept come from `x`")
+    Npix = z[0, 0].numel() if z.dim() > 2 else 1
+    _check(_timed("elementwise", 0.0, 12.0 * z.numel(), load().pnc_frames_renoise, _ptr(z, f32, "z"), _ptr(noise, f32, "noise"),
+                  _ptr(sigma, f32, "sigma"), _ptr(keep, f32, "keep"), _ptr(x, f32, "x"), _ptr(out, f32, "out"), T, Cch, Npix,
+                  _stream()), "pnc_frames_renoise")
 
 
 def tokens_to_nchw_f32(x32, ld, F, Npix, Cch, out32):

@@ -18,6 +18,8 @@ evaluation of the next window.  Nothing here changes with the policy.
 """
 from __future__ import annotations
 
+import math
+import operator
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -141,3 +143,74 @@ def rollout_frames(network, first_stage_dec, first_stage_enc, anchor_u8: torch.T
             frame = frames[far]
             out.append(frames if k == 0 else frames[:-1] if anchor == "last" else frames[1:])
     return torch.cat(out[::-1] if anchor == "last" else out)
+
+
+def edit_start_step(strength: float, num_steps: int) -> int:
+    """the schedule index an edit of `strength` in (0, 1] starts at: min(num_steps - 1, floor((1 - strength) * num_steps)).  1.0
+    starts at the first sigma (the clip only seeds the noise's mean), a small strength runs the last steps only."""
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength: a number in (0, 1], got {strength!r}")
+    return min(num_steps - 1, int(math.floor((1.0 - strength) * num_steps)))
+
+
+def edit_frames(network, first_stage_dec, first_stage_enc, frames_u8: torch.Tensor, cond: Dict[str, torch.Tensor],
+                uc: Dict[str, torch.Tensor], noise: torch.Tensor, *, strength: float = 0.6, keep: Sequence[int] = (),
+                num_steps: int = 25, cfg_scale: float = 5.0, sampler=None, denoiser=None, generator=None,
+                sample_posterior: bool = True, scale_factor: float = SCALE_FACTOR, hoist: bool = True, callback=None) -> torch.Tensor:
+    """A recorded clip re-rendered under `cond` / `uc` (another prompt, another layout), on one device: frames_u8 (T, H, W, 3) uint8
+    -> (T, H, W, 3) uint8.  The clip is encoded (z = scale_factor * first_stage_enc.encode_u8(frames_u8): a posterior draw from
+    `generator`, or the mean without `sample_posterior`), noised to the level the schedule has at
+    start_step = edit_start_step(strength, num_steps) with the ONE draw `noise` (T, 4, h, w), sampled from there on, and decoded by
+    first_stage_dec.decode_u8(z_out / scale_factor).  The frame slots in `keep` come out as the clip's own latents (what the first
+    stage makes of the recorded frames): they are put back at every noise level (sampling.ClipSource), so the frames between them
+    are generated next to them — keep=(0, T - 1) fills in between two given frames.
+
+    cond, uc: as sample_frames takes them, `concat` included.  T has to be the network's `num_frames`.  sampler, denoiser, num_steps,
+    cfg_scale, hoist: see sample_frames; kept frames need a sampler that serves them (sampling.ClipSource).  `callback(i, x)` sees the
+    latent after every step.
+
+    Refused before the first launch: first stages without encode_u8 / decode_u8 (TypeError), a backend without pnc_frames_renoise or
+    the image-boundary kernels (NotImplementedError), a network carrying a frame or view shard (NotImplementedError: one device), a
+    malformed clip or `noise`, T != num_frames, `strength` outside (0, 1] and `keep` slots outside 0 .. T-1 (ValueError)."""
+    if not hasattr(first_stage_dec, "decode_u8"):
+        raise TypeError(f"edit_frames needs a first stage with decode_u8; {type(first_stage_dec).__name__} has none")
+    if not hasattr(first_stage_enc, "encode_u8"):
+        raise TypeError(f"edit_frames needs a first stage with encode_u8; {type(first_stage_enc).__name__} has none")
+    for name in ("tokens_to_u8", "u8_to_tokens_f16"):
+        image.capability(engine.backend(), name)
+    sampling._renoise_capability()
+    model = network.diffusion_model
+    for m in (model, getattr(model, "controlnet", None)):
+        if getattr(m, "frame_shard", None) is not None or getattr(m, "view_shard", None) is not None:
+            raise NotImplementedError("edit_frames runs on one device: the network carries a frame or view shard")
+    if not isinstance(noise, torch.Tensor) or noise.dim() != 4 or 0 in noise.shape:
+        raise ValueError(f"noise: one (T, 4, h, w) draw, got "
+                         f"{tuple(noise.shape) if isinstance(noise, torch.Tensor) else type(noise).__name__}")
+    T, (h, w) = noise.shape[0], noise.shape[2:]
+    if T != model.num_frames:
+        raise ValueError(f"noise carries {T} frames, the network was built for num_frames = {model.num_frames}")
+    f = frames_u8
+    if (not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 4 or f.shape[0] != T or f.shape[3] != 3
+            or f.shape[1] % h or f.shape[2] % w or f.shape[1] // h != f.shape[2] // w):
+        raise ValueError(f"frames_u8: a ({T}, H, W, 3) uint8 clip at a multiple of the {h} x {w} latent, got "
+                         f"{tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__}"
+                         f"{' ' + str(f.dtype) if isinstance(f, torch.Tensor) else ''}")
+    try:
+        keep = tuple(operator.index(s) for s in keep)
+    except TypeError:
+        raise ValueError(f"keep: frame slots (integers) expected, got {keep!r}") from None
+    if any(not 0 <= s < T for s in keep) or len(set(keep)) != len(keep):
+        raise ValueError(f"keep: distinct frame slots in 0 .. {T - 1} expected, got {keep}")
+    smp, den = _sampler_stack(noise.device, num_steps, cfg_scale, sampler, denoiser)
+    start_step = edit_start_step(strength, smp.num_steps)
+    why = smp._keep_refusal() if keep else None
+    if why is not None:
+        raise NotImplementedError(f"{type(smp).__name__} does not keep frames {why}")
+    with torch.no_grad():
+        z = scale_factor * first_stage_enc.encode_u8(f.to(noise.device), generator=generator, sample=sample_posterior)
+        if z.shape != noise.shape:
+            raise ValueError(f"the first stage encodes the clip to {tuple(z.shape)}, noise is {tuple(noise.shape)}")
+        source = sampling.ClipSource(z.to(torch.float32), noise.to(torch.float32), keep)
+        z_out = smp(sampling.BoundDenoiser(den, network), None, cond, uc, network=network if hoist else None, callback=callback,
+                    start_step=start_step, source=source)
+        return first_stage_dec.decode_u8(z_out / scale_factor)

@@ -18,6 +18,7 @@ These are a handful of elementwise torch ops per step; the arithmetic that matte
 """
 from __future__ import annotations
 
+import operator
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
@@ -201,16 +202,128 @@ class BoundDenoiser:
         return self.denoiser(self.network, x, sigma, cond)
 
 
+def _renoise_capability():
+    """the backend's `frames_renoise` wrapper (pnc_frames_renoise), an optional capability looked up by name the way image.py looks up
+    the image-boundary kernels; NotImplementedError when the backend has none (nothing has been launched then)"""
+    from . import engine as E
+    fn = getattr(E.backend(), "frames_renoise", None)
+    if fn is None:
+        raise NotImplementedError("this backend has no `frames_renoise`: a clip source needs pnc_frames_renoise of "
+                                  "include/panacea_hip.h")
+    return fn
+
+
+class ClipSource:
+    """A recorded clip to start a schedule from (clip editing): `z` (T, C, h, w) fp32, the clip's latents already multiplied by
+    scale_factor; `noise`, ONE fixed draw of that shape; `keep`, the frame slots (0 .. T-1, each once, possibly none) that come out
+    as they went in.  The schedule starts at z + sigmas[start_step] * noise, and after every step the kept frames are rewritten as
+    z + sigma_next * noise: with a fixed noise that is where a deterministic Euler step itself lands when the denoised frame is z
+    (x + (sigma_next - sigma) * (x - z) / sigma at x = z + sigma * noise), so the other frames are denoised next to frames that sit
+    at their own noise level, and the kept frames are z exactly once sigma_next is 0.  Both are one pnc_frames_renoise launch."""
+
+    def __init__(self, z: torch.Tensor, noise: torch.Tensor, keep=()):
+        for name, t in (("z", z), ("noise", noise)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise TypeError(f"ClipSource: {name} is an fp32 tensor, got "
+                                f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if z.dim() != 4 or 0 in z.shape:
+            raise ValueError(f"ClipSource: z is (T, C, h, w), got {tuple(z.shape)}")
+        if noise.shape != z.shape or noise.device != z.device:
+            raise ValueError(f"ClipSource: noise is one draw of z's shape {tuple(z.shape)} on its device, got {tuple(noise.shape)} "
+                             f"on {noise.device}")
+        try:
+            keep = tuple(operator.index(s) for s in keep)
+        except TypeError:
+            raise TypeError(f"ClipSource: keep holds frame slots (integers), got {keep!r}") from None
+        T = z.shape[0]
+        if any(not 0 <= s < T for s in keep):
+            raise ValueError(f"ClipSource: keep slots {keep} outside 0 .. {T - 1}")
+        if len(set(keep)) != len(keep):
+            raise ValueError(f"ClipSource: keep slots {keep} name a frame twice")
+        self.z, self.noise, self.keep = z.detach().contiguous(), noise.detach().contiguous(), tuple(sorted(keep))
+        self._keep_vec = None
+
+    def keep_vector(self) -> torch.Tensor:
+        """[T] fp32 on z's device: 1 for a kept frame, 0 elsewhere (made once)"""
+        if self._keep_vec is None:
+            self._keep_vec = torch.tensor([1.0 if t in self.keep else 0.0 for t in range(self.z.shape[0])], dtype=torch.float32,
+                                          device=self.z.device)
+        return self._keep_vec
+
+    def renoise(self, sigma: torch.Tensor) -> torch.Tensor:
+        """z + sigma * noise of every frame, a new latent; `sigma`: [T] fp32 on the device"""
+        out = torch.empty_like(self.z)
+        _renoise_capability()(self.z, self.noise, sigma.contiguous(), out)
+        return out
+
+    def put_back(self, x: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
+        """the kept frames of `x` rewritten IN PLACE as z + sigma * noise (the others are not touched; no launch when nothing is
+        kept); returns `x`"""
+        if self.keep:
+            _renoise_capability()(self.z, self.noise, sigma.contiguous(), x, keep=self.keep_vector(), x=x)
+        return x
+
+
+class _Edit:
+    """A ClipSource bound to one schedule: the [T] sigma vector of every schedule index as rows of ONE device tensor made up front
+    (frame-wise copies of the schedule's own fp32 sigmas), so the loop launches without a host sync."""
+
+    def __init__(self, source: ClipSource, sig: torch.Tensor, start_step: int):
+        self.source, self.start_step = source, start_step
+        self.rows = sig.to(torch.float32)[:, None].expand(-1, source.z.shape[0]).contiguous()
+
+    def start(self) -> torch.Tensor:
+        return self.source.renoise(self.rows[self.start_step])
+
+    def after(self, callback):
+        """`callback` behind the put-back of the step's output (the loops hand every step's latent to their callback)"""
+        if not self.source.keep:
+            return callback
+
+        def hook(i, x):
+            self.source.put_back(x, self.rows[i + 1])
+            if callback is not None:
+                callback(i, x)
+        return hook
+
+
 class _Sampler:
     """What every sampler mirror shares: BaseDiffusionSampler (sampling.py:24-76) and the device half of a fused step — the
     network's eps tokens of the CFG batch for one sigma, handed to an exit kernel."""
     fuse = True          # use the fused device step when the denoiser is a BoundDenoiser around the HIP network
+    keeps_frames = False  # ClipSource.keep: served where ONE network evaluation per step feeds the next and no noise is drawn
 
     def __init__(self, num_steps: int, guider: Optional[VanillaCFG] = None, discretization=None, device="cuda"):
         self.num_steps = num_steps
         self.discretization = discretization or LegacyDDPMDiscretization()
         self.guider = guider
         self.device = device
+
+    def _keep_refusal(self) -> Optional[str]:
+        """why this sampler as configured does not serve kept frames, or None"""
+        if hasattr(self.guider, "half"):
+            return "under parallel.ShardedCFG (one CFG half per rank)"
+        return None if self.keeps_frames else "(it evaluates the network twice per step or draws fresh noise)"
+
+    def _begin(self, sig: torch.Tensor, x, start_step: int, source: Optional[ClipSource], callback):
+        """The start of a schedule, checked before anything is launched -> (start_step, the hook that stands in for `callback`,
+        a function that makes the start latent).  Without a source the start latent is `x`, scaled by sqrt(1 + sigmas[0]^2) when the
+        schedule starts at its first sigma; with one it is z + sigmas[start_step] * noise and `x` is ignored."""
+        start_step = operator.index(start_step)
+        n = len(sig) - 1
+        if not 0 <= start_step < n:
+            raise ValueError(f"start_step {start_step} outside 0 .. {n - 1} (a schedule of {n} steps)")
+        if source is None:
+            return start_step, callback, (lambda: x * torch.sqrt(1.0 + sig[0] ** 2.0) if start_step == 0 else x)
+        if not isinstance(source, ClipSource):
+            raise TypeError(f"source: a sampling.ClipSource, got {type(source).__name__}")
+        why = self._keep_refusal() if source.keep else None
+        if why is not None:
+            raise NotImplementedError(f"{type(self).__name__} does not keep frames {why}: kept frames are served by EulerEDMSampler "
+                                      "without churn, DPMPP2MSampler and LinearMultistepSampler under VanillaCFG or no guider")
+        _renoise_capability()
+        edit = _Edit(source, sig, start_step)
+        return start_step, edit.after(callback), edit.start
 
     def sigmas(self, num_steps=None) -> torch.Tensor:
         return self.discretization(self.num_steps if num_steps is None else num_steps, device=self.device)
@@ -373,19 +486,29 @@ class EulerEDMSampler(_EDM):
         d = (x - denoised) / append_dims(sigma, x.ndim)
         return x + append_dims(next_sigma - sigma, x.ndim) * d
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None, callback=None):
+    keeps_frames = True
+
+    def _keep_refusal(self):
+        return "with churn (it draws fresh noise)" if self.s_churn > 0 else super()._keep_refusal()
+
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None, callback=None, start_step: int = 0,
+                 source: Optional[ClipSource] = None):
         """`network`: optional OpenAIWrapperControlLDM3D.  When given, the step invariants of the conditioning (text
         K/V of every cross-attention site, ControlNet hint stem) are computed once for the whole schedule instead of
         once per step; the trajectory is bit-identical to the plain loop.  `callback(i, x)` sees the
-        latent after every step."""
+        latent after every step.
+        `start_step`: the schedule index the loop begins at (`x` is then the latent at sigmas[start_step], taken as it is).
+        `source`: a ClipSource — the loop starts from the clip at sigmas[start_step] (`x` is ignored and may be None) and puts the
+        kept frames back after every step."""
         sig = self.sigmas(num_steps)
+        start_step, callback, start = self._begin(sig, x, start_step, source, callback)
         uc = cond if uc is None else uc
         if network is not None:
             cond, uc = hoist_invariants(network, self.guider, cond, uc)
-        x = x * torch.sqrt(1.0 + sig[0] ** 2.0)
+        x = start()
         s_in = x.new_ones([x.shape[0]])
         sig_f = self.host_sigmas(num_steps) if self.s_churn > 0 else None
-        for i in range(len(sig) - 1):
+        for i in range(start_step, len(sig) - 1):
             gamma = _churn_gamma(self.s_churn, self.s_tmin, self.s_tmax, sig_f[i], len(sig)) if sig_f else 0.0
             if gamma > 0:
                 x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc, gamma)
@@ -456,22 +579,25 @@ class _Scheduled(_Sampler):
             raise NotImplementedError(f"{type(self).__name__} does not run under parallel.ShardedCFG (one CFG half per rank); "
                                       "use VanillaCFG, or EulerEDMSampler for CFG-half sharding")
 
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None, callback=None):
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, network=None, callback=None, start_step: int = 0,
+                 source: Optional[ClipSource] = None):
         """`network`: hoist the step invariants once per schedule (they serve every evaluation of a step); `callback(i, x)`
-        sees the latent after every step."""
+        sees the latent after every step.  `start_step`, `source`: as EulerEDMSampler.__call__ takes them; a sampler that carries
+        a history (DPM++ 2M, LMS) starts at `start_step` with an empty one, as it does at step 0."""
         self._check_guider()
         sig, sig_f = self.sigmas(num_steps), self.host_sigmas(num_steps)
+        start_step, callback, start = self._begin(sig, x, start_step, source, callback)
         uc = cond if uc is None else uc
         if network is not None:
             cond, uc = hoist_invariants(network, self.guider, cond, uc)
-        x = x * torch.sqrt(1.0 + sig[0] ** 2.0)
+        x = start()
         s_in = x.new_ones([x.shape[0]])
         loop = self._fused_loop if self._fusable(denoiser, x, cond) else self._plain_loop
-        return loop(sig, sig_f, s_in, denoiser, x, cond, uc, callback)
+        return loop(sig, sig_f, s_in, denoiser, x, cond, uc, callback, start_step)
 
-    def _fused_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+    def _fused_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None, start=0):
         state = self._state(x)
-        for i, (form, sv, draw) in enumerate(self._steps(sig, sig_f, s_in)):
+        for i, (form, sv, draw) in enumerate(self._steps(sig, sig_f, s_in, start), start):
             if draw:
                 sv["noise"] = self.noise_sampler(x).to(torch.float32).contiguous()
             x = self._device_step(form, sv, x, denoiser, cond, uc, state).to(x.dtype)
@@ -502,16 +628,16 @@ class HeunEDMSampler(_EDM, _Scheduled):
         d_prime = (d + d_new) / 2.0
         return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x + d_prime * dt, euler_step)
 
-    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
-        for i, ((gamma, last), _, _) in enumerate(self._steps(sig, sig_f, s_in)):
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None, start=0):
+        for i, ((gamma, last), _, _) in enumerate(self._steps(sig, sig_f, s_in, start), start):
             x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc, gamma, last=last)
             if callback is not None:
                 callback(i, x)
         return x
 
-    def _steps(self, sig, sig_f, s_in):
+    def _steps(self, sig, sig_f, s_in, start=0):
         T = s_in.shape[0]
-        for i in range(len(sig_f) - 1):
+        for i in range(start, len(sig_f) - 1):
             gamma = _churn_gamma(self.s_churn, self.s_tmin, self.s_tmax, sig_f[i], len(sig_f))
             yield (gamma, _all_zero([sig_f[i + 1]] * T)), {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, gamma > 0
 
@@ -547,8 +673,8 @@ class _Ancestral(_Scheduled):
         return torch.where(append_dims(next_sigma, x.ndim) > 0.0,
                            x + self.noise_sampler(x) * self.s_noise * append_dims(sigma_up, x.ndim), x)
 
-    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
-        for i in range(len(sig_f) - 1):
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None, start=0):
+        for i in range(start, len(sig_f) - 1):
             x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc)
             if callback is not None:
                 callback(i, x)
@@ -568,8 +694,8 @@ class EulerAncestralSampler(_Ancestral):
         x = self.ancestral_euler_step(x, denoised, sigma, sigma_down)
         return self.ancestral_step(x, sigma, next_sigma, sigma_up)
 
-    def _steps(self, sig, sig_f, s_in):
-        for i in range(len(sig_f) - 1):
+    def _steps(self, sig, sig_f, s_in, start=0):
+        for i in range(start, len(sig_f) - 1):
             yield None, {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, True
 
     def _device_step(self, form, sv, x, denoiser, cond, uc, state):
@@ -609,16 +735,16 @@ class DPMPP2SAncestralSampler(_Ancestral):
             x = torch.where(append_dims(sigma_down, x.ndim) > 0.0, x_dpmpp2s, x_euler)
         return self.ancestral_step(x, sigma, next_sigma, sigma_up)
 
-    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
-        for i, (last, _, _) in enumerate(self._steps(sig, sig_f, s_in)):
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None, start=0):
+        for i, (last, _, _) in enumerate(self._steps(sig, sig_f, s_in, start), start):
             x = self.sampler_step(s_in * sig[i], s_in * sig[i + 1], denoiser, x, cond, uc, last=last)
             if callback is not None:
                 callback(i, x)
         return x
 
-    def _steps(self, sig, sig_f, s_in):
+    def _steps(self, sig, sig_f, s_in, start=0):
         T = s_in.shape[0]
-        for i in range(len(sig_f) - 1):
+        for i in range(start, len(sig_f) - 1):
             # sigma_down of the fp32 schedule, on the host (the reference sums it on the device)
             sd, _ = get_ancestral_step(torch.tensor([sig_f[i]]), torch.tensor([sig_f[i + 1]]), eta=self.eta)
             yield _all_zero([float(sd[0])] * T), {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}, True
@@ -640,6 +766,7 @@ class DPMPP2SAncestralSampler(_Ancestral):
 
 class DPMPP2MSampler(_Scheduled):
     """sampling.py:290-365: DPM-Solver++(2M); carries the previous step's denoised (a device plane)."""
+    keeps_frames = True
 
     def get_variables(self, sigma, next_sigma, previous_sigma=None):
         t, t_next = [to_neg_log_sigma(s) for s in (sigma, next_sigma)]
@@ -669,24 +796,24 @@ class DPMPP2MSampler(_Scheduled):
         x_advanced = mult[0] * x - mult[1] * denoised_d
         return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x_advanced, x_standard), denoised
 
-    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None, start=0):
         old = None
         T = s_in.shape[0]
-        for i in range(len(sig_f) - 1):
-            x, old = self.sampler_step(old, None if i == 0 else s_in * sig[i - 1], s_in * sig[i], s_in * sig[i + 1], denoiser, x,
+        for i in range(start, len(sig_f) - 1):
+            x, old = self.sampler_step(old, None if i == start else s_in * sig[i - 1], s_in * sig[i], s_in * sig[i + 1], denoiser, x,
                                        cond, uc, last=_all_zero([sig_f[i + 1]] * T))
             if callback is not None:
                 callback(i, x)
         return x
 
-    def _steps(self, sig, sig_f, s_in):
+    def _steps(self, sig, sig_f, s_in, start=0):
         T = s_in.shape[0]
-        for i in range(len(sig_f) - 1):
+        for i in range(start, len(sig_f) - 1):
             sv = {"sigma": s_in * sig[i], "next_sigma": s_in * sig[i + 1]}
-            if i > 0:
+            if i > start:
                 sv["previous_sigma"] = s_in * sig[i - 1]
-            # forms: "first" (no previous denoised), "last" (every next_sigma 0), "middle"
-            yield ("first" if i == 0 else "last" if _all_zero([sig_f[i + 1]] * T) else "middle"), sv, False
+            # forms: "first" (no previous denoised: the step the loop begins at), "last" (every next_sigma 0), "middle"
+            yield ("first" if i == start else "last" if _all_zero([sig_f[i + 1]] * T) else "middle"), sv, False
 
     def _state(self, x):
         return {"old": torch.empty(x.shape, dtype=torch.float32, device=x.device)}
@@ -730,15 +857,17 @@ class LinearMultistepSampler(_Scheduled):
     """sampling.py:176-211: linear multistep of `order` on the last `order` d = (x - denoised) / sigma.  The coefficients are
     computed once per schedule (float64) and enter the update as fp32 scalars, the way torch rounds a Python float."""
     MAX_FUSED_ORDER = 4          # pnc_cfg_sampler_step keeps up to 3 previous d
+    keeps_frames = True
 
     def __init__(self, num_steps: int, guider: Optional[VanillaCFG] = None, discretization=None, device="cuda", order=4):
         super().__init__(num_steps, guider, discretization, device)
         self.order = order
 
-    def coefficients(self, sig_f: List[float]) -> List[List[float]]:
+    def coefficients(self, sig_f: List[float], start: int = 0) -> List[List[float]]:
+        """the coefficients of steps start, start + 1, ...: the order grows from 1 at the step the loop begins at"""
         out = []
-        for i in range(len(sig_f) - 1):
-            cur = min(i + 1, self.order)
+        for i in range(start, len(sig_f) - 1):
+            cur = min(i - start + 1, self.order)
             out.append([linear_multistep_coeff(cur, sig_f, i, j) for j in range(cur)])
         return out
 
@@ -751,22 +880,22 @@ class LinearMultistepSampler(_Scheduled):
             ds.pop(0)
         return x + sum(coeff * d for coeff, d in zip(coeffs, reversed(ds)))
 
-    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None):
+    def _plain_loop(self, sig, sig_f, s_in, denoiser, x, cond, uc, callback=None, start=0):
         ds = []
-        for i, cs in enumerate(self.coefficients(sig_f)):
+        for i, cs in enumerate(self.coefficients(sig_f, start), start):
             x = self.sampler_step(s_in * sig[i], denoiser, x, cond, uc, ds, cs)
             if callback is not None:
                 callback(i, x)
         return x
 
-    def _steps(self, sig, sig_f, s_in):
+    def _steps(self, sig, sig_f, s_in, start=0):
         if self.order > self.MAX_FUSED_ORDER:
             raise NotImplementedError(f"the fused LMS step keeps at most {self.MAX_FUSED_ORDER - 1} previous d (order {self.order})")
-        co = self.coefficients(sig_f)
+        co = self.coefficients(sig_f, start)
         table = torch.tensor([c + [0.0] * (self.order - len(c)) for c in co], dtype=torch.float32)      # fp32 rounding of each
         table = table[:, :, None].expand(-1, -1, s_in.shape[0]).contiguous().to(s_in.device)
-        for i, cs in enumerate(co):
-            yield len(cs) - 1, {"sigma": s_in * sig[i], "coeffs": table[i, :len(cs)]}, False
+        for k, cs in enumerate(co):
+            yield len(cs) - 1, {"sigma": s_in * sig[start + k], "coeffs": table[k, :len(cs)]}, False
 
     def _state(self, x):
         return {"hist": [torch.empty(x.shape, dtype=torch.float32, device=x.device) for _ in range(self.order - 1)]}

@@ -12,6 +12,9 @@ per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference'
     python tools/sample.py --u8 --steps 5                 (uint8 channels-last BEV layout in, uint8 frames out: panacea_amd.image)
     python tools/sample.py --windows 4 --steps 5          (a video of 8 + 3 * 7 = 29 frames: windows chained on an anchor frame,
                                                            pipeline.rollout_frames; `--anchor first` rolls forward in time)
+    python tools/sample.py --edit --strength 0.6 --keep 0,7    (clip editing, pipeline.edit_frames: a first sample is decoded to uint8
+                                                           frames, then re-rendered under the swapped prompt from 60 % of the
+                                                           schedule on, frames 0 and 7 kept as they are)
 """
 import argparse, json, sys, time
 from pathlib import Path
@@ -94,9 +97,24 @@ def main():
     ap.add_argument("--anchor", choices=["last", "first"], default="last",
                     help="--windows: the anchor's slot in the conditioning clip (last = the reference's --use_last_frame: the video "
                          "grows backwards in time; first: forwards)")
+    ap.add_argument("--edit", action="store_true",
+                    help="clip editing (pipeline.edit_frames) on a synthetic clip: a first sample is decoded to uint8 frames, then edited "
+                         "under the other prompt; the timing printed is the edit's")
+    ap.add_argument("--strength", type=float, default=0.6,
+                    help="--edit: the share of the schedule that runs, in (0, 1]: the clip is noised to the level of step "
+                         "floor((1 - strength) * steps) and sampled from there")
+    ap.add_argument("--keep", default="", metavar="SLOTS", help="--edit: comma-separated frame slots kept as they are, e.g. 0,7")
     a = ap.parse_args()
     if a.windows < 0:
         ap.error("--windows takes N >= 1")
+    if a.edit and a.windows:
+        ap.error("--edit and --windows are two different runs")
+    try:
+        keep = tuple(int(s) for s in a.keep.split(",") if s.strip())
+    except ValueError:
+        ap.error("--keep takes comma-separated frame slots")
+    if keep and not a.edit:
+        ap.error("--keep belongs to --edit")
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
     net = build_network(kw)
@@ -121,6 +139,11 @@ def main():
         layout = (g["cond_feat"][T:] * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
         cond["cond_feat"] = uc["cond_feat"] = layout
     noise = torch.randn(T, 4, h, w, generator=torch.Generator().manual_seed(a.seed)).to(dev)
+    if a.edit:     # the synthetic clip: a first sample, decoded to bytes (not part of the edit's timing)
+        clip = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, denoiser=denoiser_config(a.prediction), output="uint8")
+        enc = first_stage_encoder(a, dev)
+        cond, uc = dict(cond, crossattn=g["crossattn"][0:1]), dict(uc, crossattn=g["crossattn"][1:2])       # "another prompt"
+        noise = torch.randn(T, 4, h, w, generator=torch.Generator().manual_seed(a.seed + 1)).to(dev)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     smp = sampling.from_config({"target": P + "sampling." + SAMPLERS[a.sampler],
                                 "params": {"num_steps": a.steps,
@@ -132,6 +155,10 @@ def main():
     with profiling as prof:
         if a.windows:
             frames = rollout(a, net, fs, smp, g, dev)
+        elif a.edit:
+            frames = pipeline.edit_frames(net, fs, enc, clip, cond, uc, noise, strength=a.strength, keep=keep, num_steps=a.steps,
+                                          sampler=smp, denoiser=denoiser_config(a.prediction),
+                                          generator=torch.Generator(device=dev).manual_seed(a.seed))
         else:
             frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
                                             denoiser=denoiser_config(a.prediction), output="uint8" if a.u8 else "float")
@@ -141,6 +168,10 @@ def main():
     if a.windows:
         what = (f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): {a.windows} windows of {T} frames, anchor {a.anchor}, "
                 f"{a.steps} steps each, {tuple(frames.shape)}")
+    if a.edit:
+        start = pipeline.edit_start_step(a.strength, a.steps)
+        what = (f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): edit of {T} frames at strength {a.strength} (steps "
+                f"{start} .. {a.steps - 1} of {a.steps}), kept {keep or 'none'}, encode + decode, {tuple(frames.shape)}")
     if u8:
         print(f"{what}: {dt:.2f} s (uint8, range {frames.min().item()} .. {frames.max().item()})")
     else:
@@ -155,18 +186,23 @@ def main():
     print("wrote", out)
 
 
+def first_stage_encoder(a, dev):
+    """the first-stage encoder with synthetic weights, or the checkpoint's `first_stage_model.*` like the decoder"""
+    enc = model.FirstStageEncoder(4, VAE, precision=a.first_stage_precision)
+    if a.ckpt:
+        print(enc.load_state_dict(checkpoint.denoiser_state_dict(checkpoint.read_state_dict(a.ckpt), "first_stage_model."), strict=False))
+    else:
+        enc.load_state_dict(synth.synth_state_dict({k: list(v.shape) for k, v in enc.state_dict().items()}), strict=True)
+    return enc.to(dev)
+
+
 def rollout(a, net, fs, smp, g, dev):
     """--windows: a synthetic anchor frame and one (cond, uc) pair per window -> the video's uint8 frames.  Window k reads the layouts
     of the video frames it covers (one synthetic layout per video frame, so neighbouring windows share the layout of the frame where
     they meet); the first-stage encoder gets synthetic weights, or the checkpoint's `first_stage_model.*` like the decoder."""
     T, W = a.frames, a.windows
     N = T + (W - 1) * (T - 1)
-    enc = model.FirstStageEncoder(4, VAE, precision=a.first_stage_precision)
-    if a.ckpt:
-        print(enc.load_state_dict(checkpoint.denoiser_state_dict(checkpoint.read_state_dict(a.ckpt), "first_stage_model."), strict=False))
-    else:
-        enc.load_state_dict(synth.synth_state_dict({k: list(v.shape) for k, v in enc.state_dict().items()}), strict=True)
-    enc = enc.to(dev)
+    enc = first_stage_encoder(a, dev)
     _, _, h, w = configs.SHAPES["full"]
     hint = g["cond_feat"][T:]                                                   # T synthetic layouts, cycled over the N video frames
     layout = torch.stack([hint[i % T] for i in range(N)])
