@@ -44,7 +44,8 @@ const char* pnc_version(void);
  *  still 8 (additive): + pnc_attn_uses_text_kernel.  One dispatch is narrower: the few-key kernel takes key buffers whose row count
  *  kvH * kvW is a multiple of 8 only, a ragged buffer (77 rows) runs on the general kernel — same attention, see PncAttnParams.kv_valid;
  *  still 8 (additive): + pnc_gemm_wsplit_f16;
- *  still 8 (additive): + pnc_frames_renoise) */
+ *  still 8 (additive): + pnc_frames_renoise;
+ *  still 8 (additive): + pnc_latent_renoise_masked, + pnc_mask_pool_u8, + pnc_u8_select) */
 #define PNC_ABI_VERSION 8
 int pnc_abi_version(void);
 /* hex SHA-256 of the sources + compile flags the library was built from (panacea_amd/build.py computes the same digest over
@@ -746,6 +747,49 @@ int pnc_attn_text_split_f16(const void* q, const void* q_lo, int64_t ldq, const 
 int pnc_u8_to_tokens_f16(const uint8_t* src, const float* lut, int F, int Npix, int C, int Cpad,
                          void* out16, void* out16_lo, void* stream);
 int pnc_tokens_to_u8(const float* x, int ld, int64_t M, int C, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * 8. Region editing: camera views and pixel regions of a recorded clip kept instead of whole frames (pnc_frames_renoise with the
+ *    selector per pixel, and the two byte kernels around it).  Additive under ABI 8.  All three entries launch 256-thread
+ *    workgroups on the caller's stream, allocate nothing and do not synchronise; every store is an ordinary vector store; nothing
+ *    is launched on a refusal, and PNC_EINVAL is checked before PNC_EALIGN.  The reference has no counterpart: it has no sampling
+ *    entry that starts from a clip (see pnc_frames_renoise).
+ *
+ *    pnc_latent_renoise_masked: z, noise, x, out contiguous fp32 [T][C][Npix] (the latent layout of pnc_frames_renoise), sigma [T]
+ *    fp32, mask [T][Npix] fp32, all on the device; row t of the mask serves each of the C planes of frame t.  Element (t, c, p) is
+ *    KEPT iff mask[t][p] > 0 — 0.0, -0.0, negative and NaN do not keep, the rule of pnc_frames_renoise's keep[t]:
+ *        kept, sigma[t] == 0 (either sign) : out = z bit for bit, the noise is not read
+ *        kept, otherwise                   : out = z + (noise * sigma[t])      the product rounded to fp32 on its own, then the sum
+ *                                                                               (no FMA contraction, as pnc_frames_renoise)
+ *        not kept                          : out = x bit for bit
+ *    A select, never an arithmetic blend: the operand that is not selected is inert — NaN in noise or z at elements that are not
+ *    kept, NaN noise in frames with sigma 0 and NaN x at kept elements leave no trace in out.  out may be x (every element is
+ *    read before it is written, and only by the thread that writes it), never z, noise or mask.  mask and x are both required:
+ *    the launch that keeps everything without them is pnc_frames_renoise.  A plane moves in 16-byte loads and stores between the
+ *    16-byte boundaries of its run in out when its runs in z, noise and x sit at the same offset from a boundary, with up to three
+ *    single elements either side, and element by element otherwise; every 4-byte alignment and every Npix works (with
+ *    Npix % 4 != 0 the planes of a frame start at different offsets, and the mask index starts again at 0 in every plane).
+ *      PNC_EINVAL  a NULL z, noise, sigma, mask, x or out, T < 1, C < 1, Npix < 1, C * Npix > 2^40,
+ *                  T * C * ceil(Npix / 1024) >= 2^31;
+ *      PNC_EALIGN  any pointer not 4-byte aligned.
+ *
+ *    pnc_mask_pool_u8: a pixel mask uint8 [T][H][W] (contiguous, at ANY byte address; nonzero = this pixel is kept) -> the latent
+ *    selector fp32 [T][H/f][W/f]:
+ *        out[t][y][x] = 1.0f iff EVERY one of the f x f bytes mask_u8[t][y*f .. y*f+f-1][x*f .. x*f+f-1] is nonzero, else 0.0f
+ *    so a latent cell that the first stage computed partly from pixels that will be regenerated never counts as known.
+ *      PNC_EINVAL  a NULL pointer, T < 1, H < 1, W < 1, f < 1, f > 16, H % f != 0, W % f != 0, T * (H/f) * (W/f) > 2^38;
+ *      PNC_EALIGN  out not 4-byte aligned.
+ *
+ *    pnc_u8_select: src, gen, out uint8 [npix][C] (contiguous, at ANY byte address), mask_u8 uint8 [npix], 1 <= C <= 4:
+ *        out[p][c] = mask_u8[p] != 0 ? src[p][c] : gen[p][c]          the mask is per PIXEL: all C bytes of a pixel go together
+ *    out may be gen (bytes are read before they are written, by the thread that writes them); out == src is refused.  Exactly
+ *    npix * C bytes are written.
+ *      PNC_EINVAL  a NULL pointer, npix < 1, npix > 2^40, C < 1, C > 4, out == src.
+ * ------------------------------------------------------------------------- */
+int pnc_latent_renoise_masked(const float* z, const float* noise, const float* sigma, const float* mask, const float* x, float* out,
+                              int T, int C, int64_t Npix, void* stream);
+int pnc_mask_pool_u8(const uint8_t* mask_u8, float* out, int T, int H, int W, int f, void* stream);
+int pnc_u8_select(const uint8_t* src, const uint8_t* gen, const uint8_t* mask_u8, uint8_t* out, int64_t npix, int C, void* stream);
 
 #ifdef __cplusplus
 }

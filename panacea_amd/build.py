@@ -21,7 +21,7 @@ LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libpanacea_hip.so"
 SOURCES = ["gemm.hip", "gemm_plain.hip", "gemm_conv3x3.hip", "gemm_stencil_tile.hip", "gemm_conv1d.hip", "gemm_plain_ws.hip",
            "gemm_conv3x3_ws.hip", "gemm_conv1d_ws.hip", "attn.hip", "attn_split.hip", "attn_frame.hip", "norm.hip", "misc.hip", "stats.hip",
-           "image.hip", "attn_frame_split.hip", "attn_text_split.hip"]
+           "image.hip", "attn_frame_split.hip", "attn_text_split.hip", "region.hip"]
 HEADERS = [CSRC / "common.h", CSRC / "attn_check.h", CSRC / "gemm_kernel.h", CSRC / "gemm_dispatch.h", CSRC / "gemm_glds_body.inc", CSRC / "gemm_geglu_persist_body.inc", CSRC / "gemm_stencil_tile_body.inc",
            ROOT / "include" / "panacea_hip.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -156,6 +156,9 @@ _SIGNATURES = {
     "pnc_u8_to_tokens_f16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "pnc_tokens_to_u8": (_I, [_P, _I, _L, _I, _P, _P]),
     "pnc_frames_renoise": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _P]),
+    "pnc_latent_renoise_masked": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _P]),
+    "pnc_mask_pool_u8": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "pnc_u8_select": (_I, [_P, _P, _P, _P, _L, _I, _P]),
 }
 
 _lib = None
@@ -691,6 +694,59 @@ def frames_renoise(z, noise, sigma, out, keep=None, x=None):
     _check(_timed("elementwise", 0.0, 12.0 * z.numel(), load().pnc_frames_renoise, _ptr(z, f32, "z"), _ptr(noise, f32, "noise"),
                   _ptr(sigma, f32, "sigma"), _ptr(keep, f32, "keep"), _ptr(x, f32, "x"), _ptr(out, f32, "out"), T, Cch, Npix,
                   _stream()), "pnc_frames_renoise")
+
+
+def latent_renoise_masked(z, noise, sigma, mask, x, out):
+    """pnc_latent_renoise_masked on (T, C, ...) fp32 latents: per element out = z + noise * sigma[t] where mask[t] > 0 at its pixel,
+    x elsewhere; `mask`: (T, ...) fp32 of a frame's pixels (one row for the C planes), `sigma`: [T] fp32.  `out` may be `x`"""
+    f32 = torch.float32
+    T, Cch = z.shape[0], z.shape[1]
+    for name, t in (("z", z), ("noise", noise), ("x", x), ("out", out)):
+        if t.shape != z.shape or not t.is_contiguous():
+            raise PncError(f"latent_renoise_masked: {name} is a contiguous {tuple(z.shape)} latent, got {tuple(t.shape)} "
+                           f"(contiguous: {t.is_contiguous()})")
+    if sigma.shape != (T,) or not sigma.is_contiguous():
+        raise PncError(f"latent_renoise_masked: sigma is a contiguous [{T}] vector, got {tuple(sigma.shape)}")
+    if mask.shape != (T,) + tuple(z.shape[2:]) or not mask.is_contiguous():
+        raise PncError(f"latent_renoise_masked: mask is a contiguous {(T,) + tuple(z.shape[2:])} selector, got {tuple(mask.shape)} "
+                       f"(contiguous: {mask.is_contiguous()})")
+    Npix = z[0, 0].numel() if z.dim() > 2 else 1
+    # what the entry must move at most: z, noise and out of every element, the mask once per frame (x only where nothing is kept)
+    _check(_timed("elementwise", 0.0, 12.0 * z.numel() + 4.0 * mask.numel(), load().pnc_latent_renoise_masked, _ptr(z, f32, "z"),
+                  _ptr(noise, f32, "noise"), _ptr(sigma, f32, "sigma"), _ptr(mask, f32, "mask"), _ptr(x, f32, "x"),
+                  _ptr(out, f32, "out"), T, Cch, Npix, _stream()), "pnc_latent_renoise_masked")
+
+
+def mask_pool_u8(mask_u8, f, out):
+    """pnc_mask_pool_u8: a (T, H, W) uint8 pixel mask -> the (T, H / f, W / f) fp32 selector `out`: 1.0 where all f x f bytes of the
+    cell are nonzero, 0.0 elsewhere"""
+    if mask_u8.dim() != 3 or not mask_u8.is_contiguous():
+        raise PncError(f"mask_pool_u8: mask_u8 is a contiguous (T, H, W) byte mask, got {tuple(mask_u8.shape)} "
+                       f"(contiguous: {mask_u8.is_contiguous()})")
+    T, H, W = mask_u8.shape
+    if isinstance(f, bool) or not isinstance(f, int) or not 1 <= f <= 16 or H % f or W % f:
+        raise PncError(f"mask_pool_u8: f is an int in 1 .. 16 that divides {H} and {W}, got {f!r}")
+    if out.shape != (T, H // f, W // f) or not out.is_contiguous():
+        raise PncError(f"mask_pool_u8: out is a contiguous {(T, H // f, W // f)} selector, got {tuple(out.shape)}")
+    _check(_timed("elementwise", 0.0, 1.0 * mask_u8.numel() + 4.0 * out.numel(), load().pnc_mask_pool_u8,
+                  _ptr(mask_u8, torch.uint8, "mask_u8"), _ptr(out, torch.float32, "out"), T, H, W, f, _stream()), "pnc_mask_pool_u8")
+
+
+def u8_select(src, gen, mask_u8, out):
+    """pnc_u8_select on (..., C <= 4) uint8 channels-last frames: out = src where the pixel's byte of `mask_u8` (the frames' shape
+    without the channels) is nonzero, gen elsewhere.  `out` may be `gen`, never `src`"""
+    for name, t in (("src", src), ("gen", gen), ("out", out)):
+        if t.shape != src.shape or not t.is_contiguous():
+            raise PncError(f"u8_select: {name} holds contiguous {tuple(src.shape)} frames, got {tuple(t.shape)} "
+                           f"(contiguous: {t.is_contiguous()})")
+    if src.dim() < 2 or not 1 <= src.shape[-1] <= 4:
+        raise PncError(f"u8_select: channels-last frames of 1 .. 4 channels, got {tuple(src.shape)}")
+    if mask_u8.shape != src.shape[:-1] or not mask_u8.is_contiguous():
+        raise PncError(f"u8_select: mask_u8 is a contiguous {tuple(src.shape[:-1])} byte mask, got {tuple(mask_u8.shape)}")
+    u8 = torch.uint8
+    _check(_timed("elementwise", 0.0, 3.0 * src.numel() + 1.0 * mask_u8.numel(), load().pnc_u8_select, _ptr(src, u8, "src"),
+                  _ptr(gen, u8, "gen"), _ptr(mask_u8, u8, "mask_u8"), _ptr(out, u8, "out"), mask_u8.numel(), src.shape[-1], _stream()),
+           "pnc_u8_select")
 
 
 def tokens_to_nchw_f32(x32, ld, F, Npix, Cch, out32):

@@ -56,6 +56,88 @@ def capability(backend, name: str):
     return fn
 
 
+def region_capability(backend, name: str):
+    """the backend's `name` wrapper of the region-editing kernels (section 8 of include/panacea_hip.h), by name like `capability`"""
+    fn = getattr(backend, name, None)
+    if fn is None:
+        raise NotImplementedError(f"this backend has no `{name}`: a keep mask needs the region-editing kernels "
+                                  f"(pnc_{name} of include/panacea_hip.h)")
+    return fn
+
+
+def keep_mask_u8(mask_u8, T: int, H: int, W: int, what: str = "keep_mask_u8") -> torch.Tensor:
+    """`mask_u8` checked as a (T, H, W) uint8 pixel mask (nonzero = this pixel is kept), contiguous"""
+    if not isinstance(mask_u8, torch.Tensor) or mask_u8.dtype != torch.uint8 or mask_u8.shape != (T, H, W):
+        raise ValueError(f"{what}: a ({T}, {H}, {W}) uint8 mask of the clip's size, got "
+                         f"{tuple(mask_u8.shape) if isinstance(mask_u8, torch.Tensor) else type(mask_u8).__name__}"
+                         f"{' ' + str(mask_u8.dtype) if isinstance(mask_u8, torch.Tensor) else ''}")
+    return mask_u8.detach().contiguous()
+
+
+def pool_keep_mask(mask_u8: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """a (T, H, W) uint8 pixel mask -> the (T, h, w) fp32 selector of the latent (pnc_mask_pool_u8 at f = H / h = W / w): a latent
+    cell is 1.0 only where all of its f x f pixels are kept, so a cell the first stage computed partly from pixels that will be
+    regenerated never counts as known"""
+    from . import engine as E
+    pool = region_capability(E.backend(), "mask_pool_u8")
+    if not isinstance(mask_u8, torch.Tensor) or mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3 or 0 in mask_u8.shape:
+        raise ValueError(f"pool_keep_mask: a (T, H, W) uint8 mask, got "
+                         f"{tuple(mask_u8.shape) if isinstance(mask_u8, torch.Tensor) else type(mask_u8).__name__}")
+    T, H, W = mask_u8.shape
+    h, w = operator.index(h), operator.index(w)
+    if h < 1 or w < 1 or H % h or W % w or H // h != W // w or not 1 <= H // h <= 16:
+        raise ValueError(f"pool_keep_mask: a {H} x {W} mask pools to {h} x {w} by one factor in 1 .. 16 only")
+    out = torch.empty((T, h, w), dtype=torch.float32, device=mask_u8.device)
+    pool(mask_u8.detach().contiguous(), H // h, out)
+    return out
+
+
+def select_u8(src_u8: torch.Tensor, gen_u8: torch.Tensor, mask_u8: torch.Tensor) -> torch.Tensor:
+    """(T, H, W, C) uint8 frames: `src_u8` where the pixel's byte of the (T, H, W) `mask_u8` is nonzero, `gen_u8` elsewhere
+    (pnc_u8_select), a new tensor"""
+    from . import engine as E
+    select = region_capability(E.backend(), "u8_select")
+    for name, t in (("src_u8", src_u8), ("gen_u8", gen_u8), ("mask_u8", mask_u8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f"select_u8: {name} is a uint8 tensor, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if src_u8.dim() != 4 or gen_u8.shape != src_u8.shape or mask_u8.shape != src_u8.shape[:3]:
+        raise ValueError(f"select_u8: (T, H, W, C) frames twice and their (T, H, W) mask, got {tuple(src_u8.shape)}, "
+                         f"{tuple(gen_u8.shape)} and {tuple(mask_u8.shape)}")
+    out = torch.empty_like(gen_u8, memory_format=torch.contiguous_format)
+    select(src_u8.detach().contiguous(), gen_u8.detach().contiguous(), mask_u8.detach().contiguous(), out)
+    return out
+
+
+def view_mask(T: int, H: int, W: int, views: int, keep_views, device="cpu") -> torch.Tensor:
+    """a (T, H, W) uint8 mask of a panorama of `views` camera views side by side: 255 in the column band of every view in
+    `keep_views`, 0 elsewhere"""
+    views = operator.index(views)
+    if views < 1 or W % views:
+        raise ValueError(f"view_mask: {W} columns do not split into {views} views")
+    keep_views = tuple(operator.index(v) for v in keep_views)
+    if any(not 0 <= v < views for v in keep_views):
+        raise ValueError(f"view_mask: views {keep_views} outside 0 .. {views - 1}")
+    mask = torch.zeros((T, H, W), dtype=torch.uint8)
+    band = W // views
+    for v in keep_views:
+        mask[:, :, v * band:(v + 1) * band] = 255
+    return mask.to(device)
+
+
+def rect_mask(T: int, H: int, W: int, rect, device="cpu") -> torch.Tensor:
+    """a (T, H, W) uint8 mask that is 0 inside the rectangle rect = (y0, x0, y1, x1) (rows y0 .. y1 - 1, columns x0 .. x1 - 1 of
+    every frame: what is re-rendered) and 255 outside"""
+    try:
+        y0, x0, y1, x1 = (operator.index(v) for v in rect)
+    except (TypeError, ValueError):
+        raise ValueError(f"rect_mask: rect is four integers (y0, x0, y1, x1), got {rect!r}") from None
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError(f"rect_mask: a non-empty rectangle inside {H} x {W} expected, got {(y0, x0, y1, x1)}")
+    mask = torch.full((T, H, W), 255, dtype=torch.uint8)
+    mask[:, y0:y1, x0:x1] = 0
+    return mask.to(device)
+
+
 def frames_u8(x: torch.Tensor, what: str) -> torch.Tensor:
     """`x` as contiguous (F, H, W, C) uint8 frames; a (b, t, H, W, C) clip is flattened over its first two dimensions"""
     if x.dtype != torch.uint8:

@@ -156,7 +156,8 @@ def edit_start_step(strength: float, num_steps: int) -> int:
 def edit_frames(network, first_stage_dec, first_stage_enc, frames_u8: torch.Tensor, cond: Dict[str, torch.Tensor],
                 uc: Dict[str, torch.Tensor], noise: torch.Tensor, *, strength: float = 0.6, keep: Sequence[int] = (),
                 num_steps: int = 25, cfg_scale: float = 5.0, sampler=None, denoiser=None, generator=None,
-                sample_posterior: bool = True, scale_factor: float = SCALE_FACTOR, hoist: bool = True, callback=None) -> torch.Tensor:
+                sample_posterior: bool = True, scale_factor: float = SCALE_FACTOR, hoist: bool = True, callback=None,
+                keep_mask_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A recorded clip re-rendered under `cond` / `uc` (another prompt, another layout), on one device: frames_u8 (T, H, W, 3) uint8
     -> (T, H, W, 3) uint8.  The clip is encoded (z = scale_factor * first_stage_enc.encode_u8(frames_u8): a posterior draw from
     `generator`, or the mean without `sample_posterior`), noised to the level the schedule has at
@@ -169,7 +170,17 @@ def edit_frames(network, first_stage_dec, first_stage_enc, frames_u8: torch.Tens
     cfg_scale, hoist: see sample_frames; kept frames need a sampler that serves them (sampling.ClipSource).  `callback(i, x)` sees the
     latent after every step.
 
-    Refused before the first launch: first stages without encode_u8 / decode_u8 (TypeError), a backend without pnc_frames_renoise or
+    `keep_mask_u8` (region editing): a (T, H, W) uint8 mask of the clip's size, nonzero = this pixel is kept — a camera view
+    (image.view_mask), everything outside a rectangle (image.rect_mask), any region.  The clip is encoded as without it; the mask
+    is pooled to the latent (image.pool_keep_mask at f = H / h: a latent cell counts as known only where all of its f x f pixels
+    are kept), the sampler runs on ClipSource(z, noise, keep, mask=pooled), which puts the kept cells back at every noise level, and
+    the result is image.select_u8(frames_u8, decoded, keep_mask_u8): every kept pixel is the recorded byte itself, not the first
+    stage's reconstruction of it.  Frames in `keep` that the mask does not cover stay that reconstruction.  Generated pixels right
+    at the seam see kept latents through the decoder's receptive field; the kept region is not eroded for it.  None: the path above,
+    launch for launch.
+
+    Refused before the first launch: a malformed `keep_mask_u8` (ValueError), a backend without the region-editing kernels it needs
+    (NotImplementedError), a sampler that does not keep frames given a mask (NotImplementedError), first stages without encode_u8 / decode_u8 (TypeError), a backend without pnc_frames_renoise or
     the image-boundary kernels (NotImplementedError), a network carrying a frame or view shard (NotImplementedError: one device), a
     malformed clip or `noise`, T != num_frames, `strength` outside (0, 1] and `keep` slots outside 0 .. T-1 (ValueError)."""
     if not hasattr(first_stage_dec, "decode_u8"):
@@ -201,16 +212,28 @@ def edit_frames(network, first_stage_dec, first_stage_enc, frames_u8: torch.Tens
         raise ValueError(f"keep: frame slots (integers) expected, got {keep!r}") from None
     if any(not 0 <= s < T for s in keep) or len(set(keep)) != len(keep):
         raise ValueError(f"keep: distinct frame slots in 0 .. {T - 1} expected, got {keep}")
+    if keep_mask_u8 is not None:
+        keep_mask_u8 = image.keep_mask_u8(keep_mask_u8, T, f.shape[1], f.shape[2])
+        if f.shape[1] // h > 16:
+            raise ValueError(f"keep_mask_u8: the mask pools by at most 16, the clip is {f.shape[1] // h} times the latent")
+        for name in ("mask_pool_u8", "u8_select"):
+            image.region_capability(engine.backend(), name)
+        sampling._masked_capability()
     smp, den = _sampler_stack(noise.device, num_steps, cfg_scale, sampler, denoiser)
     start_step = edit_start_step(strength, smp.num_steps)
-    why = smp._keep_refusal() if keep else None
+    why = smp._keep_refusal() if keep or keep_mask_u8 is not None else None
     if why is not None:
         raise NotImplementedError(f"{type(smp).__name__} does not keep frames {why}")
     with torch.no_grad():
         z = scale_factor * first_stage_enc.encode_u8(f.to(noise.device), generator=generator, sample=sample_posterior)
         if z.shape != noise.shape:
             raise ValueError(f"the first stage encodes the clip to {tuple(z.shape)}, noise is {tuple(noise.shape)}")
-        source = sampling.ClipSource(z.to(torch.float32), noise.to(torch.float32), keep)
+        pooled = None
+        if keep_mask_u8 is not None:
+            keep_mask_u8 = keep_mask_u8.to(noise.device)
+            pooled = image.pool_keep_mask(keep_mask_u8, h, w)
+        source = sampling.ClipSource(z.to(torch.float32), noise.to(torch.float32), keep, mask=pooled)
         z_out = smp(sampling.BoundDenoiser(den, network), None, cond, uc, network=network if hoist else None, callback=callback,
                     start_step=start_step, source=source)
-        return first_stage_dec.decode_u8(z_out / scale_factor)
+        decoded = first_stage_dec.decode_u8(z_out / scale_factor)
+        return decoded if keep_mask_u8 is None else image.select_u8(f.to(noise.device), decoded, keep_mask_u8)

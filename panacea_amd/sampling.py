@@ -213,15 +213,32 @@ def _renoise_capability():
     return fn
 
 
+def _masked_capability():
+    """the backend's `latent_renoise_masked` wrapper (pnc_latent_renoise_masked), looked up by name like `frames_renoise` and only
+    for a source that carries a mask"""
+    from . import engine as E
+    fn = getattr(E.backend(), "latent_renoise_masked", None)
+    if fn is None:
+        raise NotImplementedError("this backend has no `latent_renoise_masked`: a clip source with a mask needs "
+                                  "pnc_latent_renoise_masked of include/panacea_hip.h")
+    return fn
+
+
 class ClipSource:
     """A recorded clip to start a schedule from (clip editing): `z` (T, C, h, w) fp32, the clip's latents already multiplied by
     scale_factor; `noise`, ONE fixed draw of that shape; `keep`, the frame slots (0 .. T-1, each once, possibly none) that come out
     as they went in.  The schedule starts at z + sigmas[start_step] * noise, and after every step the kept frames are rewritten as
     z + sigma_next * noise: with a fixed noise that is where a deterministic Euler step itself lands when the denoised frame is z
     (x + (sigma_next - sigma) * (x - z) / sigma at x = z + sigma * noise), so the other frames are denoised next to frames that sit
-    at their own noise level, and the kept frames are z exactly once sigma_next is 0.  Both are one pnc_frames_renoise launch."""
+    at their own noise level, and the kept frames are z exactly once sigma_next is 0.  Both are one pnc_frames_renoise launch.
 
-    def __init__(self, z: torch.Tensor, noise: torch.Tensor, keep=()):
+    `mask` (region editing): a (T, h, w) tensor on z's device that keeps latent PIXELS — bool, uint8 (nonzero keeps) or fp32 (> 0
+    keeps; 0.0, -0.0, negatives and NaN do not).  The fact above holds element by element, so it holds for any subset of elements:
+    what is kept is the union of the mask with the whole frames in `keep`, held as `selector`, contiguous fp32 0 / 1 made once
+    here, and the put-back is one pnc_latent_renoise_masked launch in place instead of the pnc_frames_renoise one.  A source with a
+    mask counts as keeping something even where the mask is empty (the selector lives on the device)."""
+
+    def __init__(self, z: torch.Tensor, noise: torch.Tensor, keep=(), mask: Optional[torch.Tensor] = None):
         for name, t in (("z", z), ("noise", noise)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
                 raise TypeError(f"ClipSource: {name} is an fp32 tensor, got "
@@ -240,8 +257,27 @@ class ClipSource:
             raise ValueError(f"ClipSource: keep slots {keep} outside 0 .. {T - 1}")
         if len(set(keep)) != len(keep):
             raise ValueError(f"ClipSource: keep slots {keep} name a frame twice")
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+                raise TypeError(f"ClipSource: mask is a bool, uint8 or fp32 tensor, got "
+                                f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+            if mask.shape != (T,) + tuple(z.shape[2:]) or mask.device != z.device:
+                raise ValueError(f"ClipSource: mask is {(T,) + tuple(z.shape[2:])} on z's device {z.device}, got {tuple(mask.shape)} "
+                                 f"on {mask.device}")
         self.z, self.noise, self.keep = z.detach().contiguous(), noise.detach().contiguous(), tuple(sorted(keep))
         self._keep_vec = None
+        self.selector = None
+        if mask is not None:
+            kept = mask.detach() if mask.dtype == torch.bool else mask.detach() > 0
+            if self.keep:
+                kept = kept.clone()
+                kept[list(self.keep)] = True
+            self.selector = kept.to(torch.float32).contiguous()
+
+    @property
+    def keeps(self) -> bool:
+        """whether the put-back after a step launches anything: kept frames, or a mask"""
+        return bool(self.keep) or self.selector is not None
 
     def keep_vector(self) -> torch.Tensor:
         """[T] fp32 on z's device: 1 for a kept frame, 0 elsewhere (made once)"""
@@ -258,8 +294,10 @@ class ClipSource:
 
     def put_back(self, x: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
         """the kept frames of `x` rewritten IN PLACE as z + sigma * noise (the others are not touched; no launch when nothing is
-        kept); returns `x`"""
-        if self.keep:
+        kept); with a mask, the kept elements, in one pnc_latent_renoise_masked launch; returns `x`"""
+        if self.selector is not None:
+            _masked_capability()(self.z, self.noise, sigma.contiguous(), self.selector, x, x)
+        elif self.keep:
             _renoise_capability()(self.z, self.noise, sigma.contiguous(), x, keep=self.keep_vector(), x=x)
         return x
 
@@ -277,7 +315,7 @@ class _Edit:
 
     def after(self, callback):
         """`callback` behind the put-back of the step's output (the loops hand every step's latent to their callback)"""
-        if not self.source.keep:
+        if not self.source.keeps:
             return callback
 
         def hook(i, x):
@@ -317,11 +355,13 @@ class _Sampler:
             return start_step, callback, (lambda: x * torch.sqrt(1.0 + sig[0] ** 2.0) if start_step == 0 else x)
         if not isinstance(source, ClipSource):
             raise TypeError(f"source: a sampling.ClipSource, got {type(source).__name__}")
-        why = self._keep_refusal() if source.keep else None
+        why = self._keep_refusal() if source.keeps else None
         if why is not None:
             raise NotImplementedError(f"{type(self).__name__} does not keep frames {why}: kept frames are served by EulerEDMSampler "
                                       "without churn, DPMPP2MSampler and LinearMultistepSampler under VanillaCFG or no guider")
         _renoise_capability()
+        if source.selector is not None:
+            _masked_capability()
         edit = _Edit(source, sig, start_step)
         return start_step, edit.after(callback), edit.start
 

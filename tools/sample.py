@@ -15,13 +15,17 @@ per-view JPEGs + panorama GIF.  With `--ckpt <engine checkpoint>` the reference'
     python tools/sample.py --edit --strength 0.6 --keep 0,7    (clip editing, pipeline.edit_frames: a first sample is decoded to uint8
                                                            frames, then re-rendered under the swapped prompt from 60 % of the
                                                            schedule on, frames 0 and 7 kept as they are)
+    python tools/sample.py --edit --keep-views 0,3             (region editing: camera views 0 and 3 of every frame stay the recorded
+                                                           pixels, the other four are generated next to them)
+    python tools/sample.py --edit --edit-rect 64,1024,192,1536 (only rows 64 .. 191, columns 1024 .. 1535 are re-rendered; with
+                                                           --keep-views the kept sets are united)
 """
 import argparse, json, sys, time
 from pathlib import Path
 import torch
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from panacea_amd import build_network, checkpoint, configs, engine, pipeline, sampling, synth   # noqa: E402
+from panacea_amd import build_network, checkpoint, configs, engine, image, pipeline, sampling, synth   # noqa: E402
 from panacea_amd.nn import model                                               # noqa: E402
 
 VAE = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4, 4],
@@ -29,6 +33,7 @@ VAE = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3,
 SAMPLERS = {"euler": "EulerEDMSampler", "heun": "HeunEDMSampler", "euler_a": "EulerAncestralSampler",
             "dpmpp2s_a": "DPMPP2SAncestralSampler", "dpmpp2m": "DPMPP2MSampler", "lms": "LinearMultistepSampler"}
 P = "sgm.modules.diffusionmodules."
+VIEWS = 6        # camera views side by side in a frame
 DISCRETIZATIONS = {"ddpm": "LegacyDDPMDiscretization", "edm": "EDMDiscretization"}
 
 
@@ -104,6 +109,11 @@ def main():
                     help="--edit: the share of the schedule that runs, in (0, 1]: the clip is noised to the level of step "
                          "floor((1 - strength) * steps) and sampled from there")
     ap.add_argument("--keep", default="", metavar="SLOTS", help="--edit: comma-separated frame slots kept as they are, e.g. 0,7")
+    ap.add_argument("--keep-views", default="", metavar="VIEWS",
+                    help=f"--edit: comma-separated camera views (0 .. {VIEWS - 1}, column bands of the panorama) whose recorded pixels are kept")
+    ap.add_argument("--edit-rect", default="", metavar="Y0,X0,Y1,X1",
+                    help="--edit: only the pixels of rows Y0 .. Y1-1, columns X0 .. X1-1 are re-rendered, everything outside is kept; "
+                         "with --keep-views the kept sets are united")
     a = ap.parse_args()
     if a.windows < 0:
         ap.error("--windows takes N >= 1")
@@ -115,6 +125,22 @@ def main():
         ap.error("--keep takes comma-separated frame slots")
     if keep and not a.edit:
         ap.error("--keep belongs to --edit")
+    try:
+        keep_views = tuple(int(s) for s in a.keep_views.split(",") if s.strip())
+    except ValueError:
+        ap.error("--keep-views takes comma-separated camera views")
+    if any(not 0 <= v < VIEWS for v in keep_views):
+        ap.error(f"--keep-views takes camera views in 0 .. {VIEWS - 1}")
+    rect = None
+    if a.edit_rect:
+        try:
+            rect = tuple(int(s) for s in a.edit_rect.split(","))
+        except ValueError:
+            ap.error("--edit-rect takes four integers Y0,X0,Y1,X1")
+        if len(rect) != 4 or not (0 <= rect[0] < rect[2] and 0 <= rect[1] < rect[3]):
+            ap.error("--edit-rect takes four integers Y0,X0,Y1,X1 with 0 <= Y0 < Y1 and 0 <= X0 < X1")
+    if (keep_views or rect) and not a.edit:
+        ap.error("--keep-views and --edit-rect belong to --edit")
     dev = torch.device("cuda", 0)
     kw = configs.with_frames(configs.get("full"), a.frames)
     net = build_network(kw)
@@ -144,6 +170,12 @@ def main():
         enc = first_stage_encoder(a, dev)
         cond, uc = dict(cond, crossattn=g["crossattn"][0:1]), dict(uc, crossattn=g["crossattn"][1:2])       # "another prompt"
         noise = torch.randn(T, 4, h, w, generator=torch.Generator().manual_seed(a.seed + 1)).to(dev)
+        keep_mask = None               # the pixels kept: the union of the kept views and of everything outside the rectangle
+        if keep_views:
+            keep_mask = image.view_mask(*clip.shape[:3], VIEWS, keep_views, dev)
+        if rect:
+            outside = image.rect_mask(*clip.shape[:3], rect, dev)
+            keep_mask = outside if keep_mask is None else torch.maximum(keep_mask, outside)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     smp = sampling.from_config({"target": P + "sampling." + SAMPLERS[a.sampler],
                                 "params": {"num_steps": a.steps,
@@ -158,7 +190,7 @@ def main():
         elif a.edit:
             frames = pipeline.edit_frames(net, fs, enc, clip, cond, uc, noise, strength=a.strength, keep=keep, num_steps=a.steps,
                                           sampler=smp, denoiser=denoiser_config(a.prediction),
-                                          generator=torch.Generator(device=dev).manual_seed(a.seed))
+                                          generator=torch.Generator(device=dev).manual_seed(a.seed), keep_mask_u8=keep_mask)
         else:
             frames = pipeline.sample_frames(net, fs, cond, uc, noise, num_steps=a.steps, sampler=smp,
                                             denoiser=denoiser_config(a.prediction), output="uint8" if a.u8 else "float")
@@ -171,7 +203,8 @@ def main():
     if a.edit:
         start = pipeline.edit_start_step(a.strength, a.steps)
         what = (f"{a.sampler} ({a.prediction}-prediction, {a.discretization} schedule): edit of {T} frames at strength {a.strength} (steps "
-                f"{start} .. {a.steps - 1} of {a.steps}), kept {keep or 'none'}, encode + decode, {tuple(frames.shape)}")
+                f"{start} .. {a.steps - 1} of {a.steps}), kept {kept_summary(keep, keep_views, rect, keep_mask)}, encode + decode, "
+                f"{tuple(frames.shape)}")
     if u8:
         print(f"{what}: {dt:.2f} s (uint8, range {frames.min().item()} .. {frames.max().item()})")
     else:
@@ -184,6 +217,16 @@ def main():
     checkpoint.save_view_frames(frames, str(out), [f"scene__{v}__000" for v in range(6)], view_width=width // 6)
     checkpoint.save_gif(frames[:, ::4, ::4] if u8 else frames[:, :, ::4, ::4], str(out / "panorama_quarter.gif"))
     print("wrote", out)
+
+
+def kept_summary(keep, keep_views, rect, keep_mask):
+    """what an edit kept, for the printed line: frame slots, camera views, the outside of the rectangle, the share of pixels"""
+    parts = ([f"frames {keep}"] if keep else []) + ([f"views {keep_views}"] if keep_views else [])
+    if rect:
+        parts.append(f"everything outside rows {rect[0]} .. {rect[2] - 1}, columns {rect[1]} .. {rect[3] - 1}")
+    if keep_mask is not None:
+        parts.append(f"{100.0 * (keep_mask != 0).float().mean().item():.1f} % of the pixels as recorded")
+    return ", ".join(parts) or "none"
 
 
 def first_stage_encoder(a, dev):
